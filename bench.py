@@ -16,6 +16,10 @@ Launch:  python bench.py --gpus N --steps K --warmup W          (N > 1: this pro
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W      (RANK / LOCAL_RANK / WORLD_SIZE from the env)
 No torch anywhere: the ranks talk through the engine's RCCL communicator; its 128-byte id travels through a file.
+
+A plain run sets up, warms up, times the K steps and prints the line (its roofline comes from the counters of the timed steps).
+--full adds what takes runs of its own: steady-state sweeps, the parity-arithmetic runs, the methanation line at N = 1024 and
+the CPU baselines.  --dump-outputs DIR writes what the last timed step returned, for comparing two builds on the same inputs.
 """
 from __future__ import annotations
 
@@ -56,6 +60,36 @@ HBM_BYTES_PER_PARTICLE_SOLVE = 24 + 1 + 6 * (8 + 4)  # read theta + support flag
 def load_mm_data():
     z = np.load(os.path.join(ROOT, "tests", "golden", "mm_data.npz"))
     return z["t"], z["P_obs"], z["S0"]
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <out_dir>/<name>.npy in float64
+    (<name>_rank<r>.npy with more than one rank), so that two builds can be compared output for output.  Arrays of one row
+    per particle that together exceed this rank's share of 64 MB are cut to a fixed sample of rows, the same rows for every
+    such array, written as `sample_rows`."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(arrays["p_pred"])
+    per_row = {k: a.nbytes // n for k, a in arrays.items() if a.ndim and len(a) == n}
+    budget = DUMP_BYTES_MAX // world - sum(a.nbytes for k, a in arrays.items() if k not in per_row)
+    keep = budget // (sum(per_row.values()) + 8)
+    if keep < n:
+        rows = np.sort(np.random.default_rng(20250205).choice(n, size=keep, replace=False))
+        arrays = {k: (a[rows] if k in per_row else a) for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+
+
+def run_outputs(out):
+    """What run_smc returns to its caller, as arrays: final particles and likelihoods, logZ and the tempering schedule."""
+    rec = out["records"]
+    return {"p_pred": out["p_pred"], "lk": out["lk"], "logZ": [out["logZ"]], "gamma": [r["gamma_new"] for r in rec],
+            "n_accept": [r["n_accept"] for r in rec]}
 
 
 def effective_cpus():
@@ -558,6 +592,8 @@ def methanation_line(args, n, steps, warmup, cpu_seconds):
     eng.synchronize()
     elapsed = float(comm.allreduce_max([time.perf_counter() - t0])[0])
     tm = eng.timing_get()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run_outputs(outs[-1]), rank, world)
     if rank != 0:
         comm.barrier()
         eng.close()
@@ -571,7 +607,7 @@ def methanation_line(args, n, steps, warmup, cpu_seconds):
     # counter traffic of K8 per launch: only from a PMC summary of THIS kernel revision at THIS population (same rule as the MM line)
     traffic, traffic_note = measured_traffic("smc::" + k8_kernel_name(), n, family="k8")
     k8_launches = max(1, tm["solve"]["launches"])
-    cpu = None if (args.no_cpu_baseline or world != 1 or cpu_seconds <= 0) else cpu_baseline_methanation(pkg, cond, guess, cpu_seconds)
+    cpu = None if (not args.full or args.no_cpu_baseline or world != 1 or cpu_seconds <= 0) else cpu_baseline_methanation(pkg, cond, guess, cpu_seconds)
     line = {
         "metric": "particle-mutation-steps/sec", "value": pms / elapsed, "unit": "particle-mutation-steps/s", "n_gpus": world,
         "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
@@ -634,6 +670,8 @@ def bench_methanation_sweeps(args, pkg, eng, s, n):
     eng.synchronize()
     t_mh = time.perf_counter() - t0
     tm = eng.timing_get()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"p_pred": eng.download_particles(pkg.SMC_SET_FILT), "lk": eng.download_lk(pkg.SMC_SET_FILT)})
     print(json.dumps({
         "metric": "particle-mutation-steps/sec", "value": args.meth_sweeps * n / t_mh, "unit": "particle-mutation-steps/s",
         "n_gpus": 1, "steps": args.meth_sweeps, "warmup": 0, "ms_per_step": 1e3 * t_mh / args.meth_sweeps,
@@ -665,7 +703,13 @@ def main():
     ap.add_argument("--particles-total", type=int, default=0,
                     help="STRONG scaling: this many particles in total, split evenly over the --gpus ranks (BASELINE.json: '1->8-GPU "
                          "scaling curve for 10^6 particles'); default 0 = weak scaling with --particles-per-gpu per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: steady-state sweeps, the `exact_mode` and "
+                         "`methanation_n1024` keys (see --no-extra) and `cpu_baseline` (see --no-cpu-baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (final particles, likelihoods, logZ, "
+                         "tempering schedule) as DIR/<name>.npy in float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out `cpu_baseline`")
     ap.add_argument("--cpu-baseline-particles", type=int, default=1000,
                     help="population of the CPU baseline's end-to-end run (1000 = the reference's own run, whose schedule is asserted "
                          "first; SURVEY.md 8(d) also names 10000: ~100 s on 16 cores, nothing to assert against)")
@@ -696,7 +740,7 @@ def main():
     ap.add_argument("--progress", action="store_true",
                     help="methanation only: one line per sweep on stderr and in gpurun_out/bench_methanation_progress.log")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the two extra keys of the default one-GPU line (`exact_mode`: 3 runs in the parity arithmetic; "
+                    help="--full: skip the two extra keys of the one-GPU line (`exact_mode`: 3 runs in the parity arithmetic; "
                          "`methanation_n1024`: one complete methanation run at N = 1024 with its own roofline and cpu_baseline)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -760,11 +804,13 @@ def main():
     timing = eng.timing_get()
     work = eng.work_totals()                     # device-counted: solves that produced their outputs, launches that had work
     eng.timing_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run_outputs(outs[-1]), rank, world)
 
     # steady state (outside the timed region): Metropolis sweeps at gamma = 1 on the final, posterior
     # population - the regime SURVEY.md 8(d) calls "posterior-like"; no stiff stragglers left
     steady = None
-    if world == 1:
+    if world == 1 and args.full:
         eng.timing_enable(True)
         eng.timing_reset()
         eng.upload_particles(pkg.SMC_SET_FILT, outs[-1]["p_pred"])
@@ -904,7 +950,7 @@ def main():
                 traceback.print_exc(file=sys.stderr)
                 result[key] = {"error": f"{type(ex).__name__}: {ex}"}
 
-        if world == 1 and not args.no_extra and not args.exact:
+        if world == 1 and args.full and not args.no_extra and not args.exact:
             # Two more measurements in the SAME process, after the headline's timed region: the price of the
             # parity arithmetic, and the methanation workload's line at N = 1024 - so that both are driver-run numbers
             def exact_mode():
@@ -924,9 +970,9 @@ def main():
                         "same_seeds_as_headline_runs": [1000, 1001, 1002],
                         "tempering_steps_per_run": [o["step"] for o in ox], "logZ": [o["logZ"] for o in ox]}
             guarded("exact_mode", exact_mode)
-            m_args = argparse.Namespace(**{**vars(args), "meth_sweeps": 0, "progress": False})
+            m_args = argparse.Namespace(**{**vars(args), "meth_sweeps": 0, "progress": False, "dump_outputs": None})
             guarded("methanation_n1024", lambda: methanation_line(m_args, 1024, 1, 0, cpu_seconds=0.0 if args.no_cpu_baseline else 4.0))
-        if not args.no_cpu_baseline and world == 1:     # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:     # rank 0 at N = 1 only
             guarded("cpu_baseline", lambda: cpu_baseline(n=args.cpu_baseline_particles))
         print(json.dumps(result), flush=True)
     comm.barrier()

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--workload", "methanation", "--particles-per-gpu", "64"]])
 def test_bench_prints_one_json_line_with_the_contract_fields(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
            "--particles-per-gpu", "20000"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -39,6 +39,29 @@ def test_bench_prints_one_json_line_with_the_contract_fields(extra):
         assert x["runs"] == 3 and x["ms_per_step"] > 0 and x["ratio_to_default"] > 0.5
         assert m["config"]["particles_per_gpu"] == 1024 and m["value"] > 0 and m["roofline"]["frac"] > 0
         assert m["dae_solves"] > 0 and set(m["per_solve"]) == {"bdf_steps", "newton_iters", "factorisations"}
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_only_the_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """Without --full the line carries the headline and its roofline, none of the measurements that take runs of their own;
+    --dump-outputs writes what the last timed run returned, and the same arguments give the same inputs."""
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--particles-per-gpu", "20000", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["roofline"]["achieved"] > 0 and d["steady_state"] is None
+    assert not {"exact_mode", "methanation_n1024", "cpu_baseline"} & set(d)
+    import numpy as np
+    got = {f.stem: np.load(f) for f in out.iterdir()}
+    assert set(got) == {"p_pred", "lk", "logZ", "gamma", "n_accept"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["p_pred"].shape == (20000, 3) and got["lk"].shape == (20000,) and np.all(np.isfinite(got["lk"]))
+    assert got["gamma"][-1] == 1.0 and len(got["gamma"]) == d["tempering_steps_per_run"][-1]
+    assert got["logZ"][0] == d["logZ"][-1]
 
 
 # ---- N > 1 launch plumbing, no GPU needed -------------------------------------------------------------------------------
@@ -140,6 +163,29 @@ def test_measured_fp64_peak_comes_from_a_committed_probe_log(tmp_path, monkeypat
     (tmp_path / "profiles" / "r98_fp64_fma_peak.json").write_text('{"probe": "fp64_fma_peak", "device": "X", "fp64_fma_tflops": 61.25}\n')
     v, note = bench.measured_fp64_peak()
     assert v == 61.25 and "r98_fp64_fma_peak.json" in note
+
+
+def test_dump_outputs_keeps_within_64_mb_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays; per-particle arrays beyond the budget become the same seeded sample of rows."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    n = 1000
+    arrays = {"p_pred": np.arange(3 * n, dtype=np.float32).reshape(n, 3), "lk": -np.arange(n, dtype=np.float64),
+              "logZ": [-1.5], "gamma": [0.1, 1.0]}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    full = {f.stem: np.load(f) for f in (tmp_path / "all").iterdir()}
+    assert set(full) == {"p_pred", "lk", "logZ", "gamma"} and all(a.dtype == np.float64 for a in full.values())
+    assert np.array_equal(full["p_pred"], arrays["p_pred"]) and np.array_equal(full["gamma"], [0.1, 1.0])
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 16 << 10)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    s1, s2 = ({f.stem: np.load(f) for f in (tmp_path / d).iterdir()} for d in ("s1", "s2"))
+    assert sum(a.nbytes for a in s1.values()) <= 16 << 10 and all(np.array_equal(s1[k], s2[k]) for k in s1)
+    rows = s1["sample_rows"].astype(np.int64)
+    assert 0 < len(rows) < n and np.array_equal(s1["p_pred"], full["p_pred"][rows]) and np.array_equal(s1["lk"], full["lk"][rows])
+    bench.dump_outputs(str(tmp_path / "r1"), arrays, rank=1, world=2)
+    assert (tmp_path / "r1" / "lk_rank1.npy").exists()
 
 
 def test_kernel_revision_hash_ignores_comments(tmp_path):

@@ -49,12 +49,12 @@ def main():
     py = sys.executable
     subprocess.run([py, os.path.join(ROOT, "tools", "pmc_summary.py"), os.path.join(F, "pmc_fetch"), os.path.join(F, "pmc_write"),
                     os.path.join(P, f"{tag}_pmc_fetch_write_summary.json"), "--particles-per-gpu", "1000000", "--command",
-                    "python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"], check=False)
+                    "python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra"], check=False)
     subprocess.run([py, os.path.join(ROOT, "tools", "pmc_sq_summary.py"), os.path.join(P, f"{tag}_pmc_sq_summary.json"), "--kernel",
                     "mm_solve_kernel", "--last", "10", "--command", "python3 tools/steady_state.py 1000000 1"] +
                    [os.path.join(F, f"sq{i}") for i in (1, 2, 3, 4)], check=False)
     subprocess.run([py, os.path.join(ROOT, "tools", "pmc_sq_summary.py"), os.path.join(P, f"{tag}_pmc_sq_summary_whole_run.json"),
-                    "--kernel", "mm_solve_kernel", "--command", "python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"] +
+                    "--kernel", "mm_solve_kernel", "--command", "python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra"] +
                    [os.path.join(F, f"sqrun{i}") for i in (1, 2, 3, 4)], check=False)
     if os.path.isdir(os.path.join(F, "k8_pmc_fetch")):      # round 4: K8 (methanation DAE kernel), stamped with the hash of ITS sources
         k8cmd = "python3 bench.py --workload methanation --particles-per-gpu 1024 --steps 1 --warmup 0 --no-cpu-baseline"
