@@ -107,16 +107,37 @@ int smc_set_model_methanation(smc_ctx *ctx, const double *cond, const double *gu
  * kernel (v_rcp, one Newton step, one correction: equal to a / b for normal operands and quotients up to a last bit in about one pair of 2^44, NaN where a / b
  * needs a subnormal or infinite divisor or a * (1 / b) overflows), once with IEEE division; a step attempt runs on the first
  * and is repeated on the second whenever its error norm is not finite.  smc_user_y0, smc_user_obs and smc_user_cost always
- * run with IEEE division. */
+ * run with IEEE division.
+ * Integrator (smc_set_model_user2 / smc_user_model_check2 / smc_user_model_dump_source2, `method`; the functions without
+ * the 2 are method SMC_USER_METHOD_RK45, and an unknown method fails or returns 2):
+ *   SMC_USER_METHOD_RK45  explicit RK45, as above (the default);
+ *   SMC_USER_METHOD_BDF   solve_ivp(method="BDF") as SciPy 1.15's bdf.py has it (variable-order NDF 1-5, Newton with at most four
+ *                         iterations, LU of I - c J with partial pivoting, BdfDenseOutput at t) - for a STIFF model, where
+ *                         RK45 runs on its stability limit.  The source is compiled once, with smc_div(a, b) = a / b, and may
+ *                         define a fifth ingredient (a source that contains the name must define it):
+ *   __device__ void smc_user_jac(double t, const double *y, const double *theta, const double *cond, double *J);
+ *                         J[i * n_states + j] = d dydt[i] / d y[j]; without it J is formed by forward differences as
+ *                         SciPy's num_jac does.  One attempt of the sweep counters (rk_attempts) is one BDF step attempt;
+ *                         smc_user_sweep_counters reports the rest of the work. */
 #define SMC_USER_MAX_STATES 8
+#define SMC_USER_METHOD_RK45 0
+#define SMC_USER_METHOD_BDF 1
 int smc_set_model_user(smc_ctx *ctx, const char *source, int n_states, const double *t, const double *obs, const double *cond,
                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol);
+int smc_set_model_user2(smc_ctx *ctx, const char *source, int n_states, const double *t, const double *obs, const double *cond,
+                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method);
 int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap);
+int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap);
 /* Writes exactly what hiprtc is given for `source` into the existing directory `dir`: smc_user_model.hip (the user's functions
  * followed by the library's kernel) and the four headers it includes - to read, or to compile off line
  * (`hipcc --offload-arch=gfx950 -O3 -ffp-contract=on -fno-fast-math -I dir -S dir/smc_user_model.hip`; the build container's
  * tests run the compiler's uniformity analysis on it).  0 ok, 1 a file could not be written, 2 bad arguments.  No GPU needed. */
 int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir);
+int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir);
+/* BDF user model: device-counted work of the LAST smc_loglik / smc_mh_step_* sweep, in the manner of
+ * smc_meth_sweep_counters: out = {accepted BDF steps, Newton iterations, LU factorisations, Jacobian evaluations} summed over
+ * the sweep's solves (masked proposals left out).  Fails with a message for an RK45 model. */
+int smc_user_sweep_counters(smc_ctx *ctx, int64_t out[4]);
 /* Methanation model: device-counted work of the LAST smc_loglik / smc_mh_step_* call (the counts the K8
  * roofline is built from): out = {accepted BDF steps, Newton iterations, Jacobian factorisations, failed solves}. */
 int smc_meth_sweep_counters(smc_ctx *ctx, int64_t out[4]);

@@ -1,0 +1,805 @@
+// user_bdf.h -- the second integrator of user models (SMC_USER_METHOD_BDF, include/smc_hip.h): run-time compiled source,
+// included by user_model.hip only.  It restates solve_ivp(method="BDF", t_eval = t, rtol, atol) per lane as SciPy 1.15 has
+// it (scipy/integrate/_ivp/bdf.py: the NDF coefficients, the difference array D with change_D / compute_R, solve_bdf_system,
+// the current_jac logic, the error-norm step control with the order change over k-1, k, k+1, BdfDenseOutput; common.py:
+// select_initial_step with order 1, num_jac) and defines the same smc_user_solve_kernel entry point over a UserOps-style
+// item, so that the scheduler (solve_sched.h), early rejection, user_finish_kernel and the cost-hint scan are the RK45 path's.
+//
+// NumPy rounds every product and sum on its own: the integrator is compiled without contraction.  The small matrix products
+// (change_D, psi, the LU and its solves, the dense output) are plain sequential sums where SciPy calls BLAS / LAPACK, so
+// agreement with SciPy is at rounding level per step, not bitwise.  The user's functions are compiled once, with
+// smc_div(a, b) = a / b.
+#pragma once
+
+namespace smc {
+
+static const char *kUserBdfPrelude = R"SRC(
+#include "rk45_math.h"
+namespace smc_user_ieee {
+__device__ __forceinline__ double smc_div(double a, double b) { return a / b; }
+)SRC";
+
+static const char *kUserBdfKernelSource = R"SRC(
+// ---- appended by libsmc_hip.so after the user's source: method BDF ---------------------------------------------
+#include "sweep_args.h"     // in-memory headers handed to hiprtc by the library: the argument blocks,
+#include "philox.h"         // the counter-based generator (the early-rejection bound re-derives the acceptance uniform),
+#include "solve_sched.h"    // the scheduler of the RK45 kernel
+#define NS SMC_USER_NS
+namespace smc_user_bdf {
+#pragma clang fp contract(off)
+constexpr double kEps = 0x1.0p-52;
+constexpr int kMaxOrder = 5, kNewtonMaxIter = 4;
+constexpr int kRows = kMaxOrder + 3;        // D[0 .. order + 2]
+// bdf.py BDF.__init__: gamma, alpha = (1 - kappa) gamma, error_const = kappa gamma + 1 / (1 .. 6), exactly as NumPy rounds them
+constexpr double kGamma[6] = {0x0.0p+0, 0x1.0000000000000p+0, 0x1.8000000000000p+0, 0x1.d555555555555p+0, 0x1.0aaaaaaaaaaaap+1, 0x1.2444444444444p+1};
+constexpr double kAlpha[6] = {0x0.0p+0, 0x1.2f5c28f5c28f6p+0, 0x1.aaaaaaaaaaaabp+0, 0x1.fbf59f9b82ef8p+0, 0x1.15bbbbbbbbbbbp+1, 0x1.2444444444444p+1};
+constexpr double kErrConst[6] = {0x1.0000000000000p+0, 0x1.428f5c28f5c29p-2, 0x1.5555555555555p-3, 0x1.95fb5b9d265dcp-4, 0x1.d111111111112p-4, 0x1.5555555555555p-3};
+// compute_R(order, 1): (-1)^l C(j, l), upper triangular; compute_R of a lower order is its leading block
+constexpr double kU[6][6] = {{1, 1, 1, 1, 1, 1}, {0, -1, -2, -3, -4, -5}, {0, 0, 1, 3, 6, 10},
+                             {0, 0, 0, -1, -4, -10}, {0, 0, 0, 0, 1, 5}, {0, 0, 0, 0, 0, -1}};
+// common.py num_jac
+constexpr double kNumJacDiffReject = 0x1.6a09e667f3bcdp-46, kNumJacDiffSmall = 0x1.0p-39, kNumJacDiffBig = 0x1.0p-13;
+constexpr double kNumJacMinFactor = 0x1.f4p-43;
+
+__device__ __forceinline__ double py_min(double a, double b) { return (b < a) ? b : a; }   // Python's min / max
+__device__ __forceinline__ double py_max(double a, double b) { return (b > a) ? b : a; }
+__device__ __forceinline__ double np_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }   // np.maximum
+// tab[k] for a per-lane k < 6, by selects (an indexed read of a register array would go through scratch)
+__device__ __forceinline__ double pick(const double (&tab)[6], int k) {
+    double r = tab[0];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) r = (k == j) ? tab[j] : r;
+    return r;
+}
+// common.py norm: np.linalg.norm(x) / x.size ** 0.5
+__device__ __forceinline__ double norm(const double *x) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) s += x[i] * x[i];
+    return sqrt(s) / sqrt((double)NS);
+}
+
+// One solve_ivp(BDF, t_eval = t[0..n_t)) call as a resumable state.  item_begin: initial state, first derivative,
+// select_initial_step (what the pool of solve_sched.h holds: t, h, y = D[0], f = D[1]); every item_attempt is one pass of
+// bdf.py's `while not step_accepted` body (its Newton iterations, Jacobian refresh and LU factorisation included) and,
+// when the step is accepted, the order change and the t_eval outputs it covers.  sr2 accumulates (obs - smc_user_obs)^2.
+struct Item {
+    double t, h_abs, sr2;
+    double t_bound, t_next;        // t_eval[n_t - 1]; t_eval[i_out] (+inf when every data time has been served)
+    double D[kRows][NS];           // differences; before the first attempt D[1] holds f(t0, y0) (fresh)
+    double J[NS][NS], LU[NS][NS];  // Jacobian and the factors of I - c J (row-major, L unit lower, U upper)
+    double jac_factor[NS];         // num_jac's per-column factor (no smc_user_jac)
+    int piv[NS];
+    int order, n_equal_steps, i_out, status;   // status: 0 running, 1 finished, -1 TOO_SMALL_STEP
+    bool fresh, in_step, current_jac, lu_valid;
+    unsigned n_steps, n_newton, n_lu, n_jac;   // accepted steps, Newton iterations, LU factorisations, Jacobian evaluations
+};
+
+__device__ __forceinline__ void item_cache_times(Item &it, const double2 *tp, int n_t) {
+    it.t_bound = tp[n_t - 1].x;
+    it.t_next = tp[it.i_out].x;
+}
+// what a lane sets up for an item that has not had an attempt yet (item_begin and the pool's unpack)
+__device__ __forceinline__ void item_reset_lane(Item &it) {
+#pragma unroll
+    for (int r = 2; r < kRows; ++r)
+#pragma unroll
+        for (int i = 0; i < NS; ++i) it.D[r][i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        it.jac_factor[i] = 0x1.0p-26;      // EPS ** 0.5 (jac_factor None)
+        it.piv[i] = i;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) it.J[i][j] = it.LU[i][j] = 0.0;
+    }
+    it.order = 1;
+    it.n_equal_steps = 0;
+    it.status = 0;
+    it.fresh = true;
+    it.in_step = false;
+    it.current_jac = false;
+    it.lu_valid = false;
+    it.n_steps = it.n_newton = it.n_lu = it.n_jac = 0u;
+}
+
+__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {
+    const double r = obs - smc_user_ieee::smc_user_obs(t_out, yy, theta, cond);
+    it.sr2 += r * r;
+}
+
+__device__ __forceinline__ void rhs(double t, const double *y, const double *theta, const double *cond, double *f) {
+    smc_user_ieee::smc_user_rhs(t, y, theta, cond, f);
+}
+
+// J at (t, y): the user's smc_user_jac, or num_jac's forward differences with f = f(t, y) and the adapted factor
+__device__ __forceinline__ void jacobian(Item &it, double t, const double *y, const double *f, const double *theta, const double *cond,
+                                         double atol) {
+    ++it.n_jac;
+#ifdef SMC_USER_HAS_JAC
+    (void)f;
+    (void)atol;
+    smc_user_ieee::smc_user_jac(t, y, theta, cond, &it.J[0][0]);
+#else
+#pragma unroll 1
+    for (int j = 0; j < NS; ++j) {       // one column per pass; the column is picked and written by selects
+        double yj = y[0], fj = f[0], factor = it.jac_factor[0];
+#pragma unroll
+        for (int q = 1; q < NS; ++q) {
+            yj = (j == q) ? y[q] : yj;
+            fj = (j == q) ? f[q] : fj;
+            factor = (j == q) ? it.jac_factor[q] : factor;
+        }
+        const double f_sign = (fj >= 0.0) ? 1.0 : -1.0;
+        const double y_scale = f_sign * np_max(atol, fabs(yj));
+        double fs = factor * y_scale;
+        double h = (yj + fs) - yj;
+        while (h == 0.0) {               // "make sure that the step is not 0"
+            factor *= 10;
+            fs = factor * y_scale;
+            h = (yj + fs) - yj;
+        }
+        double yy[NS], fn[NS], diff[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) yy[i] = y[i] + ((i == j) ? h : 0.0);
+        rhs(t, yy, theta, cond, fn);
+        double max_diff = -1.0, scale = 0.0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {   // np.argmax: the first maximum
+            diff[i] = fn[i] - f[i];
+            const double a = fabs(diff[i]);
+            if (a > max_diff) {
+                max_diff = a;
+                scale = np_max(fabs(f[i]), fabs(fn[i]));
+            }
+        }
+        if (max_diff < kNumJacDiffReject * scale) {     // the refinement step
+            const double new_factor = 10 * factor;
+            const double fs2 = new_factor * y_scale;
+            const double h_new = (yj + fs2) - yj;
+            double diff_new[NS];
+#pragma unroll
+            for (int i = 0; i < NS; ++i) yy[i] = y[i] + ((i == j) ? h_new : 0.0);
+            rhs(t, yy, theta, cond, fn);
+            double max_diff_new = -1.0, scale_new = 0.0;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                diff_new[i] = fn[i] - f[i];
+                const double a = fabs(diff_new[i]);
+                if (a > max_diff_new) {
+                    max_diff_new = a;
+                    scale_new = np_max(fabs(f[i]), fabs(fn[i]));
+                }
+            }
+            if (max_diff * scale_new < max_diff_new * scale) {
+                factor = new_factor;
+                h = h_new;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) diff[i] = diff_new[i];
+                scale = scale_new;
+                max_diff = max_diff_new;
+            }
+        }
+        if (max_diff < kNumJacDiffSmall * scale) factor *= 10;
+        if (max_diff > kNumJacDiffBig * scale) factor *= 0.1;
+        factor = np_max(factor, kNumJacMinFactor);
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            it.jac_factor[q] = (j == q) ? factor : it.jac_factor[q];
+#pragma unroll
+            for (int i = 0; i < NS; ++i) it.J[i][q] = (j == q) ? diff[i] / h : it.J[i][q];
+        }
+    }
+#endif
+}
+
+// lu_factor(I - c J): partial pivoting (the first largest |a| of the column, as idamax), rows swapped by selects
+__device__ __forceinline__ void lu_factor(Item &it, double c) {
+    double A[NS][NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int j = 0; j < NS; ++j) A[i][j] = ((i == j) ? 1.0 : 0.0) - c * it.J[i][j];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        int p = k;
+        double amax = fabs(A[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i) {
+            const double a = fabs(A[i][k]);
+            p = (a > amax) ? i : p;
+            amax = (a > amax) ? a : amax;
+        }
+        it.piv[k] = p;
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const double akj = A[k][j];
+                A[k][j] = (p == i) ? A[i][j] : akj;
+                A[i][j] = (p == i) ? akj : A[i][j];
+            }
+        const double pivot = A[k][k];
+        const double r = 1.0 / pivot;                  // dgetf2: scale by the reciprocal (a zero pivot leaves the column)
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i) A[i][k] = (pivot != 0.0) ? A[i][k] * r : A[i][k];
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i)
+#pragma unroll
+            for (int j = k + 1; j < NS; ++j) A[i][j] = A[i][j] - A[i][k] * A[k][j];
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int j = 0; j < NS; ++j) it.LU[i][j] = A[i][j];
+    ++it.n_lu;
+    it.lu_valid = true;
+}
+
+// lu_solve: b <- (I - c J)^-1 b
+__device__ __forceinline__ void lu_solve(const Item &it, double *b) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i) {
+            const double bk = b[k];
+            b[k] = (it.piv[k] == i) ? b[i] : bk;
+            b[i] = (it.piv[k] == i) ? bk : b[i];
+        }
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i) b[i] = b[i] - b[k] * it.LU[i][k];
+#pragma unroll
+    for (int k = NS - 1; k >= 0; --k) {
+        b[k] = b[k] / it.LU[k][k];
+#pragma unroll
+        for (int i = 0; i < k; ++i) b[i] = b[i] - b[k] * it.LU[i][k];
+    }
+}
+
+// change_D: D[:order + 1] = (R U)^T D[:order + 1] with R = compute_R(order, factor), U = compute_R(order, 1), evaluated as
+// U^T (R^T D): column l of R is a running product, so neither matrix is held (R U would need 72 doubles of registers).  For
+// the per-lane order the order-5 matrices are used - compute_R of a lower order is their leading block - with the rows above
+// `order` left out by selects.
+__device__ __forceinline__ void change_D(Item &it, int order, double factor) {
+    double E[6][NS];
+#pragma unroll
+    for (int l = 0; l < 6; ++l) {
+        double r = 1.0;                                  // R[0][l]
+#pragma unroll
+        for (int s = 0; s < NS; ++s) E[l][s] = it.D[0][s];
+#pragma unroll
+        for (int i = 1; i < 6; ++i) {
+            r = (l == 0) ? 0.0 : r * (((double)(i - 1) - factor * l) / i);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) E[l][s] = (i <= order && l > 0) ? E[l][s] + r * it.D[i][s] : E[l][s];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            double acc = E[0][s];
+#pragma unroll
+            for (int l = 1; l <= j; ++l) acc += kU[l][j] * E[l][s];
+            it.D[j][s] = (j <= order) ? acc : it.D[j][s];
+        }
+}
+
+// solve_bdf_system: at most kNewtonMaxIter iterations with the convergence-rate test.  The loop has a fixed trip count;
+// a lane that has stopped iterating only idles through the rest.
+__device__ __forceinline__ void solve_bdf_system(Item &it, const double *theta, const double *cond, double t_new, const double *y_predict,
+                                                 double c, const double *psi, const double *scale, double tol, bool &converged,
+                                                 int &n_iter, double *y, double *d) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        y[i] = y_predict[i];
+        d[i] = 0.0;
+    }
+    double dy_norm_old = 0.0;
+    bool done = false;
+    converged = false;
+    n_iter = kNewtonMaxIter;
+#pragma unroll 1
+    for (int k = 0; k < kNewtonMaxIter; ++k) {
+        if (!done) {
+            double f[NS];
+            rhs(t_new, y, theta, cond, f);
+            ++it.n_newton;
+            bool finite = true;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) finite = finite && __builtin_isfinite(f[i]);
+            if (!finite) {
+                done = true;
+                n_iter = k + 1;
+            } else {
+                double dy[NS], tmp[NS];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) dy[i] = c * f[i] - psi[i] - d[i];
+                lu_solve(it, dy);
+#pragma unroll
+                for (int i = 0; i < NS; ++i) tmp[i] = dy[i] / scale[i];
+                const double dy_norm = norm(tmp);
+                const double rate = dy_norm / dy_norm_old;      // used from the second iteration on (rate is None before)
+                if (k > 0 && (rate >= 1 || pow(rate, (double)(kNewtonMaxIter - k)) / (1 - rate) * dy_norm > tol)) {
+                    done = true;
+                    n_iter = k + 1;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) {
+                        y[i] += dy[i];
+                        d[i] += dy[i];
+                    }
+                    if (dy_norm == 0 || (k > 0 && rate / (1 - rate) * dy_norm < tol)) {
+                        converged = true;
+                        done = true;
+                        n_iter = k + 1;
+                    }
+                    dy_norm_old = dy_norm;
+                }
+            }
+        }
+    }
+}
+
+__device__ void item_begin(Item &it, const double *theta, const double *cond, const double2 *tp, int n_t, double rtol_in,
+                           double atol) {
+    const double rtol = (rtol_in < 100 * kEps) ? 100 * kEps : rtol_in;      // common.py validate_tol
+    const double t0 = tp[0].x, t_bound = tp[n_t - 1].x;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    item_reset_lane(it);
+    it.t = t0;
+    it.sr2 = 0.0;
+    it.i_out = 0;
+    double *y = it.D[0], *f = it.D[1];
+    smc_user_ieee::smc_user_y0(theta, cond, y);
+    rhs(t0, y, theta, cond, f);
+    // common.py select_initial_step, direction +1, order 1, max_step inf
+    const double interval_length = fabs(t_bound - t0);
+    if (interval_length == 0.0) {
+        it.h_abs = 0.0;
+    } else {
+        double scale[NS], tmp[NS], y1[NS], f1[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            scale[i] = atol + fabs(y[i]) * rtol;
+            tmp[i] = y[i] / scale[i];
+        }
+        const double d0 = norm(tmp);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) tmp[i] = f[i] / scale[i];
+        const double d1 = norm(tmp);
+        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        h0 = py_min(h0, interval_length);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) y1[i] = y[i] + h0 * 1.0 * f[i];
+        rhs(t0 + h0 * 1.0, y1, theta, cond, f1);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) tmp[i] = (f1[i] - f[i]) / scale[i];
+        const double d2 = norm(tmp) / h0;
+        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : sqrt(0.01 / py_max(d1, d2));   // ** (1 / 2)
+        it.h_abs = py_min(py_min(py_min(100 * h0, h1), interval_length), inf);
+    }
+    if (it.t == t_bound) {   // base.py: nothing to integrate (outputs from D[0] = y0)
+        while (tp[it.i_out].x <= it.t) { emit(it, y, theta, cond, tp[it.i_out].x, tp[it.i_out].y); ++it.i_out; }
+        it.status = 1;
+    }
+    item_cache_times(it, tp, n_t);
+}
+
+// One pass of bdf.py _step_impl's `while not step_accepted` body; on acceptance also the rest of _step_impl (D update,
+// order change) and the t_eval outputs of the step through BdfDenseOutput (built after the step, as solve_ivp does).
+__device__ __forceinline__ void item_attempt(Item &it, const double *theta, const double *cond, const double2 *tp, double rtol_in,
+                                             double atol) {
+    const double rtol = (rtol_in < 100 * kEps) ? 100 * kEps : rtol_in;
+    const double newton_tol = py_max(10 * kEps / rtol, py_min(0.03, sqrt(rtol)));
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    if (it.fresh) {          // BDF.__init__: D[1] = f h, J at (t0, y0)
+        double f0[NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            f0[i] = it.D[1][i];
+            it.D[1][i] = f0[i] * it.h_abs;
+        }
+        jacobian(it, it.t, it.D[0], f0, theta, cond, atol);
+        it.fresh = false;
+    }
+    const double t = it.t, t_bound = it.t_bound;
+    const double min_step = (t >= 0.0) ? smc::min_step_of(t) : 10 * fabs(nextafter(t, inf) - t);
+    const int order = it.order;
+    // the two rescalings of D before the Newton solve (start-of-step clip to min_step, last step clipped at t_bound) and the
+    // one after it (Newton failure, error rejection, order change) each go through ONE inlined change_D
+    bool cd_pre[2] = {false, false};
+    double cd_pre_factor[2] = {1.0, 1.0};
+    double h_abs = it.h_abs;
+    if (!it.in_step) {       // start of a step (max_step = inf: only the lower clip)
+        if (h_abs < min_step) {
+            cd_pre[0] = true;
+            cd_pre_factor[0] = min_step / h_abs;
+            h_abs = min_step;
+            it.n_equal_steps = 0;
+        }
+        it.current_jac = false;
+        it.in_step = true;
+    }
+    if (h_abs < min_step) {  // TOO_SMALL_STEP
+        it.status = -1;
+        return;
+    }
+    double t_new = t + h_abs;
+    if (t_new - t_bound > 0) {
+        t_new = t_bound;
+        cd_pre[1] = true;
+        cd_pre_factor[1] = fabs(t_new - t) / h_abs;
+        it.n_equal_steps = 0;
+        it.lu_valid = false;
+    }
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q)
+        if (q == 0 ? cd_pre[0] : cd_pre[1]) change_D(it, order, q == 0 ? cd_pre_factor[0] : cd_pre_factor[1]);
+    const double h = t_new - t;
+    h_abs = fabs(h);
+    double y_predict[NS], scale[NS], psi[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double acc = it.D[0][s];
+#pragma unroll
+        for (int j = 1; j < 6; ++j) acc = (j <= order) ? acc + it.D[j][s] : acc;
+        y_predict[s] = acc;
+        scale[s] = atol + rtol * fabs(acc);
+    }
+    const double alpha = pick(kAlpha, order);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 1; j < 6; ++j) acc = (j <= order) ? acc + it.D[j][s] * kGamma[j] : acc;
+        psi[s] = acc / alpha;
+    }
+    const double c = h / alpha;
+    bool converged = false;
+    int n_iter = 0;
+    double y_new[NS], d[NS];
+    // first with the current J; if Newton fails and J is not fresh for this step, once more with J at (t_new, y_predict)
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0 || (!converged && !it.current_jac)) {
+            if (pass == 1) {
+                double fp[NS];      // num_jac's f(t_new, y_predict) (jac_wrapped evaluates it)
+#ifndef SMC_USER_HAS_JAC
+                rhs(t_new, y_predict, theta, cond, fp);
+#endif
+                jacobian(it, t_new, y_predict, fp, theta, cond, atol);
+                it.lu_valid = false;
+                it.current_jac = true;
+            }
+            if (!it.lu_valid) lu_factor(it, c);
+            solve_bdf_system(it, theta, cond, t_new, y_predict, c, psi, scale, newton_tol, converged, n_iter, y_new, d);
+        }
+    }
+    bool accepted = false, cd = false;
+    int cd_order = order;
+    double cd_factor = 1.0;
+    if (!converged) {
+        h_abs *= 0.5;
+        cd = true;
+        cd_factor = 0.5;
+        it.n_equal_steps = 0;
+        it.lu_valid = false;
+        it.h_abs = h_abs;
+    } else {
+        const double safety = 0.9 * (2 * kNewtonMaxIter + 1) / (2 * kNewtonMaxIter + n_iter);
+        double err[NS];
+        const double ec = pick(kErrConst, order);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            scale[s] = atol + rtol * fabs(y_new[s]);
+            err[s] = ec * d[s] / scale[s];
+        }
+        const double error_norm = norm(err);
+        if (error_norm > 1) {    // rejected: the LU is kept (bdf.py: no convergence problem)
+            const double factor = py_max(0.2, safety * pow(error_norm, -1.0 / (order + 1)));
+            h_abs *= factor;
+            cd = true;
+            cd_factor = factor;
+            it.n_equal_steps = 0;
+            it.h_abs = h_abs;
+        } else {
+            accepted = true;
+            ++it.n_steps;
+            it.in_step = false;
+            it.n_equal_steps += 1;
+            it.t = t_new;
+            it.h_abs = h_abs;
+            {   // D[order + 2] = d - D[order + 1]; D[order + 1] = d; D[i] += D[i + 1] for i = order .. 0
+                double Dop1[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    double v = it.D[2][s];
+#pragma unroll
+                    for (int r = 3; r < kRows - 1; ++r) v = (r == order + 1) ? it.D[r][s] : v;
+                    Dop1[s] = v;
+                }
+#pragma unroll
+                for (int r = 2; r < kRows; ++r)
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        it.D[r][s] = (r == order + 2) ? d[s] - Dop1[s] : it.D[r][s];
+                        it.D[r][s] = (r == order + 1) ? d[s] : it.D[r][s];
+                    }
+#pragma unroll
+                for (int i = kMaxOrder; i >= 0; --i)
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) it.D[i][s] = (i <= order) ? it.D[i][s] + it.D[i + 1][s] : it.D[i][s];
+            }
+            if (it.n_equal_steps >= order + 1) {     // order change over order - 1, order, order + 1
+                double em[NS], ep[NS];
+                const double ecm = pick(kErrConst, order - 1), ecp = pick(kErrConst, order + 1 < 6 ? order + 1 : 5);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    double dm = it.D[1][s], dp = it.D[3][s];
+#pragma unroll
+                    for (int r = 2; r < 6; ++r) dm = (r == order) ? it.D[r][s] : dm;
+#pragma unroll
+                    for (int r = 4; r < kRows; ++r) dp = (r == order + 2) ? it.D[r][s] : dp;
+                    em[s] = ecm * dm / scale[s];
+                    ep[s] = ecp * dp / scale[s];
+                }
+                const double error_m_norm = (order > 1) ? norm(em) : inf;
+                const double error_p_norm = (order < kMaxOrder) ? norm(ep) : inf;
+                const double fm = pow(error_m_norm, -1.0 / order), f0 = pow(error_norm, -1.0 / (order + 1)),
+                             fp = pow(error_p_norm, -1.0 / (order + 2));
+                int delta = -1;             // np.argmax: the first maximum
+                double fmax_ = fm;
+                if (f0 > fmax_) { delta = 0; fmax_ = f0; }
+                if (fp > fmax_) { delta = 1; fmax_ = fp; }
+                if (fm != fm || f0 != f0 || fp != fp) fmax_ = fm + f0 + fp;   // np.max propagates NaN (min(10, nan) is 10 below)
+                const int new_order = order + delta;
+                it.order = new_order;
+                const double factor = py_min(10.0, safety * fmax_);
+                it.h_abs *= factor;
+                cd = true;
+                cd_order = new_order;
+                cd_factor = factor;
+                it.n_equal_steps = 0;
+                it.lu_valid = false;
+            }
+        }
+    }
+    if (cd) change_D(it, cd_order, cd_factor);
+    if (accepted && it.t_next <= t_new) {     // outputs in (t, t_new] (and t_eval[0] = t0 on the first step): BdfDenseOutput
+        const int k = it.order;
+        const double hd = it.h_abs;
+        int i_out = it.i_out;
+        double2 nx = tp[i_out];
+        do {
+            double p = 1.0, yy[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) yy[s] = 0.0;
+#pragma unroll
+            for (int j = 0; j < kMaxOrder; ++j) {
+                const double t_shift = t_new - hd * j, denom = hd * (1 + j);
+                p = (j == 0) ? (nx.x - t_shift) / denom : p * ((nx.x - t_shift) / denom);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) yy[s] = (j < k) ? yy[s] + it.D[j + 1][s] * p : yy[s];
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s) yy[s] += it.D[0][s];
+            emit(it, yy, theta, cond, nx.x, nx.y);
+            ++i_out;
+            nx = tp[i_out];                          // i_out == n_t reads the sentinel (+inf, 0)
+        } while (nx.x <= t_new);
+        it.i_out = i_out;
+        it.t_next = nx.x;
+    }
+    it.status = (accepted && t_new - t_bound >= 0) ? 1 : 0;    // base.py
+}
+}  // namespace smc_user_bdf
+
+// solve_sched.h's view of a BDF item: as UserOps of the RK45 kernel, plus the per-item work counters
+struct UserBdfOps {
+    struct Item {
+        smc_user_bdf::Item s;
+        double th[SMC_USER_DIM];
+        long long out_idx;      // e * n + p
+        int e;
+        unsigned attempts;
+    };
+    static constexpr int kPoolWords = 2 * NS + 6;
+    const smc::UserSolveArgs &a;
+    long long n;
+    int n_ex;
+    const int *list;
+    unsigned n_list;
+    const int *solo;
+    unsigned n_solo;
+    int patience;
+    long long n_pos;
+    const double2 *s_tp;
+    unsigned *counts;           // [k * n_ex * n + e * n + p], k: accepted steps, Newton iterations, LU factorisations, Jacobians
+
+    __device__ __forceinline__ const double *cond(int e) const { return a.cond + (long long)e * a.n_cond; }
+    __device__ __forceinline__ const double2 *row(int e) const { return s_tp + e * (a.n_t + 1); }
+    __device__ __forceinline__ void publish(long long idx, double sum, int info) const {
+        __hip_atomic_store(reinterpret_cast<unsigned long long *>(a.sum_r2) + idx, (unsigned long long)__double_as_longlong(sum),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        a.info[idx] = info;
+    }
+    __device__ __forceinline__ void publish_counts(long long idx, const smc_user_bdf::Item &s) const {
+        const long long m = (long long)a.n_ex * a.n;
+        counts[idx] = s.n_steps;
+        counts[m + idx] = s.n_newton;
+        counts[2 * m + idx] = s.n_lu;
+        counts[3 * m + idx] = s.n_jac;
+    }
+    __device__ __forceinline__ void load_theta(Item &it, long long p) const {
+#pragma unroll
+        for (int c = 0; c < SMC_USER_DIM; ++c) it.th[c] = a.theta[c * a.stride + p];
+    }
+    __device__ __forceinline__ int start(long long p, int e, bool from_list, Item &nb) const {
+        nb.out_idx = (long long)e * a.n + p;
+        nb.e = e;
+        nb.attempts = 0;
+        if (!from_list && list && a.listed[p] != 0) return smc::kStartSkipped;
+        if (a.p0 && a.p0[p] == 0) {
+            nb.s.n_steps = nb.s.n_newton = nb.s.n_lu = nb.s.n_jac = 0u;
+            publish_counts(nb.out_idx, nb.s);
+            publish(nb.out_idx, 0.0, 0);
+            return smc::kStartDone;
+        }
+        load_theta(nb, p);
+        smc_user_bdf::item_begin(nb.s, nb.th, cond(e), row(e), a.n_t, a.rtol, a.atol);
+        if (nb.s.status == 0) return smc::kStartStarted;
+        publish_counts(nb.out_idx, nb.s);
+        publish(nb.out_idx, nb.s.sr2, nb.s.status < 0 ? (1 << 30) : 0);
+        return smc::kStartDone;
+    }
+    __device__ __forceinline__ void pack(const Item &nb, double *slot) const {
+        slot[0 * 64] = nb.s.t;
+        slot[1 * 64] = nb.s.h_abs;
+        slot[2 * 64] = nb.s.sr2;
+        slot[3 * 64] = __hiloint2double(nb.s.i_out, 0);
+        slot[4 * 64] = __hiloint2double((int)nb.attempts, nb.e);
+        slot[5 * 64] = __longlong_as_double(nb.out_idx);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            slot[(6 + i) * 64] = nb.s.D[0][i];          // y0
+            slot[(6 + NS + i) * 64] = nb.s.D[1][i];     // f(t0, y0)
+        }
+    }
+    __device__ __forceinline__ void unpack(Item &it, const double *slot) const {
+        smc_user_bdf::item_reset_lane(it.s);
+        it.s.t = slot[0 * 64];
+        it.s.h_abs = slot[1 * 64];
+        it.s.sr2 = slot[2 * 64];
+        const double w4 = slot[4 * 64];
+        it.s.i_out = __double2hiint(slot[3 * 64]);
+        it.e = __double2loint(w4);
+        it.attempts = (unsigned)__double2hiint(w4);
+        it.out_idx = __double_as_longlong(slot[5 * 64]);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            it.s.D[0][i] = slot[(6 + i) * 64];
+            it.s.D[1][i] = slot[(6 + NS + i) * 64];
+        }
+        smc_user_bdf::item_cache_times(it.s, row(it.e), a.n_t);
+        load_theta(it, it.out_idx - (long long)it.e * a.n);
+    }
+    __device__ __forceinline__ int attempt(Item &it) const {
+        smc_user_bdf::item_attempt(it.s, it.th, cond(it.e), row(it.e), a.rtol, a.atol);
+        ++it.attempts;
+        if (it.attempts >= 0x1fffffffu) it.s.status = -1;        // hard bound so that every wave drains
+        return it.s.status;
+    }
+    __device__ __forceinline__ int uniform_attempts(Item &it, int budget) const { return smc::uniform_attempts_plain(*this, it, budget); }
+    __device__ __forceinline__ bool long_running(const Item &it) const { return it.attempts > 64u; }
+    __device__ __forceinline__ long long positions() const { return n_pos; }
+    __device__ __forceinline__ int start_at(long long pos, int e, Item &nb) const {
+        return start(a.order ? (long long)a.order[pos] : pos, e, false, nb);
+    }
+    __device__ __forceinline__ void finish(Item &it, int st) const {
+        publish_counts(it.out_idx, it.s);
+        publish(it.out_idx, it.s.sr2, (int)(it.attempts & 0x1fffffffu) | ((st < 0) ? (1 << 30) : 0));
+    }
+    __device__ __forceinline__ Item broadcast(const Item &it, int src) const {
+        Item u;
+        u.s.t = smc::lane_value(it.s.t, src);
+        u.s.h_abs = smc::lane_value(it.s.h_abs, src);
+        u.s.sr2 = smc::lane_value(it.s.sr2, src);
+        u.s.t_bound = smc::lane_value(it.s.t_bound, src);
+        u.s.t_next = smc::lane_value(it.s.t_next, src);
+#pragma unroll
+        for (int r = 0; r < smc_user_bdf::kRows; ++r)
+#pragma unroll
+            for (int i = 0; i < NS; ++i) u.s.D[r][i] = smc::lane_value(it.s.D[r][i], src);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            u.s.jac_factor[i] = smc::lane_value(it.s.jac_factor[i], src);
+            u.s.piv[i] = __builtin_amdgcn_readlane(it.s.piv[i], src);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                u.s.J[i][j] = smc::lane_value(it.s.J[i][j], src);
+                u.s.LU[i][j] = smc::lane_value(it.s.LU[i][j], src);
+            }
+        }
+        u.s.order = __builtin_amdgcn_readlane(it.s.order, src);
+        u.s.n_equal_steps = __builtin_amdgcn_readlane(it.s.n_equal_steps, src);
+        u.s.i_out = __builtin_amdgcn_readlane(it.s.i_out, src);
+        u.s.status = __builtin_amdgcn_readlane(it.s.status, src);
+        const int flags = (int)it.s.fresh | ((int)it.s.in_step << 1) | ((int)it.s.current_jac << 2) | ((int)it.s.lu_valid << 3);
+        const int uf = __builtin_amdgcn_readlane(flags, src);
+        u.s.fresh = (uf & 1) != 0;
+        u.s.in_step = (uf & 2) != 0;
+        u.s.current_jac = (uf & 4) != 0;
+        u.s.lu_valid = (uf & 8) != 0;
+        u.s.n_steps = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_steps, src);
+        u.s.n_newton = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_newton, src);
+        u.s.n_lu = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_lu, src);
+        u.s.n_jac = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_jac, src);
+#pragma unroll
+        for (int c = 0; c < SMC_USER_DIM; ++c) u.th[c] = smc::lane_value(it.th[c], src);
+        u.out_idx = smc::lane_value_ll(it.out_idx, src);
+        u.e = __builtin_amdgcn_readlane(it.e, src);
+        u.attempts = (unsigned)__builtin_amdgcn_readlane((int)it.attempts, src);
+        return u;
+    }
+    __device__ __forceinline__ bool reject_enabled() const { return a.rej != nullptr; }
+    // exact early rejection: the bound of UserOps (RK45 kernel) - the sum of squared residuals only grows as outputs are emitted
+    __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
+        const long long p = it.out_idx - (long long)it.e * a.n;
+        const double sigma = a.est_sigma ? it.th[SMC_USER_DIM - 1] : a.sigma_fixed;
+        if (!(sigma > 0.0)) return false;
+        const double s2 = sigma * sigma;
+        const double c0 = (-0.5 * a.n_t) * log(2.0 * 3.141592653589793 * s2);
+        double lk2_bound = 0.0;
+        for (int k = 0; k < a.n_ex; ++k) {
+            double S = 0.0;
+            if (k == it.e) {
+                S = it.s.sr2;
+            } else {
+                const double v = __longlong_as_double((long long)__hip_atomic_load(
+                    reinterpret_cast<unsigned long long *>(a.sum_r2) + (long long)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (v < 0.0) return true;
+                if (v == v) S = v;
+            }
+            lk2_bound += c0 - S / (2.0 * s2);
+        }
+        const smc::RejectArgs &r = *a.rej;
+        double rr;
+        if (r.device_rng) {
+            const smc::u32x4 ru = smc::philox_block(r.seed, (unsigned long long)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
+            rr = smc::u01_from(ru.x, ru.y);
+        } else {
+            rr = r.rr[p];
+        }
+        double pp = exp((lk2_bound - r.lk1[p]) * r.gamma);
+        if (r.prior_mode != 0) pp = pp * r.pratio[p];
+        return pp < rr * (1.0 - 1e-12);
+    }
+    __device__ __forceinline__ void cancel(Item &it) const {
+        publish_counts(it.out_idx, it.s);
+        publish(it.out_idx, -1.0, (int)(it.attempts & 0x1fffffffu) | (1 << 29));
+    }
+};
+
+// Outputs per item: the sum of squared residuals, attempts | cancelled << 29 | failed << 30, and the four work counters.
+extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts) {
+    extern __shared__ double s_pool_all[];
+    double *s_pool = s_pool_all + (threadIdx.x >> 6) * (UserBdfOps::kPoolWords * 64);
+    double2 *s_tp = reinterpret_cast<double2 *>(s_pool_all + 4 * (UserBdfOps::kPoolWords * 64));
+    for (int i = threadIdx.x; i < a.n_ex * (a.n_t + 1); i += blockDim.x) {
+        const int e = i / (a.n_t + 1), k = i - e * (a.n_t + 1);
+        s_tp[i] = (k < a.n_t) ? make_double2(a.t[e * a.n_t + k], a.obs[e * a.n_t + k])
+                              : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);
+    }
+    __syncthreads();
+    const unsigned n_list = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[0]) : 0u;
+    unsigned n_solo = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[1]) : 0u;
+    if (n_solo > a.solo_cap) n_solo = a.solo_cap;
+    UserBdfOps ops{a, a.n, a.n_ex, a.stiff_list, n_list, a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, a.patience,
+                   a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : a.n, s_tp, counts};
+    smc::solve_persistent(ops, a.queue, s_pool);
+}
+)SRC";
+
+}  // namespace smc

@@ -23,6 +23,7 @@
 #include "../../include/smc_hip.h"
 #include "smc_internal.h"
 #include "solve_sched.h"   // kChunk: the grid is sized in chunks of the shared scheduler
+#include "user_bdf.h"      // the BDF integrator's source (SMC_USER_METHOD_BDF)
 
 namespace smc {
 
@@ -555,6 +556,28 @@ user_finish_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, 
     if (attempts) atomicAdd(&counters->rk_attempts, attempts);
 }
 
+// BDF models: the per-item work counters of a sweep summed into four totals (smc_user_sweep_counters); masked proposals
+// (not solved: their items may hold an earlier sweep's counts) are left out
+__global__ void __launch_bounds__(256)
+user_bdf_count_kernel(const uint8_t *__restrict__ p0mask, const unsigned *__restrict__ counts, int64_t n, int n_ex,
+                      unsigned long long *__restrict__ totals) {
+    __shared__ unsigned long long s[4][256];
+    unsigned long long acc[4] = {0, 0, 0, 0};
+    const int64_t m = n * n_ex;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        if (p0mask && p0mask[i % n] == 0) continue;
+        for (int k = 0; k < 4; ++k) acc[k] += counts[k * m + i];
+    }
+    for (int k = 0; k < 4; ++k) s[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int k = 0; k < 4; ++k) s[k][threadIdx.x] += s[k][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4 && s[threadIdx.x][0]) atomicAdd(totals + threadIdx.x, s[threadIdx.x][0]);
+}
+
 struct UserModel {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
@@ -568,12 +591,30 @@ struct UserModel {
     int n_ex = 0, n_t = 0, n_cond = 0, n_states = 0, est_sigma = 1;
     int blocks_per_cu = 4;   // persistent blocks (4 waves each) per CU: what the compiled kernel's registers and LDS allow
     double sigma_fixed = 0, rtol = 1e-3, atol = 1e-6;
+    int method = SMC_USER_METHOD_RK45;
+    unsigned *d_bdf_counts = nullptr;          // BDF: per item {accepted steps, Newton iterations, LU factorisations, Jacobians}
+    unsigned long long *d_bdf_totals = nullptr;   // ... their sums over the last sweep (user_bdf_count_kernel)
 };
 
 // the optional fourth ingredient: a source that mentions smc_user_cost must define it (include/smc_hip.h)
 static bool has_cost_hint(const char *user_source) { return strstr(user_source, "smc_user_cost") != nullptr; }
 
-static std::string build_source(const char *user_source, int n_states, int dim) {
+// the optional fifth ingredient of a BDF model: a source that mentions smc_user_jac must define it (include/smc_hip.h)
+static bool has_jac(const char *user_source) { return strstr(user_source, "smc_user_jac") != nullptr; }
+
+static std::string build_source_bdf(const char *user_source, int n_states, int dim) {
+    char head[256];
+    snprintf(head, sizeof head, "#define SMC_USER_NS %d\n#define SMC_USER_DIM %d\n%s%s", n_states, dim,
+             has_cost_hint(user_source) ? "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n" : "",
+             has_jac(user_source) ? "#define SMC_USER_HAS_JAC 1\n" : "");
+    // the cost-hint scan kernel is the RK45 source's own (its #ifdef SMC_USER_HAS_COST block), appended unchanged
+    const char *scan = strstr(kUserKernelSource, "#ifdef SMC_USER_HAS_COST");
+    return std::string(head) + kUserBdfPrelude + "#line 1 \"user_model\"\n" + user_source + "\n}  // namespace smc_user_ieee\n" +
+           kUserBdfKernelSource + scan;
+}
+
+static std::string build_source(const char *user_source, int n_states, int dim, int method) {
+    if (method == SMC_USER_METHOD_BDF) return build_source_bdf(user_source, n_states, dim);
     char head[256];
     snprintf(head, sizeof head, "#define SMC_USER_NS %d\n#define SMC_USER_DIM %d\n%s", n_states, dim,
              has_cost_hint(user_source) ? "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n" : "");
@@ -622,6 +663,8 @@ void user_model_release(smc_ctx *c) {
     (void)hipFree(u->d_list);
     (void)hipFree(u->d_listed);
     (void)hipFree(u->d_count);
+    (void)hipFree(u->d_bdf_counts);
+    (void)hipFree(u->d_bdf_totals);
     if (u->module) (void)hipModuleUnload(u->module);
     delete u;
     c->user = nullptr;
@@ -706,7 +749,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
             }
         }
     }
-    void *args[] = {&a};
+    void *args[] = {&a, &u->d_bdf_counts};     // the RK45 kernel takes the first only
     {
         ScopedTimer tm(c, SMC_T_SOLVE);
         (void)hipMemsetAsync(c->d_queue, 0, sizeof(unsigned long long), c->stream);
@@ -720,6 +763,12 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     const int64_t g = (n + 255) / 256;
     hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
                        c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->n_t, u->est_sigma, u->sigma_fixed, lk, c->d_counters);
+    if (u->method == SMC_USER_METHOD_BDF) {
+        (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
+        const int64_t items = n * u->n_ex, gb = (items + 255) / 256;
+        hipLaunchKernelGGL(user_bdf_count_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0, c->stream, p0mask, u->d_bdf_counts,
+                           n, u->n_ex, u->d_bdf_totals);
+    }
 }
 
 void launch_user_loglik(smc_ctx *c, const double *theta, int64_t stride, int64_t n, double *lk) {
@@ -750,11 +799,13 @@ using namespace smc;
 
 extern "C" {
 
-int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap) {
-    if (!source || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM) return 2;
+static bool user_method_ok(int method) { return method == SMC_USER_METHOD_RK45 || method == SMC_USER_METHOD_BDF; }
+
+int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap) {
+    if (!source || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method)) return 2;
     std::vector<char> code;
     std::string lg;
-    const bool ok = compile_user(build_source(source, n_states, dim), code, lg);
+    const bool ok = compile_user(build_source(source, n_states, dim, method), code, lg);
     if (log && log_cap > 0) {
         strncpy(log, lg.c_str(), (size_t)log_cap - 1);
         log[log_cap - 1] = 0;
@@ -762,9 +813,14 @@ int smc_user_model_check(const char *source, int n_states, int dim, char *log, i
     return ok ? 0 : 1;
 }
 
-int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir) {
-    if (!source || !dir || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM) return 2;
-    const std::string src = build_source(source, n_states, dim);
+int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap) {
+    return smc_user_model_check2(source, n_states, dim, SMC_USER_METHOD_RK45, log, log_cap);
+}
+
+int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir) {
+    if (!source || !dir || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method))
+        return 2;
+    const std::string src = build_source(source, n_states, dim, method);
     const char *names[] = {"smc_user_model.hip", "sweep_args.h", "philox.h", "solve_sched.h", "rk45_math.h"};
     const char *texts[] = {src.c_str(), k_sweep_args_h, k_philox_h, k_solve_sched_h, k_rk45_math_h};
     for (int i = 0; i < 5; ++i) {
@@ -776,16 +832,21 @@ int smc_user_model_dump_source(const char *source, int n_states, int dim, const 
     return 0;
 }
 
-int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
-                       int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol) {
+int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir) {
+    return smc_user_model_dump_source2(source, n_states, dim, SMC_USER_METHOD_RK45, dir);
+}
+
+int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
+                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method) {
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
+    if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
     if (n_states < 1 || n_states > SMC_USER_MAX_STATES) return smc_fail(c, "smc_set_model_user: n_states out of range");
     if (n_ex < 1 || n_t < 1 || n_cond < 0) return smc_fail(c, "smc_set_model_user: bad data shape");
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(build_source(source, n_states, c->dim), code, lg)) {
+    if (!compile_user(build_source(source, n_states, c->dim, method), code, lg)) {
         std::string msg = "user model does not compile:\n" + lg;
         if (msg.size() > 3500) msg.resize(3500);
         return smc_fail(c, msg.c_str());
@@ -811,6 +872,10 @@ int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const doubl
     if (ok && !c->d_mlk2) ok = hipMalloc(&c->d_mlk2, (size_t)c->n_local * sizeof(double)) == hipSuccess;
     ok = ok && hipMalloc(&u->d_sum, (size_t)c->n_local * n_ex * sizeof(double)) == hipSuccess &&
          hipMalloc(&u->d_info, (size_t)c->n_local * n_ex * sizeof(int)) == hipSuccess;
+    if (ok && method == SMC_USER_METHOD_BDF)
+        ok = hipMalloc(&u->d_bdf_counts, (size_t)4 * c->n_local * n_ex * sizeof(unsigned)) == hipSuccess &&
+             hipMalloc(&u->d_bdf_totals, 4 * sizeof(unsigned long long)) == hipSuccess &&
+             hipMemset(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (ok && u->fn_scan)
         ok = hipMalloc(&u->d_list, (size_t)c->n_local * sizeof(int32_t)) == hipSuccess &&
              hipMalloc(&u->d_listed, (size_t)c->n_local) == hipSuccess && hipMalloc(&u->d_count, 4 * sizeof(unsigned)) == hipSuccess &&
@@ -841,8 +906,29 @@ int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const doubl
     u->sigma_fixed = sigma_fixed;
     u->rtol = rtol;
     u->atol = atol;
+    u->method = method;
     c->model_kind = 3;
     c->have_model = true;
+    return 0;
+}
+
+int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
+                       int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol) {
+    return smc_set_model_user2(c, source, n_states, t, obs, cond, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
+                               SMC_USER_METHOD_RK45);
+}
+
+int smc_user_sweep_counters(smc_ctx *c, int64_t out[4]) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || u->method != SMC_USER_METHOD_BDF)
+        return smc_fail(c, "smc_user_sweep_counters: the model is not a user model with method SMC_USER_METHOD_BDF");
+    if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
+    unsigned long long h[4];
+    if (hipMemcpyAsync(h, u->d_bdf_totals, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return smc_fail(c, "smc_user_sweep_counters: copying the counters failed");
+    for (int k = 0; k < 4; ++k) out[k] = (int64_t)h[k];
     return 0;
 }
 

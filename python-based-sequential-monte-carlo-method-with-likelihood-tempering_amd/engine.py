@@ -169,18 +169,21 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6):
+                       atol=1e-6, method="RK45"):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
-        per-experiment numbers (e.g. the initial concentration).  Raises SmcError with the compiler log if the source
-        does not compile."""
+        per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
+        model (then the source may also define smc_user_jac).  Raises ValueError for another method and SmcError with the
+        compiler log if the source does not compile."""
+        if method not in B.USER_METHODS:
+            raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
         obs = _f64(obs, t.shape)
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
-        self._ck(self.L.smc_set_model_user(self.ctx, source.encode(), int(n_states), _dp(t), _dp(obs), _dp(cbuf), t.shape[0],
-                                           t.shape[1], cond.shape[1], int(bool(est_sigma)), float(sigma_fixed), float(rtol),
-                                           float(atol)), "smc_set_model_user")
+        self._ck(self.L.smc_set_model_user2(self.ctx, source.encode(), int(n_states), _dp(t), _dp(obs), _dp(cbuf), t.shape[0],
+                                            t.shape[1], cond.shape[1], int(bool(est_sigma)), float(sigma_fixed), float(rtol),
+                                            float(atol), B.USER_METHODS[method]), "smc_set_model_user")
         self.model = ("user", t.shape[0], t.shape[1])
 
     def set_model_methanation(self, cond, guess, obs, base_params, est_position, est_sigma=True, sigma_fixed=5.0,
@@ -233,6 +236,13 @@ class HipEngine:
         out = (ctypes.c_int64 * 4)()
         self._ck(self.L.smc_meth_sweep_counters(self.ctx, out), "smc_meth_sweep_counters")
         return {"bdf_steps": out[0], "newton_iters": out[1], "factorisations": out[2], "failed_solves": out[3]}
+
+    def user_sweep_counters(self):
+        """Device-counted work of the last sweep of a BDF user model: accepted steps, Newton iterations, LU factorisations,
+        Jacobian evaluations (step attempts: the sweep's rk_attempts)."""
+        out = (ctypes.c_int64 * 4)()
+        self._ck(self.L.smc_user_sweep_counters(self.ctx, out), "smc_user_sweep_counters")
+        return {"steps": out[0], "newton_iters": out[1], "lu_factorisations": out[2], "jacobian_evals": out[3]}
 
     def meth_sweep_check(self):
         """Completeness of the last methanation sweep (the library already fails the sweep when these disagree)."""
