@@ -134,6 +134,32 @@ int smc_user_model_check2(const char *source, int n_states, int dim, int method,
  * tests run the compiler's uniformity analysis on it).  0 ok, 1 a file could not be written, 2 bad arguments.  No GPU needed. */
 int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir);
 int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir);
+/* SEVERAL OBSERVED OUTPUTS, MISSING DATA, RAGGED ROWS (additive; the functions above keep their behaviour, a NaN given to them
+ * still makes logL NaN).  n_obs = 1 .. SMC_USER_MAX_OBS outputs per data time; the source defines
+ *   __device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out);   out[0 .. n_obs)
+ * (with n_obs = 1 a source may define smc_user_obs instead; a source that contains the name smc_user_obs_vec must define it).
+ * t: n_ex x n_t, obs: n_ex x n_t x n_obs, row-major.  NaN in obs = not measured: the entry adds nothing to the squared residuals
+ * nor to m_e, the number of finite entries of experiment e.  A row of t may end in a run of NaN times: that experiment has
+ * n_t_e times, is integrated to t[e][n_t_e - 1], and obs at its NaN times is ignored.  The finite times of a row strictly
+ * increase and every row has one; obs holds no infinite value; obs_scale (n_obs relative scales s_k, NULL = ones) is finite
+ * and > 0 - otherwise smc_set_model_user3 fails with the reason.  With sigma as before (the last parameter or sigma_fixed):
+ *   logL = sum_e [ -m_e / 2 log(2 pi sigma^2) - sum_(observed i,k of e) log s_k - sum_(observed) ((obs - model) / s_k)^2 / (2 sigma^2) ]
+ * (sigma <= 0: -inf; an experiment with m_e = 0 adds 0).  Exact early rejection applies as before.  check3 / dump_source3:
+ * as check2 / dump_source2 (dump_source3 also writes user_obs_args.h); n_obs outside 1 .. SMC_USER_MAX_OBS returns 2. */
+#define SMC_USER_MAX_OBS 8
+int smc_set_model_user3(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                        const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed,
+                        double rtol, double atol, int method);
+int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap);
+int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir);
+/* Model PREDICTIONS of a user model (any of the three set functions; RK45 or BDF), for n host particles (n x dim, AoS; any n -
+ * run in chunks of n_local): lk[n] as smc_loglik computes it and, unless pred is NULL, pred[((p * n_ex + e) * n_t + i) * n_obs + k]
+ * = output k at t[e][i], written for every finite time whether or not obs is measured there; NaN past a row's end and from
+ * where a solve failed on.  Raw outputs, not divided by s_k.  Own staging buffers: the particle sets and their lk are not
+ * touched.  No early rejection.  n_failed / attempts (may be NULL) and, for BDF, smc_user_sweep_counters report THIS call's
+ * work.  A model of smc_set_model_user / 2 is predicted by a kernel compiled at its first call and needs data that
+ * smc_set_model_user3 would accept with no NaN. */
+int smc_user_predict(smc_ctx *ctx, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts);
 /* BDF user model: device-counted work of the LAST smc_loglik / smc_mh_step_* sweep, in the manner of
  * smc_meth_sweep_counters: out = {accepted BDF steps, Newton iterations, LU factorisations, Jacobian evaluations} summed over
  * the sweep's solves (masked proposals left out).  Fails with a message for an RK45 model. */

@@ -16,6 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smc_hip.h")
 
 SMC_SET_PRED, SMC_SET_FILT = 0, 1
 SMC_USER_METHOD_RK45, SMC_USER_METHOD_BDF = 0, 1
+SMC_USER_MAX_OBS = 8
 USER_METHODS = {"RK45": SMC_USER_METHOD_RK45, "BDF": SMC_USER_METHOD_BDF}
 SMC_PRIOR_UNIFORM, SMC_PRIOR_NORMAL, SMC_PRIOR_FLAT = 0, 1, 2
 SMC_PRIOR_MODE_MASK, SMC_PRIOR_MODE_RATIO_MASK, SMC_PRIOR_MODE_RATIO = 0, 1, 2
@@ -59,6 +60,11 @@ SIGNATURES = {
     "smc_set_model_user2": (cint, [c_ctx, ctypes.c_char_p, cint, c_dp, c_dp, c_dp, cint, cint, cint, cint, f64, f64, f64, cint]),
     "smc_user_model_check2": (cint, [ctypes.c_char_p, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source2": (cint, [ctypes.c_char_p, cint, cint, cint, ctypes.c_char_p]),
+    "smc_set_model_user3": (cint, [c_ctx, ctypes.c_char_p, cint, cint, c_dp, c_dp, c_dp, c_dp, cint, cint, cint, cint, f64, f64, f64,
+                                    cint]),
+    "smc_user_model_check3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p, cint]),
+    "smc_user_model_dump_source3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p]),
+    "smc_user_predict": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, c_i64p, c_i64p]),
     "smc_user_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_check": (cint, [c_ctx, c_i64p]),

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -23,7 +24,9 @@
 #include "../../include/smc_hip.h"
 #include "smc_internal.h"
 #include "solve_sched.h"   // kChunk: the grid is sized in chunks of the shared scheduler
+#include "stage_kernels.h" // launch_aos_to_soa (smc_user_predict)
 #include "user_bdf.h"      // the BDF integrator's source (SMC_USER_METHOD_BDF)
+#include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
 
 namespace smc {
 
@@ -525,8 +528,9 @@ extern "C" __global__ void __launch_bounds__(256) smc_user_cost_scan_kernel(smc:
 // log-likelihood of Micmem_likelihood.py:62-73 per particle from the per-item sums; counters as in the built-in path
 __global__ void __launch_bounds__(256)
 user_finish_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, int dim, uint8_t *__restrict__ p0mask,
-                   const double *__restrict__ sum_r2, const int *__restrict__ info, int n_ex, int n_t, int est_sigma,
-                   double sigma_fixed, double *__restrict__ lk_out, SweepCounters *__restrict__ counters) {
+                   const double *__restrict__ sum_r2, const int *__restrict__ info, int n_ex, const double *__restrict__ me,
+                   const double *__restrict__ ls, int est_sigma, double sigma_fixed, double *__restrict__ lk_out,
+                   SweepCounters *__restrict__ counters) {
     unsigned long long attempts = 0, failed = 0;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
         const bool masked = p0mask && p0mask[p] == 0;   // proposal reset to the current point: the stored likelihood is used
@@ -534,11 +538,14 @@ user_finish_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, 
         if (!masked && sigma <= 0.0) lk_out[p] = -__longlong_as_double(0x7ff0000000000000LL);   // Micmem_likelihood.py:53-54
         if (!masked && sigma > 0.0) {
             const double s2 = sigma * sigma;
-            const double c0 = (-0.5 * n_t) * log(2.0 * 3.141592653589793 * s2);
+            // per experiment c0 = -m_e / 2 log(2 pi sigma^2) - sum log s_k over its m_e observations: m_e = n_t and 0 for a model
+            // of smc_set_model_user / smc_set_model_user2, whose c0 this is bit for bit.  The early-rejection bound of the
+            // multi-output kernels (user_model_source3) evaluates the same expression in the same order.
+            const double lg = log(2.0 * 3.141592653589793 * s2);
             double lk = 0.0;
             unsigned pf = 0, cancelled = 0;
             for (int e = 0; e < n_ex; ++e) {
-                lk += c0 - sum_r2[(int64_t)e * n + p] / (2.0 * s2);
+                lk += ((-0.5 * me[e]) * lg - ls[e]) - sum_r2[(int64_t)e * n + p] / (2.0 * s2);
                 const int fl = info[(int64_t)e * n + p];
                 attempts += (unsigned)(fl & 0x1fffffff);
                 pf |= (unsigned)(fl >> 30) & 1u;
@@ -594,6 +601,20 @@ struct UserModel {
     int method = SMC_USER_METHOD_RK45;
     unsigned *d_bdf_counts = nullptr;          // BDF: per item {accepted steps, Newton iterations, LU factorisations, Jacobians}
     unsigned long long *d_bdf_totals = nullptr;   // ... their sums over the last sweep (user_bdf_count_kernel)
+    double *d_const = nullptr;            // [2 n_ex]: m_e, then sum log s_k (user_finish_kernel); n_t and 0 for a one-output model
+    // smc_set_model_user3 (user_obs_args.h): `multi` models run the multi-output source, whose module also holds the
+    // prediction kernel; a model of smc_set_model_user / 2 compiles that source with n_obs = 1 when it first predicts
+    bool multi = false;
+    int n_obs = 1;
+    std::string source;
+    double *d_img = nullptr;              // the LDS image (nullptr: one-output data the image cannot hold, img_error says why)
+    int img_len = 0;
+    std::string img_error;
+    hipModule_t module_pred = nullptr;
+    hipFunction_t fn_pred = nullptr;
+    int blocks_per_cu_pred = 4;
+    double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;   // smc_user_predict's staging: parameters (AoS + SoA), lk, pred
+    int64_t p_cap = 0;
 };
 
 // the optional fourth ingredient: a source that mentions smc_user_cost must define it (include/smc_hip.h)
@@ -623,12 +644,140 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
            "\n}  // namespace smc_user_ieee\n" + kUserKernelSource;
 }
 
-// compile for gfx950; on failure `log` holds hiprtc's diagnostics
-static bool compile_user(const std::string &src, std::vector<char> &code, std::string &log) {
+// The multi-output source (smc_set_model_user3): the one-output source of the same method with the data-side replacements
+// below and its kernel body compiled twice - the sweep kernel, and with SMC_USER_PRED = 1 under other names the prediction
+// kernel smc_user_predict_kernel (so the sweep kernel's code does not carry the prediction stores).  The one-output text
+// itself is left as it is: what smc_set_model_user / 2 hand to hiprtc does not change.  Every replacement must match the
+// stated number of times.
+struct SourcePatch {
+    const char *from, *to;
+    int count;
+};
+static const SourcePatch kPatchesCommon[] = {
+    {"const double2 *", "const smc_obs::Rec *", 5},          // the data table: records of user_obs_args.h
+    {"double2 nx = tp[i_out];", "smc_obs::Rec nx = tp[i_out];", 1},
+    {"tp[n_t - 1].x", "tp[n_t].y[0]", 2},                    // t_bound: the row's own end time, kept in its last record
+    {"    for (int i = threadIdx.x; i < a.n_ex * (a.n_t + 1); i += blockDim.x) {\n"
+     "        const int e = i / (a.n_t + 1), k = i - e * (a.n_t + 1);\n"
+     "        s_tp[i] = (k < a.n_t) ? make_double2(a.t[e * a.n_t + k], a.obs[e * a.n_t + k])\n"
+     "                              : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);\n"
+     "    }\n",
+     "    for (int i = threadIdx.x; i < o.img_len; i += blockDim.x) smc_obs::lds()[i] = o.img[i];   // the host-built image\n", 1},
+    // early rejection: the per-experiment constant of user_finish_kernel, the same expression in the same order
+    {"        const double c0 = (-0.5 * a.n_t) * log(2.0 * 3.141592653589793 * s2);\n",
+     "        const double lg = log(2.0 * 3.141592653589793 * s2);\n", 1},
+    {"            lk2_bound += c0 - S / (2.0 * s2);\n",
+     "            lk2_bound += ((-0.5 * smc_obs::me(k)) * lg - smc_obs::sum_log_scale(k, a.n_ex)) - S / (2.0 * s2);\n", 1},
+    // predictions: the item's pointer to its next output follows from out_idx and i_out (no pool word)
+    {"    __device__ __forceinline__ void load_theta(Item &it, long long p) const {\n",
+     "    double *pred;               // prediction kernel: UserObsArgs::pred\n"
+     "    __device__ __forceinline__ double *pred_at(long long idx, int e, int i) const {\n"
+     "        return SMC_USER_PRED ? pred + (((idx - (long long)e * a.n) * a.n_ex + e) * a.n_t + i) * smc_obs::kObs : nullptr;\n"
+     "    }\n"
+     "    // prediction kernel: NaN from the first output time not served on (past the row's end; from a failed solve's stop)\n"
+     "    template <class S>\n"
+     "    __device__ __forceinline__ void pred_tail(const S &s) const {\n"
+     "        if (SMC_USER_PRED) {\n"
+     "            for (int i = s.i_out; i < a.n_t; ++i)\n"
+     "                for (int k = 0; k < smc_obs::kObs; ++k) s.pred[(i - s.i_out) * smc_obs::kObs + k] = __longlong_as_double(0x7ff8000000000000LL);\n"
+     "        }\n"
+     "    }\n"
+     "    __device__ __forceinline__ void load_theta(Item &it, long long p) const {\n", 1},
+    {"        load_theta(nb, p);\n", "        load_theta(nb, p);\n        nb.s.pred = pred_at(nb.out_idx, e, 0);\n", 1},
+    {"        publish(nb.out_idx, nb.s.sr2, nb.s.status < 0 ? (1 << 30) : 0);\n",
+     "        pred_tail(nb.s);\n        publish(nb.out_idx, nb.s.sr2, nb.s.status < 0 ? (1 << 30) : 0);\n", 1},
+    {"        it.out_idx = __double_as_longlong(slot[5 * 64]);\n",
+     "        it.out_idx = __double_as_longlong(slot[5 * 64]);\n        it.s.pred = pred_at(it.out_idx, it.e, it.s.i_out);\n", 1},
+    {"    __device__ __forceinline__ void finish(Item &it, int st) const {\n",
+     "    __device__ __forceinline__ void finish(Item &it, int st) const {\n        pred_tail(it.s);\n", 1},
+    {"        u.s.i_out = __builtin_amdgcn_readlane(it.s.i_out, src);\n",
+     "        u.s.pred = SMC_USER_PRED ? (double *)smc::lane_value_ll((long long)it.s.pred, src) : nullptr;\n"
+     "        u.s.i_out = __builtin_amdgcn_readlane(it.s.i_out, src);\n", 1},
+};
+static const SourcePatch kPatchesRk45[] = {
+    {"    static __device__ __forceinline__ double obs(double t, const double *y, const double *th, const double *c) { return smc_user_ieee::smc_user_obs(t, y, th, c); }\n",
+     "", 1},
+    {"    int i_out, status;   // status:",
+     "    double *pred;             // prediction kernel: where the outputs of t_eval[i_out] go\n    int i_out, status;   // status:", 1},
+    {"__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {\n"
+     "    const double r = obs - Ieee::obs(t_out, yy, theta, cond);\n"
+     "    it.sr2 += r * r;\n",
+     "__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, const double *obs) {\n"
+     "    smc_obs::emit<SMC_USER_PRED, true>(it.sr2, it.pred, yy, theta, cond, t_out, obs);\n", 1},
+    {"smc_user_solve_kernel(smc::UserSolveArgs a) {", "smc_user_solve_kernel(smc::UserSolveArgs a, smc::UserObsArgs o) {", 1},
+    {"    double2 *s_tp = reinterpret_cast<double2 *>(s_pool_all + 4 * (UserOps::kPoolWords * 64));   // the data, read by every output\n",
+     "    static_assert(4 * UserOps::kPoolWords * 64 == smc_obs::kHdrAt, \"user_obs_args.h: the image follows the pools\");\n"
+     "    const smc_obs::Rec *s_tp = smc_obs::table(a.n_ex);   // the data, read by every output\n", 1},
+    {": a.n, s_tp};", ": a.n, s_tp, o.pred};", 1},
+};
+static const SourcePatch kPatchesBdf[] = {
+    {"    int order, n_equal_steps, i_out, status;",
+     "    double *pred;                  // prediction kernel: where the outputs of t_eval[i_out] go\n    int order, n_equal_steps, i_out, status;", 1},
+    {"__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {\n"
+     "    const double r = obs - smc_user_ieee::smc_user_obs(t_out, yy, theta, cond);\n"
+     "    it.sr2 += r * r;\n",
+     "__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, const double *obs) {\n"
+     "    smc_obs::emit<SMC_USER_PRED, false>(it.sr2, it.pred, yy, theta, cond, t_out, obs);\n", 1},
+    {"smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts) {",
+     "smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts, smc::UserObsArgs o) {", 1},
+    {"    double2 *s_tp = reinterpret_cast<double2 *>(s_pool_all + 4 * (UserBdfOps::kPoolWords * 64));\n",
+     "    static_assert(4 * UserBdfOps::kPoolWords * 64 == smc_obs::kHdrAt, \"user_obs_args.h: the image follows the pools\");\n"
+     "    const smc_obs::Rec *s_tp = smc_obs::table(a.n_ex);\n", 1},
+    {": a.n, s_tp, counts};", ": a.n, s_tp, counts, o.pred};", 1},
+};
+
+static bool apply_patches(std::string &s, const SourcePatch *p, int n, std::string &err) {
+    for (int i = 0; i < n; ++i) {
+        int found = 0;
+        for (size_t at = s.find(p[i].from); at != std::string::npos; at = s.find(p[i].from, at + strlen(p[i].from))) ++found;
+        if (found != p[i].count) {
+            err = std::string("internal: the multi-output replacement of \"") + std::string(p[i].from).substr(0, 60) + "\" matched " +
+                  std::to_string(found) + " times";
+            return false;
+        }
+        std::string out;
+        size_t pos = 0;
+        for (size_t at = s.find(p[i].from); at != std::string::npos; at = s.find(p[i].from, pos)) {
+            out.append(s, pos, at - pos).append(p[i].to);
+            pos = at + strlen(p[i].from);
+        }
+        s = out + s.substr(pos);
+    }
+    return true;
+}
+
+// a source that mentions smc_user_obs_vec must define it; with n_obs > 1 it is the only way to give the outputs
+static bool has_obs_vec(const char *user_source) { return strstr(user_source, "smc_user_obs_vec") != nullptr; }
+
+static bool build_source3(const char *user_source, int n_states, int dim, int method, int n_obs, std::string &src, std::string &err) {
+    const std::string one = build_source(user_source, n_states, dim, method);
+    const size_t body = one.find("// ---- appended by libsmc_hip.so after the user's source"), scan = one.find("#ifdef SMC_USER_HAS_COST", body);
+    if (body == std::string::npos || scan == std::string::npos) {
+        err = "internal: the kernel source has no body";
+        return false;
+    }
+    std::string k = one.substr(body, scan - body);
+    if (!apply_patches(k, kPatchesCommon, (int)(sizeof kPatchesCommon / sizeof *kPatchesCommon), err)) return false;
+    if (method == SMC_USER_METHOD_BDF ? !apply_patches(k, kPatchesBdf, (int)(sizeof kPatchesBdf / sizeof *kPatchesBdf), err)
+                                      : !apply_patches(k, kPatchesRk45, (int)(sizeof kPatchesRk45 / sizeof *kPatchesRk45), err))
+        return false;
+    char head[160];
+    snprintf(head, sizeof head, "#define SMC_USER_NOBS %d\n#define SMC_USER_HAS_OBS_VEC %d\n", n_obs,
+             (n_obs > 1 || has_obs_vec(user_source)) ? 1 : 0);
+    src = std::string(head) + one.substr(0, body) + "#include \"user_obs_args.h\"\n#define SMC_USER_PRED 0\n" + k +
+          "#undef SMC_USER_PRED\n// ---- the same once more: the prediction kernel ----\n#define SMC_USER_PRED 1\n"
+          "#define smc_user smc_user_pred\n#define UserOps UserOpsPred\n#define smc_user_bdf smc_user_bdf_pred\n"
+          "#define UserBdfOps UserBdfOpsPred\n#define smc_user_solve_kernel smc_user_predict_kernel\n" + k +
+          "#undef smc_user\n#undef UserOps\n#undef smc_user_bdf\n#undef UserBdfOps\n#undef smc_user_solve_kernel\n" + one.substr(scan);
+    return true;
+}
+
+// compile for gfx950; on failure `log` holds hiprtc's diagnostics.  obs_header: the multi-output source's fifth header
+static bool compile_user(const std::string &src, std::vector<char> &code, std::string &log, bool obs_header = false) {
     hiprtcProgram prog;
-    const char *headers[] = {k_sweep_args_h, k_philox_h, k_solve_sched_h, k_rk45_math_h};
-    const char *names[] = {"sweep_args.h", "philox.h", "solve_sched.h", "rk45_math.h"};
-    if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", 4, headers, names) != HIPRTC_SUCCESS) {
+    const char *headers[] = {k_sweep_args_h, k_philox_h, k_solve_sched_h, k_rk45_math_h, k_user_obs_args_h};
+    const char *names[] = {"sweep_args.h", "philox.h", "solve_sched.h", "rk45_math.h", "user_obs_args.h"};
+    if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", obs_header ? 5 : 4, headers, names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return false;
     }
@@ -665,6 +814,12 @@ void user_model_release(smc_ctx *c) {
     (void)hipFree(u->d_count);
     (void)hipFree(u->d_bdf_counts);
     (void)hipFree(u->d_bdf_totals);
+    (void)hipFree(u->d_const);
+    (void)hipFree(u->d_img);
+    (void)hipFree(u->d_pt);
+    (void)hipFree(u->d_plk);
+    (void)hipFree(u->d_ppred);
+    if (u->module_pred) (void)hipModuleUnload(u->module_pred);
     if (u->module) (void)hipModuleUnload(u->module);
     delete u;
     c->user = nullptr;
@@ -674,9 +829,16 @@ void user_model_release(smc_ctx *c) {
 static size_t user_lds_bytes(int n_states, int n_ex, int n_t) {
     return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)2 * n_ex * (n_t + 1)) * sizeof(double);
 }
+// ... of the multi-output kernels: the pools, then the image of user_obs_args.h
+static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs) {
+    return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)obs_table_at(n_ex) + (size_t)n_ex * (n_t + 1) * obs_rec_words(n_obs)) *
+           sizeof(double);
+}
+static const size_t kUserLdsCap = 150 * 1024;
 
+// pred != nullptr: the prediction kernel (smc_user_predict) - it writes there, and the BDF totals then add up over its chunks
 static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, int64_t n, uint8_t *p0mask, double *lk,
-                               bool reject) {
+                               bool reject, double *pred = nullptr) {
     UserModel *u = (UserModel *)c->user;
     UserSolveArgs a{};
     a.theta = theta;
@@ -703,10 +865,11 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     const bool lists = u->fn_scan && c->stiff_first != 0;
     const int64_t chunks = (((n + 63) / 64) * 64 * u->n_ex + kChunk - 1) / kChunk;
     const int64_t need = (chunks + 3) / 4 + (lists ? (n * u->n_ex + 3) / 4 : 0);
-    int64_t blocks = (int64_t)c->cu_count * u->blocks_per_cu;
+    int64_t blocks = (int64_t)c->cu_count * (pred ? u->blocks_per_cu_pred : u->blocks_per_cu);
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
-    const unsigned lds = (unsigned)user_lds_bytes(u->n_states, u->n_ex, u->n_t);
+    const bool multi = u->multi || pred;
+    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
     if (lists) {
         u->parity ^= 1;
         UserScanArgs sa{};
@@ -749,11 +912,15 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
             }
         }
     }
-    void *args[] = {&a, &u->d_bdf_counts};     // the RK45 kernel takes the first only
+    UserObsArgs o{u->d_img, u->img_len, pred};
+    void *args1[] = {&a, &u->d_bdf_counts};     // the RK45 kernel takes the first only
+    void *args3[] = {&a, &o};                   // multi-output kernels: RK45 ...
+    void *args3b[] = {&a, &u->d_bdf_counts, &o};   // ... and BDF
+    void **args = !multi ? args1 : (u->method == SMC_USER_METHOD_BDF ? args3b : args3);
     {
         ScopedTimer tm(c, SMC_T_SOLVE);
         (void)hipMemsetAsync(c->d_queue, 0, sizeof(unsigned long long), c->stream);
-        const hipError_t e = hipModuleLaunchKernel(u->fn, (unsigned)blocks, 1, 1, 256, 1, 1, lds, c->stream, args, nullptr);
+        const hipError_t e = hipModuleLaunchKernel(pred ? u->fn_pred : u->fn, (unsigned)blocks, 1, 1, 256, 1, 1, lds, c->stream, args, nullptr);
         if (e != hipSuccess) {
             smc_fail(c, (std::string("launch of the user-model kernel failed: ") + hipGetErrorString(e)).c_str());
             c->launch_failed = true;
@@ -762,9 +929,10 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     }
     const int64_t g = (n + 255) / 256;
     hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
-                       c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->n_t, u->est_sigma, u->sigma_fixed, lk, c->d_counters);
+                       c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
+                       lk, c->d_counters);
     if (u->method == SMC_USER_METHOD_BDF) {
-        (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
+        if (!pred) (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
         const int64_t items = n * u->n_ex, gb = (items + 255) / 256;
         hipLaunchKernelGGL(user_bdf_count_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0, c->stream, p0mask, u->d_bdf_counts,
                            n, u->n_ex, u->d_bdf_totals);
@@ -793,6 +961,78 @@ void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
     launch_generic_accept(c, n, mh, c->d_mlk2);
 }
 
+// smc_set_model_user3's data rules (include/smc_hip.h; user_models.obs_layout is the same in NumPy): every row of t is a
+// strictly increasing run of n_t_e >= 1 finite times followed by NaN only; NaN in obs is a value not measured (what lies at a
+// NaN time is ignored), an infinite one is refused; obs_scale (nullptr: ones) is finite and > 0.  On success me / ls hold
+// m_e and the sum of log s_k over the observed values of each experiment; "" = valid, else what is wrong.
+static std::string obs_layout(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
+                              std::vector<double> &me, std::vector<double> &ls) {
+    for (int k = 0; k < n_obs; ++k)
+        if (scale && !(std::isfinite(scale[k]) && scale[k] > 0.0)) return "obs_scale must be finite and > 0";
+    me.assign(n_ex, 0.0);
+    ls.assign(n_ex, 0.0);
+    for (int e = 0; e < n_ex; ++e) {
+        const double *te = t + (size_t)e * n_t;
+        int len = 0;
+        while (len < n_t && !std::isnan(te[len])) ++len;
+        const std::string row = "row " + std::to_string(e) + " of t ";
+        for (int i = len; i < n_t; ++i)
+            if (!std::isnan(te[i])) return row + "has a NaN time before a number (only a trailing run of NaN may shorten a row)";
+        if (len == 0) return row + "has no finite time";
+        for (int i = 0; i < len; ++i) {
+            if (!std::isfinite(te[i])) return row + "holds an infinite time";
+            if (i > 0 && !(te[i] > te[i - 1])) return row + "is not strictly increasing";
+        }
+        for (int i = 0; i < len; ++i)
+            for (int k = 0; k < n_obs; ++k) {
+                const double v = obs[((size_t)e * n_t + i) * n_obs + k];
+                if (std::isnan(v)) continue;
+                if (!std::isfinite(v)) return "obs holds an infinite value (NaN marks a value that was not measured)";
+                me[e] += 1.0;
+                ls[e] += scale ? std::log(scale[k]) : 0.0;
+            }
+    }
+    return "";
+}
+
+// the LDS image of user_obs_args.h for data obs_layout has accepted
+static std::vector<double> build_obs_image(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
+                                           const std::vector<double> &me, const std::vector<double> &ls) {
+    const int R = obs_rec_words(n_obs), at = obs_table_at(n_ex);
+    std::vector<double> img((size_t)at + (size_t)n_ex * (n_t + 1) * R, 0.0);
+    for (int k = 0; k < kObsHdrMe; ++k) img[k] = (scale && k < n_obs) ? 1.0 / scale[k] : 1.0;
+    for (int e = 0; e < n_ex; ++e) {
+        img[kObsHdrMe + e] = me[e];
+        img[kObsHdrMe + n_ex + e] = ls[e];
+        const double *te = t + (size_t)e * n_t;
+        int len = 0;
+        while (len < n_t && !std::isnan(te[len])) ++len;
+        double *row = img.data() + at + (size_t)e * (n_t + 1) * R;
+        for (int i = 0; i <= n_t; ++i) {
+            double *r = row + (size_t)i * R;
+            if (i < len) {
+                r[0] = te[i];
+                for (int k = 0; k < n_obs; ++k) r[1 + k] = obs[((size_t)e * n_t + i) * n_obs + k];
+            } else {
+                r[0] = HUGE_VAL;          // the sentinel: no output time is ever >= it
+                r[1] = te[len - 1];       // t_bound
+            }
+        }
+    }
+    return img;
+}
+
+// occupancy and LDS limit of the prediction kernel (u->fn_pred)
+static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
+    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs);
+    int nb = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu_pred = nb;
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(u->fn_pred), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return smc_fail(c, "smc_user_predict: raising the dynamic LDS limit of the prediction kernel failed");
+    return 0;
+}
+
 }  // namespace smc
 
 using namespace smc;
@@ -800,6 +1040,7 @@ using namespace smc;
 extern "C" {
 
 static bool user_method_ok(int method) { return method == SMC_USER_METHOD_RK45 || method == SMC_USER_METHOD_BDF; }
+static bool user_obs_ok(int n_obs) { return n_obs >= 1 && n_obs <= SMC_USER_MAX_OBS; }
 
 int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap) {
     if (!source || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method)) return 2;
@@ -817,13 +1058,24 @@ int smc_user_model_check(const char *source, int n_states, int dim, char *log, i
     return smc_user_model_check2(source, n_states, dim, SMC_USER_METHOD_RK45, log, log_cap);
 }
 
-int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir) {
-    if (!source || !dir || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method))
+int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap) {
+    if (!source || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method) ||
+        !user_obs_ok(n_obs))
         return 2;
-    const std::string src = build_source(source, n_states, dim, method);
-    const char *names[] = {"smc_user_model.hip", "sweep_args.h", "philox.h", "solve_sched.h", "rk45_math.h"};
-    const char *texts[] = {src.c_str(), k_sweep_args_h, k_philox_h, k_solve_sched_h, k_rk45_math_h};
-    for (int i = 0; i < 5; ++i) {
+    std::vector<char> code;
+    std::string src, lg;
+    const bool ok = build_source3(source, n_states, dim, method, n_obs, src, lg) && compile_user(src, code, lg, true);
+    if (log && log_cap > 0) {
+        strncpy(log, lg.c_str(), (size_t)log_cap - 1);
+        log[log_cap - 1] = 0;
+    }
+    return ok ? 0 : 1;
+}
+
+static int dump_files(const char *dir, const std::string &src, int n_files) {
+    const char *names[] = {"smc_user_model.hip", "sweep_args.h", "philox.h", "solve_sched.h", "rk45_math.h", "user_obs_args.h"};
+    const char *texts[] = {src.c_str(), k_sweep_args_h, k_philox_h, k_solve_sched_h, k_rk45_math_h, k_user_obs_args_h};
+    for (int i = 0; i < n_files; ++i) {
         FILE *f = fopen((std::string(dir) + "/" + names[i]).c_str(), "w");
         if (!f) return 1;
         const bool ok = fputs(texts[i], f) >= 0;
@@ -832,21 +1084,48 @@ int smc_user_model_dump_source2(const char *source, int n_states, int dim, int m
     return 0;
 }
 
+int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir) {
+    if (!source || !dir || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method))
+        return 2;
+    return dump_files(dir, build_source(source, n_states, dim, method), 5);
+}
+
 int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir) {
     return smc_user_model_dump_source2(source, n_states, dim, SMC_USER_METHOD_RK45, dir);
 }
 
-int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
-                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method) {
+int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir) {
+    if (!source || !dir || n_states < 1 || n_states > SMC_USER_MAX_STATES || dim < 1 || dim > SMC_MAX_DIM || !user_method_ok(method) ||
+        !user_obs_ok(n_obs))
+        return 2;
+    std::string src, err;
+    if (!build_source3(source, n_states, dim, method, n_obs, src, err)) return 1;
+    return dump_files(dir, src, 6);
+}
+
+// The models of all three set functions.  multi: smc_set_model_user3 (obs n_ex x n_t x n_obs, validated, the multi-output
+// source); else the one-output source and data exactly as before, plus the image for a later smc_user_predict when the data
+// allows one.
+static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                               const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
+                               double sigma_fixed, double rtol, double atol, int method, bool multi) {
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
     if (n_states < 1 || n_states > SMC_USER_MAX_STATES) return smc_fail(c, "smc_set_model_user: n_states out of range");
+    if (multi && !user_obs_ok(n_obs)) return smc_fail(c, "smc_set_model_user3: n_obs out of range (1 .. SMC_USER_MAX_OBS)");
     if (n_ex < 1 || n_t < 1 || n_cond < 0) return smc_fail(c, "smc_set_model_user: bad data shape");
+    std::vector<double> me, ls;
+    std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls) : std::string("NULL t or obs");
+    if (multi && !bad.empty()) return smc_fail(c, ("smc_set_model_user3: " + bad).c_str());
+    if (multi && user_lds_bytes3(n_states, n_ex, n_t, n_obs) > kUserLdsCap)
+        return smc_fail(c, "smc_set_model_user3: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) "
+                           "(n_obs + 2 rounded down to even)) x 8 B + pools > 150 KB)");
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
-    std::string lg;
-    if (!compile_user(build_source(source, n_states, c->dim, method), code, lg)) {
+    std::string lg, src;
+    if (multi ? !(build_source3(source, n_states, c->dim, method, n_obs, src, lg) && compile_user(src, code, lg, true))
+              : !compile_user(build_source(source, n_states, c->dim, method), code, lg)) {
         std::string msg = "user model does not compile:\n" + lg;
         if (msg.size() > 3500) msg.resize(3500);
         return smc_fail(c, msg.c_str());
@@ -856,7 +1135,8 @@ int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const doub
     UserModel *u = new UserModel();
     c->user = u;
     if (hipModuleLoadData(&u->module, code.data()) != hipSuccess ||
-        hipModuleGetFunction(&u->fn, u->module, "smc_user_solve_kernel") != hipSuccess) {
+        hipModuleGetFunction(&u->fn, u->module, "smc_user_solve_kernel") != hipSuccess ||
+        (multi && hipModuleGetFunction(&u->fn_pred, u->module, "smc_user_predict_kernel") != hipSuccess)) {
         user_model_release(c);
         return smc_fail(c, "smc_set_model_user: loading the compiled module failed");
     }
@@ -865,10 +1145,33 @@ int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const doub
         return smc_fail(c, "smc_set_model_user: the source mentions smc_user_cost but the scan kernel is missing from the module");
     }
     const size_t nt = (size_t)n_ex * n_t * sizeof(double), nc = (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
-    bool ok = hipMalloc(&u->d_t, nt) == hipSuccess && hipMalloc(&u->d_obs, nt) == hipSuccess && hipMalloc(&u->d_cond, nc) == hipSuccess;
-    ok = ok && hipMemcpy(u->d_t, t, nt, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(u->d_obs, obs, nt, hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = hipMalloc(&u->d_cond, nc) == hipSuccess;
+    if (ok && !multi)      // the one-output kernel reads the data itself
+        ok = hipMalloc(&u->d_t, nt) == hipSuccess && hipMalloc(&u->d_obs, nt) == hipSuccess &&
+             hipMemcpy(u->d_t, t, nt, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(u->d_obs, obs, nt, hipMemcpyHostToDevice) == hipSuccess;
     if (ok && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    {   // likelihood constants; and the image (one-output model: only if its data is what smc_set_model_user3 would accept)
+        std::vector<double> k(2 * (size_t)n_ex, 0.0);
+        for (int e = 0; e < n_ex; ++e) {
+            k[e] = multi ? me[e] : (double)n_t;
+            k[n_ex + e] = multi ? ls[e] : 0.0;
+        }
+        ok = ok && hipMalloc(&u->d_const, k.size() * sizeof(double)) == hipSuccess &&
+             hipMemcpy(u->d_const, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        if (bad.empty() && !multi) {
+            for (int e = 0; e < n_ex; ++e)
+                if (me[e] != (double)n_t) bad = "a missing observation (NaN)";
+        }
+        if (bad.empty()) {
+            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls);
+            u->img_len = (int)img.size();
+            ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
+                 hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        } else {
+            u->img_error = "smc_user_predict: the data of this model (set through smc_set_model_user / smc_set_model_user2) cannot be "
+                           "predicted: " + bad + "; set it through smc_set_model_user3";
+        }
+    }
     if (ok && !c->d_mlk2) ok = hipMalloc(&c->d_mlk2, (size_t)c->n_local * sizeof(double)) == hipSuccess;
     ok = ok && hipMalloc(&u->d_sum, (size_t)c->n_local * n_ex * sizeof(double)) == hipSuccess &&
          hipMalloc(&u->d_info, (size_t)c->n_local * n_ex * sizeof(int)) == hipSuccess;
@@ -884,10 +1187,12 @@ int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const doub
         user_model_release(c);
         return smc_fail(c, "smc_set_model_user: device allocation / upload failed");
     }
+    u->n_obs = n_obs;
+    u->multi = multi;
     {   // occupancy of the compiled kernel with its pool in LDS
         int nb = 0;
-        const size_t lds = user_lds_bytes(n_states, n_ex, n_t);
-        if (lds > 150 * 1024) {
+        const size_t lds = multi ? user_lds_bytes3(n_states, n_ex, n_t, n_obs) : user_lds_bytes(n_states, n_ex, n_t);
+        if (lds > kUserLdsCap) {
             user_model_release(c);
             return smc_fail(c, "smc_set_model_user: data set too large for the kernel's LDS table (n_ex * n_t * 16 B + pools > 150 KB)");
         }
@@ -898,6 +1203,7 @@ int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const doub
             return smc_fail(c, "smc_set_model_user: raising the dynamic LDS limit of the compiled kernel failed");
         }
     }
+    u->source = source;
     u->n_ex = n_ex;
     u->n_t = n_t;
     u->n_cond = n_cond;
@@ -907,9 +1213,19 @@ int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const doub
     u->rtol = rtol;
     u->atol = atol;
     u->method = method;
+    if (multi && prepare_pred_kernel(c, u) != 0) {
+        user_model_release(c);
+        return 1;
+    }
     c->model_kind = 3;
     c->have_model = true;
     return 0;
+}
+
+int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
+                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method) {
+    return set_model_user_impl(c, source, n_states, 1, t, obs, cond, nullptr, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
+                               method, false);
 }
 
 int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
@@ -918,6 +1234,81 @@ int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const doubl
                                SMC_USER_METHOD_RK45);
 }
 
+int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol,
+                        double atol, int method) {
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol,
+                               atol, method, true);
+}
+
+int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_predict: no user model has been set");
+    if (n < 0 || (n > 0 && (!particle || !lk))) return smc_fail(c, "smc_user_predict: bad arguments");
+    if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
+    if (n_failed) *n_failed = 0;
+    if (attempts) *attempts = 0;
+    if (n == 0) return 0;
+    if (!u->d_img) return smc_fail(c, u->img_error.c_str());
+    if (!u->fn_pred) {      // a one-output model of smc_set_model_user / 2: its prediction kernel, compiled once
+        if (user_lds_bytes3(u->n_states, u->n_ex, u->n_t, 1) > kUserLdsCap)
+            return smc_fail(c, "smc_user_predict: data set too large for the prediction kernel's LDS table");
+        std::vector<char> code;
+        std::string src, lg;
+        if (!(build_source3(u->source.c_str(), u->n_states, c->dim, u->method, 1, src, lg) && compile_user(src, code, lg, true)))
+            return smc_fail(c, ("smc_user_predict: the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
+        if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
+            hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
+            u->fn_pred = nullptr;
+            return smc_fail(c, "smc_user_predict: loading the prediction module failed");
+        }
+        if (prepare_pred_kernel(c, u) != 0) {
+            u->fn_pred = nullptr;
+            return 1;
+        }
+    }
+    const int dim = c->dim;
+    const int64_t chunk = n < c->n_local ? n : c->n_local;      // the per-item buffers hold n_local particles
+    const size_t per = (size_t)u->n_ex * u->n_t * u->n_obs;
+    if (chunk > u->p_cap) {
+        (void)hipFree(u->d_pt);
+        (void)hipFree(u->d_plk);
+        (void)hipFree(u->d_ppred);
+        u->d_pt = u->d_plk = u->d_ppred = nullptr;
+        u->p_cap = 0;
+        if (hipMalloc(&u->d_pt, (size_t)chunk * dim * 2 * sizeof(double)) != hipSuccess ||
+            hipMalloc(&u->d_plk, (size_t)chunk * sizeof(double)) != hipSuccess ||
+            hipMalloc(&u->d_ppred, (size_t)chunk * per * sizeof(double)) != hipSuccess)
+            return smc_fail(c, "smc_user_predict: device allocation failed");
+        u->p_cap = chunk;
+    }
+    double *aos = u->d_pt, *soa = u->d_pt + (size_t)u->p_cap * dim;
+    if (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
+        (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess))
+        return smc_fail(c, "smc_user_predict: clearing the counters failed");
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = (n - off < chunk) ? n - off : chunk;
+        if (hipMemcpyAsync(aos, particle + off * dim, (size_t)m * dim * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return smc_fail(c, "smc_user_predict: upload failed");
+        launch_aos_to_soa(c, aos, soa, m, dim, m);
+        launch_user_kernel(c, soa, m, m, nullptr, u->d_plk, false, u->d_ppred);
+        if (c->launch_failed) {
+            c->launch_failed = false;
+            return 1;
+        }
+        if (hipMemcpyAsync(lk + off, u->d_plk, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            (pred && hipMemcpyAsync(pred + (size_t)off * per, u->d_ppred, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream) != hipSuccess))
+            return smc_fail(c, "smc_user_predict: download failed");
+    }
+    if (hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return smc_fail(c, (std::string("smc_user_predict: ") + hipGetErrorString(hipGetLastError())).c_str());
+    if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
+    if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
+    return 0;
+}
 int smc_user_sweep_counters(smc_ctx *c, int64_t out[4]) {
     if (!c) return smc_fail(nullptr, "NULL context");
     UserModel *u = (UserModel *)c->user;

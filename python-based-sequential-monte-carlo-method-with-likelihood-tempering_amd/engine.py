@@ -123,6 +123,7 @@ class HipEngine:
             raise SmcError(f"smc_create: {msg.decode() if msg else 'unknown error'}")
         self.ctx = ctx
         self.model = None
+        self.user_n_obs = 1     # outputs per data time of a user model (set_model_user)
         if "smc_ess_search_global" in B.MISSING:   # A/B build of an older revision (SMC_HIP_LIB): the driver falls back
             self.ess_search_global = None
         self._peer_barrier = None
@@ -169,22 +170,44 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6, method="RK45"):
+                       atol=1e-6, method="RK45", obs_scale=None):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
         model (then the source may also define smc_user_jac).  Raises ValueError for another method and SmcError with the
-        compiler log if the source does not compile."""
+        compiler log if the source does not compile.
+        Several measured outputs, missing data, ragged rows (smc_set_model_user3): obs (n_ex, n_t, n_obs) with NaN for a value
+        that was not measured, t rows that may end in NaN times, obs_scale (n_obs,) relative noise scales; the source then
+        defines smc_user_obs_vec.  A 3-D obs or any obs_scale takes this path (ValueError for data it refuses, see
+        user_models.obs_layout); a 2-D obs without obs_scale goes through smc_set_model_user2 exactly as before."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
-        obs = _f64(obs, t.shape)
+        obs = np.asarray(obs)
+        multi = obs.ndim == 3 or obs_scale is not None
+        if multi:
+            # several outputs, NaN = not measured, ragged rows (smc_set_model_user3); the same checks as the library's
+            obs = _f64(obs if obs.ndim == 3 else obs.reshape(obs.shape + (1,)))
+            from .user_models import obs_layout
+            obs_layout(t, obs, obs_scale)
+            n_obs = obs.shape[2]
+            scale = None if obs_scale is None else _f64(np.asarray(obs_scale).reshape(-1), (n_obs,))
+        else:
+            obs = _f64(obs, t.shape)
+            n_obs = 1
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
-        self._ck(self.L.smc_set_model_user2(self.ctx, source.encode(), int(n_states), _dp(t), _dp(obs), _dp(cbuf), t.shape[0],
-                                            t.shape[1], cond.shape[1], int(bool(est_sigma)), float(sigma_fixed), float(rtol),
-                                            float(atol), B.USER_METHODS[method]), "smc_set_model_user")
-        self.model = ("user", t.shape[0], t.shape[1])
+        if multi:
+            self._ck(self.L.smc_set_model_user3(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
+                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
+                                                int(bool(est_sigma)), float(sigma_fixed), float(rtol), float(atol),
+                                                B.USER_METHODS[method]), "smc_set_model_user3")
+        else:
+            self._ck(self.L.smc_set_model_user2(self.ctx, source.encode(), int(n_states), _dp(t), _dp(obs), _dp(cbuf), t.shape[0],
+                                                t.shape[1], cond.shape[1], int(bool(est_sigma)), float(sigma_fixed), float(rtol),
+                                                float(atol), B.USER_METHODS[method]), "smc_set_model_user")
+        self.model = ("user", t.shape[0], t.shape[1])      # the driver indexes this 3-tuple
+        self.user_n_obs = n_obs
 
     def set_model_methanation(self, cond, guess, obs, base_params, est_position, est_sigma=True, sigma_fixed=5.0,
                               tf=75.0, rtol=1e-6, atol=1e-6):
@@ -372,6 +395,23 @@ class HipEngine:
         nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
         self._ck(self.L.smc_mm_loglik_host(self.ctx, _dp(particle), n, _dp(lk), _dp(pred) if want_pred else None,
                                            ctypes.byref(nf), ctypes.byref(att)), "smc_mm_loglik_host")
+        return lk, pred, {"n_failed": nf.value, "rk_attempts": att.value}
+
+    def predict_user(self, particles):
+        """A user model's predictions for host particles (n, dim) (include/smc_hip.h: smc_user_predict): returns lk (n,),
+        pred (n, n_ex, n_t, n_obs) - the model's outputs at every finite data time, NaN past a row's end and from where a solve
+        failed - and {"n_failed", "rk_attempts"} of this call.  Leaves the particle sets and their lk untouched."""
+        if self.model is None or self.model[0] != "user":
+            raise SmcError("predict_user: no user model has been set")
+        particles = _f64(particles)
+        if particles.ndim != 2 or particles.shape[1] != self.dim:
+            raise ValueError(f"predict_user: particles must be (n, {self.dim}), got {particles.shape}")
+        n = particles.shape[0]
+        lk = np.empty(n)
+        pred = np.empty((n, self.model[1], self.model[2], self.user_n_obs))
+        nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._ck(self.L.smc_user_predict(self.ctx, _dp(particles), n, _dp(lk), _dp(pred), ctypes.byref(nf), ctypes.byref(att)),
+                 "smc_user_predict")
         return lk, pred, {"n_failed": nf.value, "rk_attempts": att.value}
 
     # ---- weights / ESS -------------------------------------------------------------------------

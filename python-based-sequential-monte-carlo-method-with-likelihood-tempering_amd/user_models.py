@@ -47,3 +47,65 @@ __device__ void smc_user_jac(double t, const double *y, const double *theta, con
     J[6] = 0.0; J[7] = 2.0 * k2 * y[1];              J[8] = 0.0;
 }
 """
+
+# several observed outputs (include/smc_hip.h: smc_set_model_user3, n_obs = 2): A -> B -> C as above with both A and B measured.
+# Closed form: A = A0 e^(-k1 t), B = A0 k1 / (k2 - k1) (e^(-k1 t) - e^(-k2 t)), C = A0 - A - B (the unobserved product)
+CONSECUTIVE_REACTIONS_AB = r"""
+__device__ void smc_user_y0(const double *theta, const double *cond, double *y) { y[0] = cond[0]; y[1] = 0.0; }
+__device__ void smc_user_rhs(double t, const double *y, const double *theta, const double *cond, double *dydt) {
+    dydt[0] = -theta[0] * y[0];
+    dydt[1] = theta[0] * y[0] - theta[1] * y[1];
+}
+__device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out) {
+    out[0] = y[0];
+    out[1] = y[1];
+}
+"""
+# ... and the unobserved product C = A0 - A - B as a third output, for predictions (give it an all-NaN column of obs)
+CONSECUTIVE_REACTIONS_ABC = CONSECUTIVE_REACTIONS_AB.replace("    out[1] = y[1];\n", "    out[1] = y[1];\n    out[2] = cond[0] - y[0] - y[1];\n")
+
+# Robertson's kinetics (ROBERTSON, method="BDF") with A and C measured: A falls from A0 while C stays below about 1e-2 A0 over
+# the data times - outputs orders of magnitude apart, what obs_scale is for
+ROBERTSON_AC = ROBERTSON.replace(
+    "__device__ double smc_user_obs(double t, const double *y, const double *theta, const double *cond) { return y[2]; }\n",
+    "__device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out) {\n"
+    "    out[0] = y[0];\n    out[1] = y[2];\n}\n")
+
+
+def obs_layout(t, obs, obs_scale=None):
+    """The data rules of smc_set_model_user3 (include/smc_hip.h), in NumPy: t (n_ex, n_t); obs (n_ex, n_t, n_obs) with NaN for a
+    value that was not measured; obs_scale (n_obs,) relative scales s_k > 0 (None: ones).  A row of t is a strictly increasing
+    run of finite times, possibly followed by NaN only.  Returns {"n_t_e": (n_ex,) int, "m_e": (n_ex,) finite observations at
+    the row's times, "sum_log_scale": (n_ex,) sum of log s_k over them}; raises ValueError for data the library refuses."""
+    import numpy as np
+    t = np.asarray(t, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    if t.ndim != 2 or obs.ndim != 3 or obs.shape[:2] != t.shape:
+        raise ValueError(f"obs_layout: t must be (n_ex, n_t) and obs (n_ex, n_t, n_obs), got {t.shape} and {obs.shape}")
+    n_ex, n_t, n_obs = obs.shape
+    if not 1 <= n_obs <= 8:
+        raise ValueError(f"obs_layout: n_obs = {n_obs} outside 1 .. 8 (SMC_USER_MAX_OBS)")
+    scale = np.ones(n_obs) if obs_scale is None else np.asarray(obs_scale, dtype=np.float64).reshape(-1)
+    if scale.shape != (n_obs,):
+        raise ValueError(f"obs_layout: obs_scale must have n_obs = {n_obs} entries, got {scale.shape}")
+    if not np.all(np.isfinite(scale) & (scale > 0)):
+        raise ValueError("obs_layout: obs_scale must be finite and > 0")
+    nan_t = np.isnan(t)
+    n_t_e = np.where(nan_t.any(axis=1), nan_t.argmax(axis=1), n_t)
+    for e in range(n_ex):
+        k = n_t_e[e]
+        if not nan_t[e, k:].all():
+            raise ValueError(f"obs_layout: row {e} of t has a NaN time before a number (only a trailing run of NaN may shorten a row)")
+        if k == 0:
+            raise ValueError(f"obs_layout: row {e} of t has no finite time")
+        if not np.all(np.isfinite(t[e, :k])):
+            raise ValueError(f"obs_layout: row {e} of t holds an infinite time")
+        if not np.all(np.diff(t[e, :k]) > 0):
+            raise ValueError(f"obs_layout: row {e} of t is not strictly increasing")
+    inside = np.arange(n_t)[None, :] < n_t_e[:, None]
+    o = np.where(inside[:, :, None], obs, np.nan)
+    if np.any(np.isinf(o)):
+        raise ValueError("obs_layout: obs holds an infinite value (NaN marks a value that was not measured)")
+    seen = ~np.isnan(o)
+    return {"n_t_e": n_t_e.astype(np.int64), "m_e": seen.sum(axis=(1, 2)).astype(np.int64),
+            "sum_log_scale": np.sum(np.where(seen, np.log(scale)[None, None, :], 0.0), axis=(1, 2))}
