@@ -1,26 +1,28 @@
-// user_bdf.h -- the second integrator of user models (SMC_USER_METHOD_BDF, include/smc_hip.h): run-time compiled source,
-// included by user_model.hip only.  It restates solve_ivp(method="BDF", t_eval = t, rtol, atol) per lane as SciPy 1.15 has
-// it (scipy/integrate/_ivp/bdf.py: the NDF coefficients, the difference array D with change_D / compute_R, solve_bdf_system,
-// the current_jac logic, the error-norm step control with the order change over k-1, k, k+1, BdfDenseOutput; common.py:
-// select_initial_step with order 1, num_jac) and defines the same smc_user_solve_kernel entry point over a UserOps-style
-// item, so that the scheduler (solve_sched.h), early rejection, user_finish_kernel and the cost-hint scan are the RK45 path's.
+// user_bdf_kernel.h -- the second integrator of user models (SMC_USER_METHOD_BDF, include/smc_hip.h).  Device code only: the
+// library appends this text to the user's source and hands the whole to hiprtc (user_model.hip: build_source).  It restates
+// solve_ivp(method="BDF", t_eval = t, rtol, atol) per lane as SciPy 1.15 has it (scipy/integrate/_ivp/bdf.py: the NDF
+// coefficients, the difference array D with change_D / compute_R, solve_bdf_system, the current_jac logic, the error-norm step
+// control with the order change over k-1, k, k+1, BdfDenseOutput; common.py: select_initial_step with order 1, num_jac) and
+// defines the same smc_user_solve_kernel entry point over a UserOps-style item, so that the scheduler (solve_sched.h), early
+// rejection, user_finish_kernel and the cost-hint scan are the RK45 path's.
 //
 // NumPy rounds every product and sum on its own: the integrator is compiled without contraction.  The small matrix products
 // (change_D, psi, the LU and its solves, the dense output) are plain sequential sums where SciPy calls BLAS / LAPACK, so
 // agreement with SciPy is at rounding level per step, not bitwise.  The user's functions are compiled once, with
 // smc_div(a, b) = a / b.
-#pragma once
-
-namespace smc {
-
-static const char *kUserBdfPrelude = R"SRC(
-#include "rk45_math.h"
-namespace smc_user_ieee {
-__device__ __forceinline__ double smc_div(double a, double b) { return a / b; }
-)SRC";
-
-static const char *kUserBdfKernelSource = R"SRC(
-// ---- appended by libsmc_hip.so after the user's source: method BDF ---------------------------------------------
+//
+// One text, three kernels, as user_rk45_kernel.h: the one-output kernel (SMC_USER_NOBS not defined), and with SMC_USER_NOBS
+// defined the sweep kernel and, appended a second time with SMC_USER_PRED 1 under the names below, the prediction kernel.
+// What differs is in the blocks marked "data side" and "prediction".  No #pragma once; SMC_USER_PRED and the names are
+// undefined again at the end.
+#ifndef SMC_USER_PRED
+#define SMC_USER_PRED 0
+#endif
+#if SMC_USER_PRED
+#define smc_user_bdf smc_user_bdf_pred
+#define UserBdfOps UserBdfOpsPred
+#define smc_user_solve_kernel smc_user_predict_kernel
+#endif
 #include "sweep_args.h"     // in-memory headers handed to hiprtc by the library: the argument blocks,
 #include "philox.h"         // the counter-based generator (the early-rejection bound re-derives the acceptance uniform),
 #include "solve_sched.h"    // the scheduler of the RK45 kernel
@@ -70,13 +72,34 @@ struct Item {
     double J[NS][NS], LU[NS][NS];  // Jacobian and the factors of I - c J (row-major, L unit lower, U upper)
     double jac_factor[NS];         // num_jac's per-column factor (no smc_user_jac)
     int piv[NS];
+#ifdef SMC_USER_NOBS
+    double *pred;   // prediction kernel: where the outputs of t_eval[i_out] go (UserBdfOps::set_pred); else nullptr
+#endif
     int order, n_equal_steps, i_out, status;   // status: 0 running, 1 finished, -1 TOO_SMALL_STEP
     bool fresh, in_step, current_jac, lu_valid;
     unsigned n_steps, n_newton, n_lu, n_jac;   // accepted steps, Newton iterations, LU factorisations, Jacobian evaluations
 };
 
-__device__ __forceinline__ void item_cache_times(Item &it, const double2 *tp, int n_t) {
-    it.t_bound = tp[n_t - 1].x;
+// ---- data side: one data time of an experiment, the end time of its row, and what an output adds to the item ----
+#ifdef SMC_USER_NOBS
+// several outputs: the records of user_obs_args.h; the row's own end time is kept in its last record
+using DataRec = smc_obs::Rec;
+__device__ __forceinline__ double t_bound_of(const DataRec *tp, int n_t) { return tp[n_t].y[0]; }
+__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, const double *obs) {
+    smc_obs::emit<SMC_USER_PRED, false>(it.sr2, it.pred, yy, theta, cond, t_out, obs);
+}
+#else
+// one output: n_t + 1 (time, observation) pairs, the last one the sentinel (+inf, 0), as in the RK45 kernel
+using DataRec = double2;
+__device__ __forceinline__ double t_bound_of(const DataRec *tp, int n_t) { return tp[n_t - 1].x; }
+__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {
+    const double r = obs - smc_user_ieee::smc_user_obs(t_out, yy, theta, cond);
+    it.sr2 += r * r;
+}
+#endif
+// ---- end of the data side ----
+__device__ __forceinline__ void item_cache_times(Item &it, const DataRec *tp, int n_t) {
+    it.t_bound = t_bound_of(tp, n_t);
     it.t_next = tp[it.i_out].x;
 }
 // what a lane sets up for an item that has not had an attempt yet (item_begin and the pool's unpack)
@@ -102,10 +125,6 @@ __device__ __forceinline__ void item_reset_lane(Item &it) {
     it.n_steps = it.n_newton = it.n_lu = it.n_jac = 0u;
 }
 
-__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {
-    const double r = obs - smc_user_ieee::smc_user_obs(t_out, yy, theta, cond);
-    it.sr2 += r * r;
-}
 
 __device__ __forceinline__ void rhs(double t, const double *y, const double *theta, const double *cond, double *f) {
     smc_user_ieee::smc_user_rhs(t, y, theta, cond, f);
@@ -342,10 +361,10 @@ __device__ __forceinline__ void solve_bdf_system(Item &it, const double *theta, 
     }
 }
 
-__device__ void item_begin(Item &it, const double *theta, const double *cond, const double2 *tp, int n_t, double rtol_in,
+__device__ void item_begin(Item &it, const double *theta, const double *cond, const DataRec *tp, int n_t, double rtol_in,
                            double atol) {
     const double rtol = (rtol_in < 100 * kEps) ? 100 * kEps : rtol_in;      // common.py validate_tol
-    const double t0 = tp[0].x, t_bound = tp[n_t - 1].x;
+    const double t0 = tp[0].x, t_bound = t_bound_of(tp, n_t);
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     item_reset_lane(it);
     it.t = t0;
@@ -389,7 +408,7 @@ __device__ void item_begin(Item &it, const double *theta, const double *cond, co
 
 // One pass of bdf.py _step_impl's `while not step_accepted` body; on acceptance also the rest of _step_impl (D update,
 // order change) and the t_eval outputs of the step through BdfDenseOutput (built after the step, as solve_ivp does).
-__device__ __forceinline__ void item_attempt(Item &it, const double *theta, const double *cond, const double2 *tp, double rtol_in,
+__device__ __forceinline__ void item_attempt(Item &it, const double *theta, const double *cond, const DataRec *tp, double rtol_in,
                                              double atol) {
     const double rtol = (rtol_in < 100 * kEps) ? 100 * kEps : rtol_in;
     const double newton_tol = py_max(10 * kEps / rtol, py_min(0.03, sqrt(rtol)));
@@ -571,7 +590,7 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         const int k = it.order;
         const double hd = it.h_abs;
         int i_out = it.i_out;
-        double2 nx = tp[i_out];
+        DataRec nx = tp[i_out];
         do {
             double p = 1.0, yy[NS];
 #pragma unroll
@@ -615,11 +634,11 @@ struct UserBdfOps {
     unsigned n_solo;
     int patience;
     long long n_pos;
-    const double2 *s_tp;
+    const smc_user_bdf::DataRec *s_tp;
     unsigned *counts;           // [k * n_ex * n + e * n + p], k: accepted steps, Newton iterations, LU factorisations, Jacobians
 
     __device__ __forceinline__ const double *cond(int e) const { return a.cond + (long long)e * a.n_cond; }
-    __device__ __forceinline__ const double2 *row(int e) const { return s_tp + e * (a.n_t + 1); }
+    __device__ __forceinline__ const smc_user_bdf::DataRec *row(int e) const { return s_tp + e * (a.n_t + 1); }
     __device__ __forceinline__ void publish(long long idx, double sum, int info) const {
         __hip_atomic_store(reinterpret_cast<unsigned long long *>(a.sum_r2) + idx, (unsigned long long)__double_as_longlong(sum),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -632,6 +651,29 @@ struct UserBdfOps {
         counts[2 * m + idx] = s.n_lu;
         counts[3 * m + idx] = s.n_jac;
     }
+    // ---- prediction: smc_user_predict_kernel (SMC_USER_PRED 1) writes the model's outputs to `pred`; an item's pointer to its
+    // next output follows from out_idx and i_out (no pool word).  A one-output item has no such pointer.
+    double *pred;               // UserObsArgs::pred; nullptr in every other kernel
+#ifdef SMC_USER_NOBS
+    __device__ __forceinline__ void set_pred(Item &it, int i) const {
+        it.s.pred = SMC_USER_PRED ? pred + (((it.out_idx - (long long)it.e * a.n) * a.n_ex + it.e) * a.n_t + i) * smc_obs::kObs : nullptr;
+    }
+    __device__ __forceinline__ void pred_from_lane(Item &u, const Item &it, int src) const {
+        u.s.pred = SMC_USER_PRED ? (double *)smc::lane_value_ll((long long)it.s.pred, src) : nullptr;
+    }
+    // NaN from the first output time not served on (past the row's end; from a failed solve's stop)
+    __device__ __forceinline__ void pred_tail(const Item &it) const {
+        if (SMC_USER_PRED) {
+            for (int i = it.s.i_out; i < a.n_t; ++i)
+                for (int k = 0; k < smc_obs::kObs; ++k) it.s.pred[(i - it.s.i_out) * smc_obs::kObs + k] = __longlong_as_double(0x7ff8000000000000LL);
+        }
+    }
+#else
+    __device__ __forceinline__ void set_pred(Item &, int) const {}
+    __device__ __forceinline__ void pred_from_lane(Item &, const Item &, int) const {}
+    __device__ __forceinline__ void pred_tail(const Item &) const {}
+#endif
+    // ---- end of prediction ----
     __device__ __forceinline__ void load_theta(Item &it, long long p) const {
 #pragma unroll
         for (int c = 0; c < SMC_USER_DIM; ++c) it.th[c] = a.theta[c * a.stride + p];
@@ -648,9 +690,11 @@ struct UserBdfOps {
             return smc::kStartDone;
         }
         load_theta(nb, p);
+        set_pred(nb, 0);
         smc_user_bdf::item_begin(nb.s, nb.th, cond(e), row(e), a.n_t, a.rtol, a.atol);
         if (nb.s.status == 0) return smc::kStartStarted;
         publish_counts(nb.out_idx, nb.s);
+        pred_tail(nb);
         publish(nb.out_idx, nb.s.sr2, nb.s.status < 0 ? (1 << 30) : 0);
         return smc::kStartDone;
     }
@@ -677,6 +721,7 @@ struct UserBdfOps {
         it.e = __double2loint(w4);
         it.attempts = (unsigned)__double2hiint(w4);
         it.out_idx = __double_as_longlong(slot[5 * 64]);
+        set_pred(it, it.s.i_out);
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             it.s.D[0][i] = slot[(6 + i) * 64];
@@ -698,6 +743,7 @@ struct UserBdfOps {
         return start(a.order ? (long long)a.order[pos] : pos, e, false, nb);
     }
     __device__ __forceinline__ void finish(Item &it, int st) const {
+        pred_tail(it);
         publish_counts(it.out_idx, it.s);
         publish(it.out_idx, it.s.sr2, (int)(it.attempts & 0x1fffffffu) | ((st < 0) ? (1 << 30) : 0));
     }
@@ -724,6 +770,7 @@ struct UserBdfOps {
         }
         u.s.order = __builtin_amdgcn_readlane(it.s.order, src);
         u.s.n_equal_steps = __builtin_amdgcn_readlane(it.s.n_equal_steps, src);
+        pred_from_lane(u, it, src);
         u.s.i_out = __builtin_amdgcn_readlane(it.s.i_out, src);
         u.s.status = __builtin_amdgcn_readlane(it.s.status, src);
         const int flags = (int)it.s.fresh | ((int)it.s.in_step << 1) | ((int)it.s.current_jac << 2) | ((int)it.s.lu_valid << 3);
@@ -750,7 +797,10 @@ struct UserBdfOps {
         const double sigma = a.est_sigma ? it.th[SMC_USER_DIM - 1] : a.sigma_fixed;
         if (!(sigma > 0.0)) return false;
         const double s2 = sigma * sigma;
-        const double c0 = (-0.5 * a.n_t) * log(2.0 * 3.141592653589793 * s2);
+        const double lg = log(2.0 * 3.141592653589793 * s2);
+#ifndef SMC_USER_NOBS   // data side: every experiment has n_t observations of scale 1
+        const double c0 = (-0.5 * a.n_t) * lg;
+#endif
         double lk2_bound = 0.0;
         for (int k = 0; k < a.n_ex; ++k) {
             double S = 0.0;
@@ -762,6 +812,9 @@ struct UserBdfOps {
                 if (v < 0.0) return true;
                 if (v == v) S = v;
             }
+#ifdef SMC_USER_NOBS    // data side: the experiment's own count and scales
+            const double c0 = (-0.5 * smc_obs::me(k)) * lg - smc_obs::sum_log_scale(k, a.n_ex);
+#endif
             lk2_bound += c0 - S / (2.0 * s2);
         }
         const smc::RejectArgs &r = *a.rej;
@@ -783,6 +836,16 @@ struct UserBdfOps {
 };
 
 // Outputs per item: the sum of squared residuals, attempts | cancelled << 29 | failed << 30, and the four work counters.
+// LDS per wave: a ring of 64 started items of UserBdfOps::kPoolWords words; then the data, read by every output
+#ifdef SMC_USER_NOBS   // data side: the image the host has built (user_obs_args.h)
+extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts, smc::UserObsArgs o) {
+    extern __shared__ double s_pool_all[];
+    double *s_pool = s_pool_all + (threadIdx.x >> 6) * (UserBdfOps::kPoolWords * 64);
+    static_assert(4 * UserBdfOps::kPoolWords * 64 == smc_obs::kHdrAt, "user_obs_args.h: the image follows the pools");
+    const smc_obs::Rec *s_tp = smc_obs::table(a.n_ex);
+    for (int i = threadIdx.x; i < o.img_len; i += blockDim.x) smc_obs::lds()[i] = o.img[i];
+    double *const pred = o.pred;
+#else                  // data side: the table of (time, observation) pairs, built here
 extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts) {
     extern __shared__ double s_pool_all[];
     double *s_pool = s_pool_all + (threadIdx.x >> 6) * (UserBdfOps::kPoolWords * 64);
@@ -792,14 +855,19 @@ extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::Use
         s_tp[i] = (k < a.n_t) ? make_double2(a.t[e * a.n_t + k], a.obs[e * a.n_t + k])
                               : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);
     }
+    double *const pred = nullptr;
+#endif
     __syncthreads();
     const unsigned n_list = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[0]) : 0u;
     unsigned n_solo = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[1]) : 0u;
     if (n_solo > a.solo_cap) n_solo = a.solo_cap;
     UserBdfOps ops{a, a.n, a.n_ex, a.stiff_list, n_list, a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, a.patience,
-                   a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : a.n, s_tp, counts};
+                   a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : a.n, s_tp, counts, pred};
     smc::solve_persistent(ops, a.queue, s_pool);
 }
-)SRC";
-
-}  // namespace smc
+#if SMC_USER_PRED
+#undef smc_user_bdf
+#undef UserBdfOps
+#undef smc_user_solve_kernel
+#endif
+#undef SMC_USER_PRED
