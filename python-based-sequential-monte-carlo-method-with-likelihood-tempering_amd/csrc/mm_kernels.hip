@@ -30,6 +30,7 @@
 
 #include <cstdlib>
 
+#include "mh_control.h"
 #include "mm_rk45.h"
 #include "solve_sched.h"
 #include "philox.h"
@@ -123,12 +124,13 @@ __device__ __forceinline__ unsigned mm_cost_bucket(double Vmax, double Km, bool 
     const int k = u < 0 ? 0 : (u > 123 ? 123 : u);
     return (unsigned)(123 - k);         // long solves first
 }
-// Table of the counting sort (ctx->d_order_hist, unsigned words):  counts[kCostBlocks][kCostBuckets] - zero between sweeps: the
-// offsets kernel clears what it has read - | offs[kCostBlocks][kCostBuckets] | totals[kCostBuckets] | n_ordered.
+// Table of the counting sort (ctx->d_order_hist, unsigned words):  counts[kCostBlocks][kCostBuckets] - zero between sweeps: whoever
+// turns them into offsets clears them - | offs[kCostBlocks][kCostBuckets] | totals[kCostBuckets] | n_ordered | arrival counter of
+// cost_scatter_kernel.  (offs and totals: only the user-model path, whose scatter kernel still follows cost_offsets_kernel.)
 // A slice is a whole number of 256-particle blocks, so that every block of the propose kernel belongs to exactly one slice and
 // can add its LDS histogram to that slice's row (round 4: the separate histogram launch is gone).
 constexpr int kCostCounts = 0, kCostOffs = kCostBlocks * kCostBuckets, kCostTotals = 2 * kCostBlocks * kCostBuckets,
-              kCostNOrdered = kCostTotals + kCostBuckets, kCostTableWords = kCostNOrdered + 64;
+              kCostNOrdered = kCostTotals + kCostBuckets, kCostArrive = kCostNOrdered + 1, kCostTableWords = kCostNOrdered + 64;
 __host__ __device__ __forceinline__ int64_t cost_slice_blocks(int64_t n) { return (((n + 255) / 256) + kCostBlocks - 1) / kCostBlocks; }
 __host__ __device__ __forceinline__ int64_t cost_slice_particles(int64_t n) { return cost_slice_blocks(n) * 256; }
 size_t cost_table_bytes() { return (size_t)kCostTableWords * sizeof(unsigned); }
@@ -183,12 +185,46 @@ __device__ __forceinline__ void cost_cursors(unsigned *__restrict__ table, unsig
 // ... and the proposals themselves (rows [c * stride + i]) into cost order, as 32-byte records (Vmax, Km, sigma, particle): one
 // scattered 32-byte write per proposal here instead of one scattered line read per value and experiment in the solve kernel
 // (whose counter traffic went from 339 to 832 MB per launch with the gathers, profiles/r03_ab_cost_order.log)
-__global__ void __launch_bounds__(256) cost_scatter_kernel(const uint8_t *__restrict__ bucket, int64_t n, unsigned *__restrict__ table,
+// One launch: every block first turns the histogram rows into the cursors of ITS slice by itself - per class, the members in
+// the slices below it and in all slices: 32 16-byte loads per thread out of a 128 KB table that sits in L2 (round 5 had a kernel of its
+// own, cost_offsets_kernel, do this between the propose kernel and this one) - and the last block to finish clears the rows for
+// the next sweep.  Integer sums: the order does not matter.
+__global__ void __launch_bounds__(256) cost_scatter_kernel(const uint8_t *__restrict__ bucket, int64_t n, unsigned *table,
                                                           const double *__restrict__ theta, int64_t stride,
                                                           SortedProposal *__restrict__ sorted, const MHControl *__restrict__ ctl) {
-    __shared__ unsigned cur[kCostBuckets], tot[kCostBuckets];
+    static_assert(kCostBlocks == 256 && kCostBuckets == 128, "32 threads x 4 classes, 8 groups of 32 slices");
+    __shared__ unsigned cur[kCostBuckets], tot[kCostBuckets], part[2][kCostBuckets];   // part: [below this slice | all slices]
+    __shared__ int s_last;
     if (ctl && ctl->stop) return;
-    cost_cursors(table, cur, tot);
+    if (threadIdx.x < 2 * kCostBuckets) (&part[0][0])[threadIdx.x] = 0u;
+    __syncthreads();
+    {   // thread -> four classes (one 16-byte load per row) of every eighth slice: 32 independent loads, all in flight at once
+        const int k4 = (threadIdx.x & 31) * 4, s0 = threadIdx.x >> 5;
+        unsigned below[4] = {0, 0, 0, 0}, total[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < kCostBlocks / 8; ++j) {
+            const int s = s0 + 8 * j;
+            const uint4 v = *reinterpret_cast<const uint4 *>(table + kCostCounts + s * kCostBuckets + k4);
+            const unsigned m = s < (int)blockIdx.x ? ~0u : 0u;
+            total[0] += v.x; total[1] += v.y; total[2] += v.z; total[3] += v.w;
+            below[0] += v.x & m; below[1] += v.y & m; below[2] += v.z & m; below[3] += v.w & m;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            atomicAdd(&part[0][k4 + q], below[q]);
+            atomicAdd(&part[1][k4 + q], total[q]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < kCostBuckets) tot[threadIdx.x] = part[1][threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x < kCostBuckets) {
+        unsigned base = 0;
+        for (int q = 0; q < (int)threadIdx.x; ++q) base += tot[q];
+        cur[threadIdx.x] = part[0][threadIdx.x] + base;
+        if (blockIdx.x == 0 && threadIdx.x == kCostBuckets - 1) table[kCostNOrdered] = base;   // positions the solve kernel hands out
+    }
+    __syncthreads();
     const int64_t per = cost_slice_particles(n), lo = per * blockIdx.x, hi = (lo + per < n) ? lo + per : n;
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         SortedProposal r;
@@ -198,6 +234,12 @@ __global__ void __launch_bounds__(256) cost_scatter_kernel(const uint8_t *__rest
         r.particle = i;
         sorted[atomicAdd(&cur[bucket[i]], 1u)] = r;
     }
+    // every block has read the rows before it counts itself in; the last one clears them (nobody waits)
+    if (threadIdx.x == 0) s_last = atomicAdd(&table[kCostArrive], 1u) == gridDim.x - 1;
+    __syncthreads();
+    if (!s_last) return;
+    for (int i = threadIdx.x; i < kCostBlocks * kCostBuckets; i += blockDim.x) table[kCostCounts + i] = 0u;
+    if (threadIdx.x == 0) table[kCostArrive] = 0u;
 }
 
 // ... or, for a model the library knows nothing about (user_model.hip: the class bytes come from the model's cost hint), just the
@@ -323,7 +365,7 @@ mm_propose_kernel(Prior prior, MHParams mh, const double *__restrict__ filt, int
         }
     }
     // cost-ordered sweep: the class histogram of this block's 256 proposals, added to the row of the slice the block belongs to
-    // (the counting sort's first pass; its table is zero on entry, see cost_offsets_kernel)
+    // (the counting sort's first pass; its table is zero on entry, see cost_scatter_kernel)
     __shared__ unsigned s_hist[kCostBuckets];
     if (mh.cost_bucket) {
         if (threadIdx.x < kCostBuckets) s_hist[threadIdx.x] = 0u;
@@ -665,19 +707,68 @@ SMC_SOLVE_DEFAULT_MODE(false, true)
 // ---------------------------------------------------------------------------------------------
 // finish: logL from the per-experiment sums, then store or accept/select
 // ---------------------------------------------------------------------------------------------
-template <int MODE /*0 = likelihood only, 1 = MH accept/select*/>
+// a word of a per-block row, written through to device scope for the last block of the same kernel (see mm_finish_kernel's tail)
+__device__ __forceinline__ void row_store(unsigned long long *p, unsigned long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void row_store(double *p, double v) {
+    row_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v));
+}
+
+// Everything the accept step of ONE particle reads, loaded before the first value is used: one round trip to memory per particle
+// instead of four dependent ones (sigma, then the sums, then lk1, then the points).  Two particles in flight at a time measured
+// the same (44.4 us per launch at 10^6 particles either way, profiles/r06_ab_stream_overhead.log) at twice the registers.
+// NEX > 0: n_ex known at compile time (the sums and info words live in registers); NEX == 0: any n_ex, read where they are used.
+template <int MODE, int NEX>
+struct FinishLoad {
+    double sigma, lk1, rr, pratio;
+    double th[3], f[3];
+    double sum[NEX > 0 ? NEX : 1];
+    int fl[NEX > 0 ? NEX : 1];
+    uint8_t p0, ever;
+};
+template <int MODE, int NEX>
+__device__ __forceinline__ FinishLoad<MODE, NEX> finish_load(const MMModel &mm, const MHParams &mh, const double *__restrict__ theta,
+                                                              int64_t stride, int64_t n, const double *__restrict__ sum_r2,
+                                                              const int *__restrict__ info, const uint8_t *__restrict__ p0_in,
+                                                              const double *lk_io, const double *filt, int64_t fstride,
+                                                              const uint8_t *r_ac, int64_t p) {
+    FinishLoad<MODE, NEX> L;
+    L.sigma = mm.est_sigma ? theta[2 * stride + p] : mm.sigma_fixed;
+#pragma unroll
+    for (int k = 0; k < NEX; ++k) {
+        L.sum[k] = sum_r2[(int64_t)k * n + p];
+        L.fl[k] = info[(int64_t)k * n + p];
+    }
+    if (MODE == 1) {
+        L.p0 = p0_in[p];
+        L.lk1 = lk_io[p];
+        L.rr = mh.device_rng ? 0.0 : mh.rr[p];
+        L.pratio = (mh.prior_mode != SMC_PRIOR_MODE_MASK) ? mh.pratio[p] : 1.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            L.th[c] = theta[c * stride + p];
+            L.f[c] = filt[c * fstride + p];
+        }
+        L.ever = r_ac[p];
+    }
+    return L;
+}
+
+template <int MODE /*0 = likelihood only, 1 = MH accept/select*/, int NEX /*n_ex, or 0 = read it from the model*/>
 __global__ void __launch_bounds__(256)
 mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* evaluated point (proposal) */,
                  int64_t stride, int64_t n, const double *__restrict__ sum_r2, const int *__restrict__ info,
                  const uint8_t *__restrict__ p0_in, double *lk_io, double *filt, int64_t fstride,
-                 uint8_t *__restrict__ r_ac, SweepCounters *__restrict__ counters, double *__restrict__ dbg_lk2,
-                 uint8_t *__restrict__ dbg_r) {
-    __shared__ unsigned long long s_cnt[4][4];
+                 uint8_t *r_ac, SweepCounters *__restrict__ counters, double *__restrict__ dbg_lk2,
+                 uint8_t *__restrict__ dbg_r, FinishTail tail) {
+    __shared__ unsigned long long s_cnt[4][5];
     __shared__ double s_mom[4][9];
+    __shared__ int s_last;
     if (MODE == 1 && mh.ctl && mh.ctl->stop) return;   // after the loop's `break`: p_filt, lk1, r_ac and the counters stay as they are
     unsigned long long attempts = 0, failed = 0, acc_now = 0, acc_ever = 0, long_items = 0;
     // (items whose solve ran to t_bound and produced its n_t dense outputs - bench.py's roofline numerator - are counted in a
-    // 32-bit register and ride in the HIGH half of `failed` through the block reduction: the kernel's time is its per-block tail)
+    // 32-bit register and ride in the HIGH half of `failed` through the block reduction)
     unsigned solved = 0;
     // moments of the SELECTED particles about mh.moment_shift (MODE 1, fused iteration): sum y, sum y y^T (upper), y = x - shift
     double m0 = 0, m1 = 0, m2 = 0, c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
@@ -688,15 +779,14 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         sh1 = mh.moment_shift[1];
         sh2 = mh.moment_shift[2];
     }
-    // grid-stride: a few hundred blocks, so that the counters cost one atomic per block, not per wave
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        const int n_ex = mm.n_ex;
-        const double sigma = mm.est_sigma ? theta[2 * stride + p] : mm.sigma_fixed;
-        const bool masked = (MODE == 1) && (p0_in[p] == 0);
+    const int n_ex = NEX > 0 ? NEX : mm.n_ex;
+    auto accept_one = [&](const FinishLoad<MODE, NEX> &L, int64_t p) {
+        const double sigma = L.sigma;
+        const bool masked = (MODE == 1) && (L.p0 == 0);
         bool cancelled = false;   // a solve of this proposal stopped because its rejection was certain (mm_certainly_rejected)
         double lk2;
         if (masked) {
-            lk2 = lk_io[p];  // proposal was reset to the current point: the likelihood is the stored one
+            lk2 = L.lk1;     // proposal was reset to the current point: the likelihood is the stored one
         } else if (sigma <= 0.0) {
             lk2 = -__longlong_as_double(0x7ff0000000000000LL);  // Micmem_likelihood.py:53-54
         } else {
@@ -704,9 +794,10 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
             const double c0 = (-0.5 * mm.n_t) * log(2.0 * 3.141592653589793 * s2);  // :70
             lk2 = 0.0;
             unsigned pf = 0;
+#pragma unroll
             for (int k = 0; k < n_ex; ++k) {
-                lk2 += mm_loglik_term(c0, sum_r2[(int64_t)k * n + p], s2);          // :70-73
-                const int fl = info[(int64_t)k * n + p];
+                lk2 += mm_loglik_term(c0, NEX > 0 ? L.sum[NEX > 0 ? k : 0] : sum_r2[(int64_t)k * n + p], s2);          // :70-73
+                const int fl = NEX > 0 ? L.fl[NEX > 0 ? k : 0] : info[(int64_t)k * n + p];
                 attempts += (unsigned)(fl & kInfoAttemptsMask);
                 long_items += (unsigned)(fl & kInfoAttemptsMask) > (unsigned)kLongItemAttempts;
                 pf |= (unsigned)(fl >> 30) & 1u;
@@ -721,7 +812,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
             lk_io[p] = lk2;
         } else {
             // ---- accept / select (:231-241) ----
-            const double lk1 = lk_io[p];
+            const double lk1 = L.lk1;
             if (cancelled) lk2 = lk1;   // rejected for certain: its logL was never completed and is not needed (r = 0 below)
             const double p0 = masked ? 0.0 : 1.0;
             double rr;
@@ -730,18 +821,18 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                                               SMC_PHILOX_BLOCK_UNIFORM);
                 rr = u01_from(ru.x, ru.y);
             } else {
-                rr = mh.rr[p];
+                rr = L.rr;
             }
             const double px = lk2 - lk1;
             double pp = exp(px * mh.gamma);
-            if (mh.prior_mode != SMC_PRIOR_MODE_MASK) pp = pp * mh.pratio[p];
+            if (mh.prior_mode != SMC_PRIOR_MODE_MASK) pp = pp * L.pratio;
             if (mh.prior_mode != SMC_PRIOR_MODE_RATIO) pp = pp * p0;
             const double r = (!cancelled && pp >= rr) ? 1.0 : 0.0;
             const double nr = 1.0 - r;
             double sel[3];
+#pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const double th = theta[c * stride + p], f = filt[c * fstride + p];
-                sel[c] = __dadd_rn(__dmul_rn(th, r), __dmul_rn(f, nr));
+                sel[c] = __dadd_rn(__dmul_rn(L.th[c], r), __dmul_rn(L.f[c], nr));
                 filt[c * fstride + p] = sel[c];
             }
             if (acc_mom) {
@@ -750,7 +841,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                 c00 += y0 * y0; c01 += y0 * y1; c02 += y0 * y2; c11 += y1 * y1; c12 += y1 * y2; c22 += y2 * y2;
             }
             lk_io[p] = __dadd_rn(__dmul_rn(lk2, r), __dmul_rn(lk1, nr));
-            const uint8_t ever = (uint8_t)(r_ac[p] | (uint8_t)(r != 0.0));
+            const uint8_t ever = (uint8_t)(L.ever | (uint8_t)(r != 0.0));
             r_ac[p] = ever;
             acc_now += (r != 0.0);
             acc_ever += ever;
@@ -759,16 +850,18 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                 dbg_r[p] = (uint8_t)(r != 0.0);
             }
         }
-    }
+    };
+    // grid-stride, a thread's particles in ascending order (the order of its moment sums)
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x)
+        accept_one(finish_load<MODE, NEX>(mm, mh, theta, stride, n, sum_r2, info, p0_in, lk_io, filt, fstride, r_ac, p), p);
     failed += (unsigned long long)solved << 32;
-    // integer reductions (order-independent): wave shuffles, LDS across the 4 waves, one atomic per block
-    for (int off = 32; off > 0; off >>= 1) long_items += __shfl_down(long_items, off);
-    if ((threadIdx.x & 63) == 0 && long_items) atomicAdd(&counters->long_items, long_items);
+    // integer reductions (order-independent): wave shuffles, LDS across the 4 waves, one row of counts per block
     for (int off = 32; off > 0; off >>= 1) {
         attempts += __shfl_down(attempts, off);
         failed += __shfl_down(failed, off);
         acc_now += __shfl_down(acc_now, off);
         acc_ever += __shfl_down(acc_ever, off);
+        long_items += __shfl_down(long_items, off);
     }
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -776,6 +869,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         s_cnt[w][1] = failed;
         s_cnt[w][2] = acc_now;
         s_cnt[w][3] = acc_ever;
+        s_cnt[w][4] = long_items;
     }
     if (acc_mom) {   // fixed-order block sums -> one row of 9 per block (deterministic; reduced by moments_reduce_kernel)
         double mv[9] = {m0, m1, m2, c00, c01, c02, c11, c12, c22};
@@ -787,40 +881,108 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         }
     }
     __syncthreads();
+    // The counts of the block go into a row of its own, like its moments (round 5: up to nine atomics per block on six words of
+    // one cache line).  The LAST block to arrive adds the rows up - integers, any order - and, in a batch on one rank, takes the
+    // loop's decision (mh_control.h).  Nobody waits: a block counts itself in and leaves.
+    // Both rows are written through to device scope (relaxed agent-scope stores, as publish_item does) and the block waits for
+    // them to be acknowledged before it counts itself in.  A release fence instead would write the whole L2 back - the 33 MB
+    // of points and likelihoods this kernel has just stored - once per block: measured, it doubles the kernel's time.
     if (acc_mom && threadIdx.x < 9)
-        mh.moment_rows[(size_t)blockIdx.x * 9 + threadIdx.x] =
-            ((s_mom[0][threadIdx.x] + s_mom[1][threadIdx.x]) + s_mom[2][threadIdx.x]) + s_mom[3][threadIdx.x];
-    if (threadIdx.x < 4) {
-        unsigned long long v = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+        row_store(mh.moment_rows + (size_t)blockIdx.x * 9 + threadIdx.x,
+                  ((s_mom[0][threadIdx.x] + s_mom[1][threadIdx.x]) + s_mom[2][threadIdx.x]) + s_mom[3][threadIdx.x]);
+    if (threadIdx.x < 5) {
+        const unsigned long long v = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+        unsigned long long *row = tail.count_rows + (size_t)blockIdx.x * kFinishCountWords;
         if (threadIdx.x == 1) {      // low half: failed solves; high half: solves that produced their outputs
-            if (v >> 32) atomicAdd(&counters->solved_items, v >> 32);
-            v &= 0xffffffffULL;
+            row_store(row + 1, v & 0xffffffffULL);
+            row_store(row + 5, v >> 32);
+        } else {
+            row_store(row + threadIdx.x, v);
         }
-        unsigned long long *dst = threadIdx.x == 0 ? &counters->rk_attempts
-                                  : threadIdx.x == 1 ? &counters->n_failed
-                                  : threadIdx.x == 2 ? &counters->accepted_now : &counters->accepted_ever;
-        if (v) atomicAdd(dst, v);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(tail.arrive, 1u) == gridDim.x - 1;
+    __syncthreads();
+    if (!s_last) return;
+    {
+        unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
+        for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) tot[q] += ctl_load<true>(tail.count_rows + (size_t)b * kFinishCountWords + q);
+        __shared__ unsigned long long s_tot[4][6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            for (int off = 32; off > 0; off >>= 1) tot[q] += __shfl_down(tot[q], off);
+            if ((threadIdx.x & 63) == 0) s_tot[w][q] = tot[q];
+        }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            const unsigned long long v = s_tot[0][threadIdx.x] + s_tot[1][threadIdx.x] + s_tot[2][threadIdx.x] + s_tot[3][threadIdx.x];
+            unsigned long long *dst = threadIdx.x == 0 ? &counters->rk_attempts
+                                      : threadIdx.x == 1 ? &counters->n_failed
+                                      : threadIdx.x == 2 ? &counters->accepted_now
+                                      : threadIdx.x == 3 ? &counters->accepted_ever
+                                      : threadIdx.x == 4 ? &counters->long_items : &counters->solved_items;
+            // (with its result: the addition has happened before the control step below reads the counters)
+            if (v) s_tot[0][threadIdx.x] = atomicAdd(dst, v);
+        }
+        if (threadIdx.x == 0) __hip_atomic_store(tail.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (MODE == 1 && tail.fuse_control) {
+        __syncthreads();
+        __shared__ double s_wpart[4][9];
+        mh_control_body<3, true>(tail.ctl, tail.wcov, s_wpart);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-// Blocks of the accept kernel: grid-stride, so that counters and moment rows cost one atomic / one row per block.  More blocks
-// do NOT help (A/B on one box, whole run of 10^6 particles, profiles/r04_ab_finish_grid.log: 1024 -> 74.6 ms, 2048 -> 75.1,
-// 4096 -> 76.3): the kernel's time goes into the per-block tail - nine 6-step wave reductions of the moments and the counters -
-// not into its 170 B per particle.
+// Blocks of the accept kernel: grid-stride, one row of counts and one row of moments per block.  The cap is a constant, not
+// derived from the device: the moment rows and the order in which they are added feed the next proposal covariance, so the
+// block-to-particle mapping is part of the result.
 #ifndef SMC_FINISH_GRID_CAP
 #define SMC_FINISH_GRID_CAP 1024
 #endif
 static unsigned finish_grid(int64_t n) {
-    static const int64_t cap = [] {
-        const char *e = getenv("SMC_FINISH_GRID_CAP");     // A/B knob
-        const int64_t v = e ? atoll(e) : 0;
-        return (v >= 1 && v <= 8192) ? v : (int64_t)SMC_FINISH_GRID_CAP;
-    }();
-    const int64_t g = (n + 255) / 256;
+    const int64_t g = (n + 255) / 256, cap = SMC_FINISH_GRID_CAP;
     return (unsigned)(g < cap ? (g < 1 ? 1 : g) : cap);
+}
+// ctx->d_finish_rows: the count rows of the accept kernel's blocks, then its arrival counter (zero between kernels)
+size_t finish_rows_bytes() { return ((size_t)SMC_FINISH_GRID_CAP * kFinishCountWords + 8) * sizeof(unsigned long long); }
+
+// accept kernel (MODE 0: likelihood only): n_ex of the data set as a template argument up to 8, any other through NEX = 0.
+// ctl_after: batch of iterations on one rank - the control step that follows this sweep, run by the kernel's last block.
+template <int MODE>
+static void launch_finish(smc_ctx *ctx, const MHParams &mh, const double *theta, int64_t stride, int64_t n, const uint8_t *p0,
+                          double *lk, double *filt, int64_t fstride, uint8_t *r_ac, double *dbg_lk2, uint8_t *dbg_r,
+                          const MHControlArgs *ctl_after, const double *w_cov) {
+    FinishTail tail{};
+    tail.count_rows = ctx->d_finish_rows;
+    tail.arrive = reinterpret_cast<unsigned *>(ctx->d_finish_rows + (size_t)SMC_FINISH_GRID_CAP * kFinishCountWords);
+    const unsigned grid = finish_grid(n);
+    if (ctl_after) {
+        tail.fuse_control = 1;
+        tail.ctl = *ctl_after;
+        tail.ctl.rows = mh.moment_rows;
+        tail.ctl.n_rows = (int)grid;
+        for (int i = 0; i < ctx->dim * ctx->dim; ++i) tail.wcov.w[i] = w_cov[i];
+    }
+#define SMC_FIN(NEX) hipLaunchKernelGGL((mm_finish_kernel<MODE, NEX>), dim3(grid), dim3(256), 0, ctx->stream, ctx->mm, mh, theta, stride, n, \
+                                        ctx->d_sum_r2, ctx->d_info, p0, lk, filt, fstride, r_ac, ctx->d_counters, dbg_lk2, dbg_r, tail)
+    switch (ctx->mm.n_ex) {
+        case 1: SMC_FIN(1); break;
+        case 2: SMC_FIN(2); break;
+        case 3: SMC_FIN(3); break;
+        case 4: SMC_FIN(4); break;
+        case 5: SMC_FIN(5); break;
+        case 6: SMC_FIN(6); break;
+        case 7: SMC_FIN(7); break;
+        case 8: SMC_FIN(8); break;
+        default: SMC_FIN(0); break;
+    }
+#undef SMC_FIN
 }
 
 // dynamic LDS of the solve kernel: the (time, observation) table, S0, and the four waves' pools of started items
@@ -928,12 +1090,10 @@ void launch_mm_loglik(smc_ctx *ctx, const double *theta, int64_t stride, int64_t
     launch_solve(ctx, theta, stride, n, nullptr, pred, sl, false, false, dbg_order ? ctx->order_debug_patience : 0,
                  dbg_order ? ctx->d_order : nullptr);
     MHParams mh{};
-    hipLaunchKernelGGL((mm_finish_kernel<0>), dim3(finish_grid(n)), dim3(256), 0, ctx->stream, ctx->mm, mh,
-                       theta, stride, n, ctx->d_sum_r2, ctx->d_info, nullptr, lk, nullptr, 0, nullptr, ctx->d_counters,
-                       nullptr, nullptr);
+    launch_finish<0>(ctx, mh, theta, stride, n, nullptr, lk, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in) {
+void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in, const MHControlArgs *ctl_after, const double *w_cov) {
     if (n <= 0) return;
     ParticleSet &F = ctx->set[SMC_SET_FILT];
     ParticleSet &P = ctx->set[SMC_SET_PRED];  // receives the proposals, as the reference's p_pred does (:220,228)
@@ -961,7 +1121,6 @@ void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in) {
     hipLaunchKernelGGL(mm_propose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->prior, mh,
                        F.theta, F.stride, n, P.theta, P.stride, ctx->d_p0);
     if (cost_order) {
-        hipLaunchKernelGGL(cost_offsets_kernel, dim3(kCostBuckets), dim3(kCostBlocks), 0, ctx->stream, ctx->d_order_hist, mh.ctl);
         hipLaunchKernelGGL(cost_scatter_kernel, dim3(kCostBlocks), dim3(256), 0, ctx->stream, ctx->d_bucket, n, ctx->d_order_hist, P.theta, P.stride,
                            static_cast<SortedProposal *>(ctx->d_sorted), mh.ctl);
     }
@@ -970,9 +1129,8 @@ void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in) {
                  ctx->order_debug ? ctx->d_order : nullptr, cost_order, mh.ctl);
     ctx->pending_sweep_items = n * ctx->mm.n_ex;
     ctx->moment_rows_n = mh.moment_rows ? (int)finish_grid(n) : 0;
-    hipLaunchKernelGGL((mm_finish_kernel<1>), dim3(finish_grid(n)), dim3(256), 0, ctx->stream, ctx->mm, mh,
-                       P.theta, P.stride, n, ctx->d_sum_r2, ctx->d_info, ctx->d_p0, F.lk, F.theta, F.stride, ctx->r_ac,
-                       ctx->d_counters, dbg ? ctx->dbg_lk2 : nullptr, dbg ? ctx->dbg_r : nullptr);
+    launch_finish<1>(ctx, mh, P.theta, P.stride, n, ctx->d_p0, F.lk, F.theta, F.stride, ctx->r_ac, dbg ? ctx->dbg_lk2 : nullptr,
+                     dbg ? ctx->dbg_r : nullptr, ctl_after, w_cov);
 }
 
 int query_solve_blocks_per_cu(bool fast) {

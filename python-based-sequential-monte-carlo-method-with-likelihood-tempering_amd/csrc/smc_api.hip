@@ -206,6 +206,8 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
     CK(hipMemsetAsync(c->r_ac, 0, (size_t)n_local, c->stream));
     CK(hipMalloc(&c->d_counters, sizeof(SweepCounters)));
     CK(hipMalloc(&c->d_queue, 2 * sizeof(unsigned long long)));
+    CK(hipMalloc(&c->d_finish_rows, finish_rows_bytes()));
+    CK(hipMemsetAsync(c->d_finish_rows, 0, finish_rows_bytes(), c->stream));   // the arrival counter is zero between kernels
     CK(hipMalloc(&c->d_reject, sizeof(RejectArgs)));
     CK(hipMalloc(&c->d_stiff_count, 4 * sizeof(unsigned)));
     CK(hipMemsetAsync(c->d_stiff_count, 0, 4 * sizeof(unsigned), c->stream));
@@ -229,18 +231,21 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
     c->partials_cap = 2048 * 64;
     CK(hipMalloc(&c->d_partials, (size_t)c->partials_cap * sizeof(double)));
     CK(hipMalloc(&c->d_small, 4096 * sizeof(double)));
-    CK(hipMalloc(&c->d_fused, 256 * sizeof(double)));
-    CK(hipMemsetAsync(c->d_fused, 0, 256 * sizeof(double), c->stream));
-    CK(hipHostMalloc(&c->h_fused, 256 * sizeof(double)));
+    {   // loop control, the fused iteration's words and the batch log: ONE block, so that a batch ends with one copy to the host
+        BatchBlock *db = nullptr, *hb = nullptr;
+        CK(hipMalloc(&db, sizeof(BatchBlock)));
+        c->d_batch = db;
+        CK(hipMemsetAsync(db, 0, sizeof(BatchBlock), c->stream));
+        CK(hipHostMalloc(&hb, sizeof(BatchBlock)));
+        c->h_batch = hb;
+        memset(hb, 0, sizeof(BatchBlock));
+        c->d_fused = db->fused;  c->h_fused = hb->fused;
+        c->d_mhctl = &db->ctl;   c->h_mhctl = &hb->ctl;
+        c->d_mhlog = db->log;    c->h_mhlog = hb->log;
+    }
     CK(hipMalloc(&c->d_ess, 128 * sizeof(double)));          // the fused ESS search's own words (max(lk) + 2 x 32 sums)
     CK(hipMemsetAsync(c->d_ess, 0, 128 * sizeof(double), c->stream));
     CK(hipHostMalloc(&c->h_ess, 128 * sizeof(double)));
-    CK(hipMalloc(&c->d_mhctl, sizeof(MHControl)));            // device-side loop control of a batch of Metropolis iterations
-    CK(hipMemsetAsync(c->d_mhctl, 0, sizeof(MHControl), c->stream));
-    CK(hipMalloc(&c->d_mhlog, (kMHBatchMax + 1) * sizeof(MHLogEntry)));
-    CK(hipMemsetAsync(c->d_mhlog, 0, (kMHBatchMax + 1) * sizeof(MHLogEntry), c->stream));
-    CK(hipHostMalloc(&c->h_mhlog, (kMHBatchMax + 1) * sizeof(MHLogEntry)));
-    CK(hipHostMalloc(&c->h_mhctl, sizeof(MHControl)));
     CK(hipHostMalloc(&c->h_small, 4096 * sizeof(double)));
     c->n_tiles = (n_local + kScanTile - 1) / kScanTile;
     CK(hipMalloc(&c->d_oscan, (size_t)n_local * sizeof(int32_t)));
@@ -282,14 +287,10 @@ void smc_destroy(smc_ctx *c) {
     (void)hipFree(c->d_stage);
     (void)hipFree(c->d_partials);
     (void)hipFree(c->d_small);
-    (void)hipFree(c->d_fused);
-    if (c->h_fused) (void)hipHostFree(c->h_fused);
+    (void)hipFree(c->d_batch);     // d_fused, d_mhctl and d_mhlog point into it
+    if (c->h_batch) (void)hipHostFree(c->h_batch);
     (void)hipFree(c->d_ess);
     if (c->h_ess) (void)hipHostFree(c->h_ess);
-    (void)hipFree(c->d_mhctl);
-    (void)hipFree(c->d_mhlog);
-    if (c->h_mhlog) (void)hipHostFree(c->h_mhlog);
-    if (c->h_mhctl) (void)hipHostFree(c->h_mhctl);
     if (c->h_small) (void)hipHostFree(c->h_small);
     (void)hipFree(c->d_oscan);
     (void)hipFree(c->d_blk_r);
@@ -309,6 +310,7 @@ void smc_destroy(smc_ctx *c) {
     (void)hipFree(c->d_mn_thr);
     (void)hipFree(c->d_mn_blk);
     (void)hipFree(c->d_queue);
+    (void)hipFree(c->d_finish_rows);
     (void)hipFree(c->d_reject);
     (void)hipFree(c->d_stiff_count);
     (void)hipFree(c->d_order);
@@ -1468,9 +1470,9 @@ int smc_mh_iteration_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, c
 // halve mhstep_ratio when r_ac.sum() < r_threshold_min * N, and form the next iteration's cov_m and factor; every kernel of an
 // iteration after the break returns at once (ctl->stop).  With RCCL the counts this kernel reads were all-reduced on the
 // stream just before it, so every rank takes the same decision and the enqueued collectives stay matched.  Stream order per
-// iteration (one rank):  control -> propose -> [cost_hist, cost_offsets, cost_scatter] -> solve -> accept  - the row reduction
-// of the moments and the factor live in the control kernel; several ranks:  ... -> accept -> moments_reduce -> ncclAllReduce
-// -> control.  What the host decides once per batch instead of once per sweep: in phase / cost order (from the last sweep
+// iteration (one rank, Michaelis-Menten):  propose -> [cost_scatter] -> solve -> accept  - the control step (row reduction of the
+// moments, decision, next factor: mh_control.h) runs in the last block of the accept kernel to finish; other models:  control
+// -> propose -> ... -> accept; several ranks:  ... -> accept -> moments_reduce -> ncclAllReduce -> control.  What the host decides once per batch instead of once per sweep: in phase / cost order (from the last sweep
 // before the batch); neither can change a result.
 int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, const double *w_cov, uint64_t seed, uint64_t stream0,
                              int n_iter, double thr_stop, double thr_halve, int64_t global_offset, int *n_done, int *stopped,
@@ -1488,6 +1490,9 @@ int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, cons
     const int d = c->dim, npair = d * (d + 1) / 2;
     const int nv = mm ? d + npair : 0;         // carried moments in front of the counts (Michaelis-Menten accept kernel only)
     const bool one_rank = !can_reduce(c);      // a one-rank RCCL communicator (tests) takes the several-ranks path as well
+    // Michaelis-Menten on one rank: nothing lies between an accept kernel and the control step that follows it, so the last
+    // block of the accept kernel to finish takes the decision and forms the next factor (mm_kernels.hip: mm_finish_kernel)
+    const bool fuse_ctl = mm && one_rank && d == 3;
     double *S = c->d_fused;
     // where an iteration's [moments | accepted_now, accepted_ever, n_failed] vector lives: Michaelis-Menten S + kV (carried
     // moments); the other models right behind the centred sums of the two-pass covariance, so that ONE all-reduce takes both
@@ -1556,12 +1561,20 @@ int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, cons
             mh.zero_queue = c->d_queue;
             mh.moment_shift = S + kShift;
             mh.moment_rows = c->d_partials;
-            launch_mm_mh(c, c->n_local, mh);
+            if (fuse_ctl) {    // the control step that follows this iteration rides in its accept kernel
+                a.counts_local = 0;
+                a.mom = S + kV;
+                a.sums = nullptr;
+                a.mode = kCtlDecide | (i + 1 < n_iter ? kCtlTransform : 0);
+                a.iteration = i + 1;
+            }
+            launch_mm_mh(c, c->n_local, mh, fuse_ctl ? &a : nullptr, w_cov);
         } else {
             launch_meth_mh(c, c->n_local, mh);
         }
         if (hipGetLastError() != hipSuccess) { fail(c, "smc_mh_sweeps_device_rng: a kernel launch of the batch failed"); return bail(); }
         if (c->launch_failed) { c->launch_failed = false; return bail(); }
+        if (fuse_ctl) continue;
         const bool transform_next = i + 1 < n_iter;
         ScopedTimer tm(c, SMC_T_MOMENTS);
         if (mm) {
@@ -1595,9 +1608,9 @@ int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, cons
         launch_mh_control(c, a, w_cov);
     }
     if (hipGetLastError() != hipSuccess) { fail(c, "smc_mh_sweeps_device_rng: a kernel launch of the batch failed"); return bail(); }
-    HIPC(c, hipMemcpyAsync(c->h_mhlog, c->d_mhlog, (size_t)(n_iter + 1) * sizeof(MHLogEntry), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(c->h_mhctl, c->d_mhctl, sizeof(MHControl), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(c->h_fused, S, (size_t)kFusedWords * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    // control block, fused words and the log entries of this batch: one copy (BatchBlock, smc_internal.h)
+    HIPC(c, hipMemcpyAsync(c->h_batch, c->d_batch, offsetof(BatchBlock, log) + (size_t)(n_iter + 1) * sizeof(MHLogEntry),
+                           hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));          // the one synchronisation of the batch
     const int done = c->h_mhctl->n_done;
     if (done < 1 || done > n_iter) return fail(c, "smc_mh_sweeps_device_rng: the device reports an impossible iteration count");

@@ -98,6 +98,13 @@ struct MHLogEntry {             // what the driver's Python kept per iteration (
 constexpr int kMHBatchMax = 32;                     // iterations per batch (ad_mhstep_num is 20)
 constexpr int kCtlInit = 1, kCtlDecide = 2, kCtlTransform = 4;
 struct SweepCounters;
+// What the host reads back after a batch, in ONE device block (and one pinned mirror): a batch ends with a single copy of the
+// control block, the fused iteration's words and the log entries it used.
+struct BatchBlock {
+    MHControl ctl;
+    double fused[256];
+    MHLogEntry log[kMHBatchMax + 1];
+};
 struct MHControlArgs {
     MHControl *ctl;
     MHLogEntry *log;
@@ -190,6 +197,8 @@ struct smc_ctx {
     double *d_partials = nullptr;                // reduction partials
     int64_t partials_cap = 0;
     double *d_small = nullptr, *h_small = nullptr;  // small results (device / pinned host), 4096 doubles
+    smc::BatchBlock *d_batch = nullptr, *h_batch = nullptr;   // control block, fused words and batch log (host copy pinned); the six
+                                                              // pointers d_/h_fused, d_/h_mhctl and d_/h_mhlog point into them
     double *d_fused = nullptr, *h_fused = nullptr;  // the fused Metropolis iteration's own 256 doubles (carried moments, cov_m, factor)
     double *d_ess = nullptr, *h_ess = nullptr;      // the fused ESS search's own 128 doubles: max(lk) and the candidates' sums
     bool ess_max_valid = false;                     // d_ess[0] holds max over the PRED set's lk as it is now
@@ -221,6 +230,7 @@ struct smc_ctx {
     double *d_mn_thr = nullptr;      // multinomial resampling: n_global + 1 thresholds
     double *d_mn_blk = nullptr;      // ... and their per-tile sums
     unsigned long long *d_queue = nullptr;
+    unsigned long long *d_finish_rows = nullptr;   // accept kernel: one row of counts per block + its arrival counter (mm_kernels.hip)
     smc::RejectArgs *d_reject = nullptr;   // early-rejection arguments of the running sweep (written by its propose kernel)
     int32_t *d_stiff_list = nullptr;       // stiff list (item_cap entries) and its two alternating counters
     unsigned *d_stiff_count = nullptr;
@@ -282,7 +292,10 @@ namespace smc {
 
 // kernel launchers implemented in mm_kernels.hip
 void launch_mm_loglik(smc_ctx *ctx, const double *theta, int64_t stride, int64_t n, double *lk, double *pred);
-void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh);   // mh.moment_rows set: returns the row count in ctx->moment_rows_n
+// mh.moment_rows set: returns the row count in ctx->moment_rows_n.  ctl_after (with w_cov): the control step of a batch that follows
+// this sweep on one rank (its rows / n_rows are filled in here); the accept kernel's last block runs it, no launch of its own
+void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh, const MHControlArgs *ctl_after = nullptr, const double *w_cov = nullptr);
+size_t finish_rows_bytes();                 // mm_kernels.hip: size of ctx->d_finish_rows
 int query_solve_blocks_per_cu(bool fast);
 // in-phase patience of homogeneous and of cost-ordered sweeps (solve_sched.h; profiles/r03_ab_patience.log, r03_ab_cost_order.log)
 constexpr int kInPhasePatience = 12;
