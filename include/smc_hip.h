@@ -160,6 +160,40 @@ int smc_user_model_dump_source3(const char *source, int n_states, int dim, int m
  * work.  A model of smc_set_model_user / 2 is predicted by a kernel compiled at its first call and needs data that
  * smc_set_model_user3 would accept with no NaN. */
 int smc_user_predict(smc_ctx *ctx, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts);
+/* Predictions on a DESIGN other than the data's: t_new (n_ex_new x n_t_new) and cond_new (n_ex_new x n_cond), by the row rules
+ * of smc_set_model_user3 - a finite strictly increasing run, then only NaN; t_new[e][0] is the initial time; integration runs to
+ * the row's last finite time.  Replaces setting the model again with all-NaN observations in order to predict at other times or
+ * for an experiment that was never run.  pred[((p * n_ex_new + e) * n_t_new + i) * n_obs + k], NaN past a row's end and from
+ * where a solve failed on; raw outputs.  t_new == NULL: the data's own design - pred, n_failed and attempts are then those of
+ * smc_user_predict, bit for bit (and the data-side refusal of a one-output model applies).  An explicit design works for every
+ * user model (a model of smc_set_model_user / 2 through its prediction kernel, compiled at the first call).  The design reaches
+ * the kernel as a second LDS image with every observation NaN: no recompile.  A design whose image exceeds the kernel's LDS table
+ * runs in groups of consecutive experiments; n_failed then counts a particle once per group in which one of its solves failed.
+ * Fails with the reason for a design that breaks the row rules, and with the bytes needed and available when a single row does
+ * not fit the table.  Own staging buffers: the particle sets and their lk are not touched. */
+int smc_user_predict_at(smc_ctx *ctx, const double *particle, int64_t n, const double *t_new, const double *cond_new, int n_ex_new,
+                        int n_t_new, double *pred, int64_t *n_failed, int64_t *attempts);
+/* Posterior predictive SUMMARIES of a resident particle set, formed on the device: replaces downloading the set, smc_user_predict
+ * of it (n x n_ex x n_t x n_obs doubles over the bus) and a reduction on the host.  set: SMC_SET_PRED or SMC_SET_FILT, its n_local
+ * particles equally weighted (the resampled posterior).  Design as smc_user_predict_at (t_new == NULL: the data's).  A cell is
+ * (experiment e, time i, output k), index c = (e * n_t_new + i) * n_obs + k.  Per cell, over the m = n_finite[c] finite
+ * predictions (NaN past a row's end and where a solve failed): mean[c], sd[c] (population, two-pass; summed in a fixed order, a
+ * repeated call returns the same bits), and for every probs[j] (0 < n_probs <= 16, each in [0, 1]) the order statistics of ranks
+ * floor and ceil of (m - 1) probs[j] in lower[j * cells + c] and upper[j * cells + c] - the elements numpy.nanquantile picks with
+ * method "lower" / "higher"; exact (a radix select), no sketch.  m = 0: NaN in all of them.
+ * noise != 0: the summaries are of replicated observations pred + sigma_p s_k z - sigma_p the particle's last parameter (est_sigma)
+ * or sigma_fixed, s_k the model's obs_scale, z a standard normal (Philox4x32-10, Box-Muller) keyed by (seed, global_offset + p,
+ * c): independent of the staging groups.  noise == 0 draws nothing.
+ * Staging: predictions plus keys, 2 x n_local x n_t_new x n_obs x 8 B per experiment, stay within max_staging_bytes (0: most of the
+ * free device memory) by running groups of experiments; a single experiment that does not fit is refused with the bytes needed.
+ * Nothing with a particle axis leaves the device: cells x (3 + 2 n_probs) numbers and the counters come back in one
+ * synchronisation.  The particle sets, their lk, the accept flags and smc_work_totals stay as they were.  n_failed / attempts as
+ * smc_user_predict_at.  kernel_ms (may be NULL): [0] the prediction sweeps, [1] the summary kernels, from events.
+ * Several ranks: the summary describes THIS rank's block of particles only; merging order statistics across ranks is not done. */
+int smc_user_predict_summary(smc_ctx *ctx, int set, const double *t_new, const double *cond_new, int n_ex_new, int n_t_new,
+                             const double *probs, int n_probs, int noise, uint64_t seed, int64_t global_offset,
+                             size_t max_staging_bytes, double *mean, double *sd, double *lower, double *upper, int64_t *n_finite,
+                             int64_t *n_failed, int64_t *attempts, double *kernel_ms);
 /* BDF user model: device-counted work of the LAST smc_loglik / smc_mh_step_* sweep, in the manner of
  * smc_meth_sweep_counters: out = {accepted BDF steps, Newton iterations, LU factorisations, Jacobian evaluations} summed over
  * the sweep's solves (masked proposals left out).  Fails with a message for an RK45 model. */

@@ -23,6 +23,7 @@ SMC_PRIOR_MODE_MASK, SMC_PRIOR_MODE_RATIO_MASK, SMC_PRIOR_MODE_RATIO = 0, 1, 2
 PRIOR_MODES = {"mask": 0, "ratio_mask": 1, "ratio": 2}
 RESAMPLING = {"residual_systematic": 0, "systematic": 1, "multinomial": 2}
 SMC_MAX_ESS_CAND = 16
+SMC_PRED_MAX_PROBS = 16
 SMC_ABI_VERSION = 3
 SMC_SWEEP_COUNTER_WORDS = 14
 SWEEP_COUNTER_NAMES = ("n_failed", "rk_attempts", "accepted_now", "accepted_ever", "newton_iters", "factorisations", "failed_solves",
@@ -65,6 +66,9 @@ SIGNATURES = {
     "smc_user_model_check3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p]),
     "smc_user_predict": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, c_i64p, c_i64p]),
+    "smc_user_predict_at": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, cint, cint, c_dp, c_i64p, c_i64p]),
+    "smc_user_predict_summary": (cint, [c_ctx, cint, c_dp, c_dp, cint, cint, c_dp, cint, cint, u64, i64, ctypes.c_size_t, c_dp, c_dp,
+                                         c_dp, c_dp, c_i64p, c_i64p, c_i64p, c_dp]),
     "smc_user_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_check": (cint, [c_ctx, c_i64p]),

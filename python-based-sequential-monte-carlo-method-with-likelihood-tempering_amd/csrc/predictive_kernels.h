@@ -1,0 +1,42 @@
+// predictive_kernels.h -- the summary kernels of smc_user_predict_summary (include/smc_hip.h): per cell (experiment, time,
+// output) the mean, the standard deviation and exact order statistics over the particle axis of a block of predictions that
+// the prediction kernel has left in device memory.  Implemented in predictive_kernels.hip; called from user_model.hip.
+#pragma once
+#include <stdint.h>
+
+#include "predictive_select.h"
+
+struct smc_ctx;
+
+namespace smc {
+
+// One group of experiments: `pred` is what the prediction kernel wrote for n particles, particle-major
+// (pred[p * cells + c], c = (e_local * n_t + i) * n_obs + k); `keys` (pred_summary_key_bytes) is the summary's own buffer.
+struct PredSummaryArgs {
+    const double *pred;
+    unsigned long long *keys;      // cell-major: keys[c * stride + p] = smc_sel::key_of(value), stride = n rounded up to even
+    int64_t n;
+    int cells;                     // of this group
+    int64_t cell_base, cells_total;   // the group's first cell in the whole design, and the design's cell count
+    int n_obs;
+    // replicated observations (noise != 0): value = pred + sigma_p * scale[k] * z(seed, global_offset + p, cell_base + c)
+    int noise;
+    const double *theta;           // SoA, theta[c * stride + p]
+    int64_t stride;
+    int dim, est_sigma;
+    double sigma_fixed;
+    double scale[8];
+    uint64_t seed;
+    int64_t global_offset;
+    // order statistics
+    int n_probs;
+    double probs[smc_sel::kMaxProbs];
+    // results, one value per cell of the whole design: [mean | sd | n_finite | lower[n_probs] | upper[n_probs]] x cells_total
+    double *out;
+};
+
+size_t pred_summary_key_bytes(int64_t n, int cells);
+// the two launches of a group, on ctx->stream: transpose into keys (adding the noise), then one block per cell
+void launch_pred_summary(smc_ctx *ctx, const PredSummaryArgs &a);
+
+}  // namespace smc

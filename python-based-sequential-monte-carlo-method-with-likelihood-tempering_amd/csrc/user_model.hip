@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -26,6 +27,7 @@
 #include "solve_sched.h"   // kChunk: the grid is sized in chunks of the shared scheduler
 #include "stage_kernels.h" // launch_aos_to_soa (smc_user_predict)
 #include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
+#include "predictive_kernels.h"   // smc_user_predict_summary's kernels
 
 namespace smc {
 
@@ -146,6 +148,9 @@ struct UserModel {
     int blocks_per_cu_pred = 4;
     double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;   // smc_user_predict's staging: parameters (AoS + SoA), lk, pred
     int64_t p_cap = 0;
+    // what a design other than the data's needs again on the host (smc_user_predict_at, smc_user_predict_summary)
+    std::vector<double> h_t, h_cond;
+    double scale[kUserMaxObs] = {1, 1, 1, 1, 1, 1, 1, 1};
 };
 
 // an optional ingredient (smc_user_cost, smc_user_jac, smc_user_obs_vec; smc_div): a source that mentions it must define it
@@ -447,6 +452,124 @@ static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
     return 0;
 }
 
+// ---- a design other than the data's (smc_user_predict_at, smc_user_predict_summary) ----------------------------------------
+// The prediction kernel takes n_ex and n_t as arguments and its data as an image, so a design is a second bundle of what
+// launch_user_kernel reads from the model, with every observation NaN (m_e = 0, no likelihood term).  A design whose image does
+// not fit the LDS cap runs as several such bundles, one per run of consecutive experiments.
+
+// what a launch writes per (experiment, particle): shared by the groups of a design, which run one after the other
+struct DesignItems {
+    double *d_sum = nullptr;
+    int *d_info = nullptr;
+    unsigned *d_bdf_counts = nullptr;
+    void release() {
+        (void)hipFree(d_sum);
+        (void)hipFree(d_info);
+        (void)hipFree(d_bdf_counts);
+        d_sum = nullptr;
+        d_info = nullptr;
+        d_bdf_counts = nullptr;
+    }
+};
+static size_t design_item_bytes(const UserModel *u) {      // per (experiment, particle)
+    return sizeof(double) + sizeof(int) + (u->method == SMC_USER_METHOD_BDF ? 4 * sizeof(unsigned) : 0);
+}
+static bool design_items_alloc(const UserModel *u, DesignItems &it, int64_t n, int g) {
+    const size_t items = (size_t)n * g;
+    return hipMalloc(&it.d_sum, items * sizeof(double)) == hipSuccess && hipMalloc(&it.d_info, items * sizeof(int)) == hipSuccess &&
+           (u->method != SMC_USER_METHOD_BDF || hipMalloc(&it.d_bdf_counts, 4 * items * sizeof(unsigned)) == hipSuccess);
+}
+
+struct DesignGroup {
+    double *d_img = nullptr, *d_cond = nullptr, *d_const = nullptr;
+    int e0 = 0, n_ex = 0, n_t = 0, img_len = 0, blocks_per_cu = 4;
+    void release() {
+        (void)hipFree(d_img);
+        (void)hipFree(d_cond);
+        (void)hipFree(d_const);
+        d_img = d_cond = d_const = nullptr;
+    }
+};
+
+// experiments [e0, e0 + g) of the design (t: rows of n_t times, cond: rows of n_cond numbers) as a bundle on the device
+static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const double *t, const double *cond, int e0, int g, int n_t) {
+    const std::vector<double> nan_obs((size_t)g * n_t * u->n_obs, std::nan("")), zero(2 * (size_t)g, 0.0);
+    std::vector<double> me, ls;
+    if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
+    const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls);
+    const size_t nc = (size_t)g * (u->n_cond > 0 ? u->n_cond : 1) * sizeof(double);
+    dg.e0 = e0;
+    dg.n_ex = g;
+    dg.n_t = n_t;
+    dg.img_len = (int)img.size();
+    bool ok = hipMalloc(&dg.d_img, img.size() * sizeof(double)) == hipSuccess && hipMalloc(&dg.d_cond, nc) == hipSuccess &&
+              hipMalloc(&dg.d_const, zero.size() * sizeof(double)) == hipSuccess &&
+              hipMemcpy(dg.d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && u->n_cond > 0)
+        ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * u->n_cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs);
+    int nb = 0;
+    if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
+    (void)c;
+    return ok;
+}
+
+// while it lives, launch_user_kernel(..., pred) runs the prediction kernel on the group instead of the data
+struct DesignScope {
+    UserModel *u;
+    UserModel saved;
+    DesignScope(UserModel *um, const DesignGroup &dg, const DesignItems &it) : u(um), saved(*um) {
+        u->d_img = dg.d_img;
+        u->img_len = dg.img_len;
+        u->d_cond = dg.d_cond;
+        u->d_const = dg.d_const;
+        u->n_ex = dg.n_ex;
+        u->n_t = dg.n_t;
+        u->blocks_per_cu_pred = dg.blocks_per_cu;
+        u->d_sum = it.d_sum;
+        u->d_info = it.d_info;
+        u->d_bdf_counts = it.d_bdf_counts;
+    }
+    ~DesignScope() {
+        saved.parity = u->parity;      // the one thing a launch changes in the model
+        *u = saved;
+    }
+};
+
+// the largest run of experiments whose image fits the LDS cap (0: not even one row)
+static int design_lds_group(const UserModel *u, int n_ex, int n_t) {
+    int g = 0;
+    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs) <= kUserLdsCap) ++g;
+    return g;
+}
+
+// the prediction kernel of the model: part of a multi-output module, else compiled at the first call that needs it
+static int ensure_pred_kernel(smc_ctx *c, UserModel *u, const char *who) {
+    if (u->fn_pred) return 0;
+    std::vector<char> code;
+    std::string lg;
+    if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg))
+        return smc_fail(c, (std::string(who) + ": the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
+    if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
+        hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
+        u->fn_pred = nullptr;
+        return smc_fail(c, (std::string(who) + ": loading the prediction module failed").c_str());
+    }
+    // the data's own image may be one the kernel cannot hold (smc_user_predict refuses it): then only designs are predicted
+    if (user_lds_bytes3(u->n_states, u->n_ex, u->n_t, 1) <= kUserLdsCap && prepare_pred_kernel(c, u) != 0) {
+        u->fn_pred = nullptr;
+        return 1;
+    }
+    return 0;
+}
+// any design may need more dynamic LDS than the data's image: raised once to the cap
+static int raise_pred_lds(smc_ctx *c, UserModel *u, const char *who) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(u->fn_pred), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kUserLdsCap) != hipSuccess)
+        return smc_fail(c, (std::string(who) + ": raising the dynamic LDS limit of the prediction kernel failed").c_str());
+    return 0;
+}
+
 }  // namespace smc
 
 using namespace smc;
@@ -608,6 +731,9 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         }
     }
     u->source = source;
+    if (t) u->h_t.assign(t, t + (size_t)n_ex * n_t);
+    if (n_cond > 0) u->h_cond.assign(cond, cond + (size_t)n_ex * n_cond);
+    for (int k = 0; k < n_obs && obs_scale; ++k) u->scale[k] = obs_scale[k];
     u->n_ex = n_ex;
     u->n_t = n_t;
     u->n_cond = n_cond;
@@ -713,6 +839,246 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
     if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
     return 0;
 }
+// the design of a call: (t_new, cond_new) checked by the rules of smc_set_model_user3, or the data's own
+static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const double *&t, const double *&cond, int &n_ex, int &n_t) {
+    const std::string w = std::string(who) + ": ";
+    if (!t) {
+        if (!u->d_img) return smc_fail(c, u->img_error.c_str());
+        t = u->h_t.data();
+        cond = u->h_cond.data();
+        n_ex = u->n_ex;
+        n_t = u->n_t;
+        return 0;
+    }
+    if (n_ex < 1 || n_t < 1) return smc_fail(c, (w + "bad design shape").c_str());
+    if (u->n_cond > 0 && !cond) return smc_fail(c, (w + "the model has n_cond > 0 and cond_new is NULL").c_str());
+    const std::vector<double> nan_obs((size_t)n_ex * n_t * u->n_obs, std::nan(""));
+    std::vector<double> me, ls;
+    const std::string bad = obs_layout(t, nan_obs.data(), u->scale, n_ex, n_t, u->n_obs, me, ls);
+    if (!bad.empty()) return smc_fail(c, (w + bad + " (t_new)").c_str());
+    return 0;
+}
+static int design_too_large(smc_ctx *c, const UserModel *u, const char *who, int n_t) {
+    return smc_fail(c, (std::string(who) + ": one row of the design does not fit the kernel's LDS table: " +
+                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs)) + " B needed, " + std::to_string(kUserLdsCap) +
+                        " B available").c_str());
+}
+
+int smc_user_predict_at(smc_ctx *c, const double *particle, int64_t n, const double *t_new, const double *cond_new, int n_ex_new,
+                        int n_t_new, double *pred, int64_t *n_failed, int64_t *attempts) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_predict_at: no user model has been set");
+    if (n < 0 || (n > 0 && (!particle || !pred))) return smc_fail(c, "smc_user_predict_at: bad arguments");
+    if (!t_new) {       // the data's design: smc_user_predict itself
+        std::vector<double> lk((size_t)n);
+        return smc_user_predict(c, particle, n, lk.data(), pred, n_failed, attempts);
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
+    if (n_failed) *n_failed = 0;
+    if (attempts) *attempts = 0;
+    const double *t = t_new, *cond = cond_new;
+    int n_ex = n_ex_new, n_t = n_t_new;
+    if (resolve_design(c, u, "smc_user_predict_at", t, cond, n_ex, n_t) != 0) return 1;
+    if (n == 0) return 0;
+    const int g_max = design_lds_group(u, n_ex, n_t);
+    if (g_max < 1) return design_too_large(c, u, "smc_user_predict_at", n_t);
+    if (ensure_pred_kernel(c, u, "smc_user_predict_at") != 0 || raise_pred_lds(c, u, "smc_user_predict_at") != 0) return 1;
+    const int dim = c->dim;
+    const int64_t chunk = n < c->n_local ? n : c->n_local;      // the scan lists of a model with a cost hint hold n_local particles
+    const size_t row = (size_t)n_t * u->n_obs;                   // one experiment of one particle
+    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
+    DesignItems items;
+    double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;
+    int rc = 0;
+    bool ok = design_items_alloc(u, items, chunk, g_max) && hipMalloc(&d_pt, (size_t)chunk * dim * 2 * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_plk, (size_t)chunk * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_ppred, (size_t)chunk * g_max * row * sizeof(double)) == hipSuccess;
+    for (size_t k = 0; ok && k < groups.size(); ++k) {
+        const int e0 = (int)k * g_max;
+        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
+    }
+    if (!ok) rc = smc_fail(c, "smc_user_predict_at: device allocation / upload failed");
+    double *aos = d_pt, *soa = d_pt + (size_t)chunk * dim;
+    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
+                    (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
+        rc = smc_fail(c, "smc_user_predict_at: clearing the counters failed");
+    for (int64_t off = 0; rc == 0 && off < n; off += chunk) {
+        const int64_t m = (n - off < chunk) ? n - off : chunk;
+        if (hipMemcpyAsync(aos, particle + off * dim, (size_t)m * dim * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            rc = smc_fail(c, "smc_user_predict_at: upload failed");
+            break;
+        }
+        launch_aos_to_soa(c, aos, soa, m, dim, m);
+        for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
+            const DesignGroup &dg = groups[k];
+            {
+                DesignScope scope(u, dg, items);
+                launch_user_kernel(c, soa, m, m, nullptr, d_plk, false, d_ppred);
+            }
+            if (c->launch_failed) {
+                c->launch_failed = false;
+                rc = 1;
+                break;
+            }
+            // the group's experiments of every particle into their place in pred[p][e][i][k]
+            if (hipMemcpy2DAsync(pred + ((size_t)off * n_ex + dg.e0) * row, (size_t)n_ex * row * sizeof(double), d_ppred,
+                                 (size_t)dg.n_ex * row * sizeof(double), (size_t)dg.n_ex * row * sizeof(double), (size_t)m,
+                                 hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+                rc = smc_fail(c, "smc_user_predict_at: download failed");
+        }
+    }
+    if (rc == 0 && (hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipStreamSynchronize(c->stream) != hipSuccess))
+        rc = smc_fail(c, (std::string("smc_user_predict_at: ") + hipGetErrorString(hipGetLastError())).c_str());
+    if (rc != 0) (void)hipStreamSynchronize(c->stream);
+    if (rc == 0 && n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
+    if (rc == 0 && attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
+    for (DesignGroup &dg : groups) dg.release();
+    items.release();
+    (void)hipFree(d_pt);
+    (void)hipFree(d_plk);
+    (void)hipFree(d_ppred);
+    return rc;
+}
+
+int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const double *cond_new, int n_ex_new, int n_t_new,
+                             const double *probs, int n_probs, int noise, uint64_t seed, int64_t global_offset, size_t max_staging_bytes,
+                             double *mean, double *sd, double *lower, double *upper, int64_t *n_finite, int64_t *n_failed,
+                             int64_t *attempts, double *kernel_ms) {
+    const char *who = "smc_user_predict_summary";
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_predict_summary: no user model has been set");
+    if (set != SMC_SET_PRED && set != SMC_SET_FILT) return smc_fail(c, "smc_user_predict_summary: set must be SMC_SET_PRED or SMC_SET_FILT");
+    if (n_probs < 1 || n_probs > smc_sel::kMaxProbs || !probs) return smc_fail(c, "smc_user_predict_summary: n_probs outside 1 .. 16");
+    for (int j = 0; j < n_probs; ++j)
+        if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return smc_fail(c, "smc_user_predict_summary: a probability outside [0, 1]");
+    if (!mean || !sd || !lower || !upper || !n_finite) return smc_fail(c, "smc_user_predict_summary: NULL result array");
+    if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
+    if (n_failed) *n_failed = 0;
+    if (attempts) *attempts = 0;
+    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
+    const double *t = t_new, *cond = cond_new;
+    int n_ex = n_ex_new, n_t = n_t_new;
+    if (resolve_design(c, u, who, t, cond, n_ex, n_t) != 0) return 1;
+    const int64_t n = c->n_local;
+    const int g_lds = design_lds_group(u, n_ex, n_t);
+    if (g_lds < 1) return design_too_large(c, u, who, n_t);
+    // staging: per experiment the predictions and their keys (n x n_t x n_obs words each) and the per-item words of a launch;
+    // once, the likelihoods the finish kernel writes and the results
+    const size_t row = (size_t)n_t * u->n_obs;
+    const int64_t cells_total = (int64_t)n_ex * (int64_t)row;
+    const size_t out_words = (size_t)cells_total * (3 + 2 * (size_t)n_probs);
+    const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pred_summary_key_bytes(n, (int)row);
+    const size_t fixed = (size_t)n * sizeof(double) + out_words * sizeof(double);
+    size_t budget = max_staging_bytes;
+    if (budget == 0) {      // default: most of what is free
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return smc_fail(c, "smc_user_predict_summary: hipMemGetInfo failed");
+        budget = free_b / 10 * 8;
+    }
+    if (budget < fixed + per_ex)
+        return smc_fail(c, (std::string(who) + ": one experiment of the design needs " + std::to_string(fixed + per_ex) +
+                            " B of staging (predictions and keys of " + std::to_string(n) + " particles), max_staging_bytes allows " +
+                            std::to_string(budget) + " B").c_str());
+    int g_max = (int)std::min<size_t>((budget - fixed) / per_ex, (size_t)g_lds);
+    if (g_max > n_ex) g_max = n_ex;
+    if (ensure_pred_kernel(c, u, who) != 0 || raise_pred_lds(c, u, who) != 0) return 1;
+
+    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
+    std::vector<hipEvent_t> ev(3 * groups.size(), nullptr);
+    DesignItems items;
+    double *d_plk = nullptr, *d_ppred = nullptr, *d_out = nullptr;
+    unsigned long long *d_keys = nullptr;
+    std::vector<double> h_out(out_words);
+    int rc = 0;
+    bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_ppred, (size_t)n * g_max * row * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_keys, pred_summary_key_bytes(n, (int)(g_max * row))) == hipSuccess &&
+              hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess;
+    for (size_t k = 0; ok && k < groups.size(); ++k) {
+        const int e0 = (int)k * g_max;
+        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
+    }
+    for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
+    if (!ok) rc = smc_fail(c, "smc_user_predict_summary: device allocation / upload failed");
+    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
+                    (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
+        rc = smc_fail(c, "smc_user_predict_summary: clearing the counters failed");
+    const ParticleSet &P = c->set[set];
+    for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
+        const DesignGroup &dg = groups[k];
+        (void)hipEventRecord(ev[3 * k], c->stream);
+        {
+            DesignScope scope(u, dg, items);
+            launch_user_kernel(c, P.theta, P.stride, n, nullptr, d_plk, false, d_ppred);
+        }
+        if (c->launch_failed) {
+            c->launch_failed = false;
+            rc = 1;
+            break;
+        }
+        (void)hipEventRecord(ev[3 * k + 1], c->stream);
+        PredSummaryArgs a{};
+        a.pred = d_ppred;
+        a.keys = d_keys;
+        a.n = n;
+        a.cells = (int)(dg.n_ex * row);
+        a.cell_base = (int64_t)dg.e0 * (int64_t)row;      // the GLOBAL cell index keys the noise: grouping cannot change a result
+        a.cells_total = cells_total;
+        a.n_obs = u->n_obs;
+        a.noise = noise != 0;
+        a.theta = P.theta;
+        a.stride = P.stride;
+        a.dim = c->dim;
+        a.est_sigma = u->est_sigma;
+        a.sigma_fixed = u->sigma_fixed;
+        for (int j = 0; j < kUserMaxObs; ++j) a.scale[j] = u->scale[j];
+        a.seed = seed;
+        a.global_offset = global_offset;
+        a.n_probs = n_probs;
+        for (int j = 0; j < n_probs; ++j) a.probs[j] = probs[j];
+        a.out = d_out;
+        launch_pred_summary(c, a);
+        (void)hipEventRecord(ev[3 * k + 2], c->stream);
+    }
+    // the one synchronisation: results and counters
+    if (rc == 0 && (hipMemcpyAsync(h_out.data(), d_out, out_words * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipStreamSynchronize(c->stream) != hipSuccess))
+        rc = smc_fail(c, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+    if (rc != 0) (void)hipStreamSynchronize(c->stream);
+    if (rc == 0) {
+        const size_t ct = (size_t)cells_total;
+        for (size_t i = 0; i < ct; ++i) {
+            mean[i] = h_out[i];
+            sd[i] = h_out[ct + i];
+            n_finite[i] = (int64_t)h_out[2 * ct + i];
+        }
+        for (size_t i = 0; i < ct * (size_t)n_probs; ++i) {
+            lower[i] = h_out[3 * ct + i];
+            upper[i] = h_out[(3 + (size_t)n_probs) * ct + i];
+        }
+        if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
+        if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
+        for (size_t k = 0; kernel_ms && k < groups.size(); ++k) {
+            float a_ms = 0.f, b_ms = 0.f;
+            if (hipEventElapsedTime(&a_ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) kernel_ms[0] += a_ms;
+            if (hipEventElapsedTime(&b_ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) kernel_ms[1] += b_ms;
+        }
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (DesignGroup &dg : groups) dg.release();
+    items.release();
+    (void)hipFree(d_plk);
+    (void)hipFree(d_ppred);
+    (void)hipFree(d_keys);
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int smc_user_sweep_counters(smc_ctx *c, int64_t out[4]) {
     if (!c) return smc_fail(nullptr, "NULL context");
     UserModel *u = (UserModel *)c->user;

@@ -319,7 +319,7 @@ def _rng_state_from_json(j):
 
 def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy", verbose: bool = True,
             p_pred0=None, seed_device: int | None = None, log=print, dump_dir: str | None = None,
-            resume_from: tuple | None = None):
+            resume_from: tuple | None = None, predictive: dict | None = None):
     """Run the tempering loop (main:95-262).  The engine must already hold the model and the prior.
 
     dump_dir: per-step dumps in the reference's formats plus a small state file per step.
@@ -327,8 +327,13 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     likelihoods recomputed, gamma / logZ / random state from pred/{step}_state.json; with rng="device" the continuation
     is bit-identical to the uninterrupted run (tests/test_gpu_parity.py).
 
+    predictive: keyword arguments of HipEngine.predictive_summary (user models only; `which` defaults to the final posterior,
+    SMC_SET_PRED): the summary is formed on the device before returning and stored as out["predictive"].
+
     Returns a dict: final particles (this rank's block), lk, schedule records, logZ, counters.
     """
+    if predictive is not None and (getattr(engine, "model", None) is None or engine.model[0] != "user"):
+        raise ValueError("run_smc: predictive= applies to a user model (HipEngine.set_model_user) only")
     s = s or SMCSettings()
     comm = comm or SingleComm()
     n = s.n_particle
@@ -545,6 +550,9 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
         _dump(dump_dir, "pred/last_p_pred", final, rank, world)
         _dump(dump_dir, "Posterior_Distribution", final, rank, world, header=list(s.priors.keys()))
     pin = {"pinned": True} if (s.pinned_results and getattr(engine, "pinned_downloads", False)) else {}
-    return {"p_pred": engine.download_particles(SMC_SET_PRED, **pin), "lk": engine.download_lk(SMC_SET_PRED, **pin),
-            "records": records, "logZ": logZ, "gamma": gamma_new, "step": step, "stats": stats,
-            "wall_s": time.perf_counter() - start_time}
+    out = {"p_pred": engine.download_particles(SMC_SET_PRED, **pin), "lk": engine.download_lk(SMC_SET_PRED, **pin),
+           "records": records, "logZ": logZ, "gamma": gamma_new, "step": step, "stats": stats,
+           "wall_s": time.perf_counter() - start_time}
+    if predictive is not None:
+        out["predictive"] = engine.predictive_summary(**{"which": SMC_SET_PRED, **predictive})
+    return out

@@ -124,6 +124,7 @@ class HipEngine:
         self.ctx = ctx
         self.model = None
         self.user_n_obs = 1     # outputs per data time of a user model (set_model_user)
+        self.user_n_cond = 0    # ... and its numbers per experiment
         if "smc_ess_search_global" in B.MISSING:   # A/B build of an older revision (SMC_HIP_LIB): the driver falls back
             self.ess_search_global = None
         self._peer_barrier = None
@@ -208,6 +209,7 @@ class HipEngine:
                                                 float(atol), B.USER_METHODS[method]), "smc_set_model_user")
         self.model = ("user", t.shape[0], t.shape[1])      # the driver indexes this 3-tuple
         self.user_n_obs = n_obs
+        self.user_n_cond = cond.shape[1]
 
     def set_model_methanation(self, cond, guess, obs, base_params, est_position, est_sigma=True, sigma_fixed=5.0,
                               tf=75.0, rtol=1e-6, atol=1e-6):
@@ -413,6 +415,72 @@ class HipEngine:
         self._ck(self.L.smc_user_predict(self.ctx, _dp(particles), n, _dp(lk), _dp(pred), ctypes.byref(nf), ctypes.byref(att)),
                  "smc_user_predict")
         return lk, pred, {"n_failed": nf.value, "rk_attempts": att.value}
+
+    def _design(self, what, t, cond):
+        """(t, cond) of a prediction design as contiguous arrays and their C arguments; (None, None): the data's own design."""
+        if t is None:
+            if cond is not None:
+                raise ValueError(f"{what}: cond without t (a design is both, or neither for the data's own)")
+            return None, None, (None, None, 0, 0), (self.model[1], self.model[2])
+        from .user_models import design_layout
+        t = _f64(t)
+        design_layout(t, cond, self.user_n_cond)
+        cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond, dtype=np.float64).reshape(t.shape[0], -1))
+        cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
+        return t, cbuf, (_dp(t), _dp(cbuf), t.shape[0], t.shape[1]), t.shape
+
+    def predict_user_at(self, particles, t=None, cond=None):
+        """A user model's predictions for host particles (n, dim) on a design of its own (include/smc_hip.h: smc_user_predict_at):
+        t (n_ex_new, n_t_new) rows of output times (the first is the initial time; a row may end in NaN), cond
+        (n_ex_new, n_cond) - other times, a longer horizon, an experiment that was never run.  Without a design: the data's,
+        with predict_user's bits.  Returns pred (n, n_ex_new, n_t_new, n_obs), NaN past a row's end and from where a solve
+        failed, and {"n_failed", "rk_attempts"}.  ValueError for a design that breaks the rules (user_models.design_layout)."""
+        if self.model is None or self.model[0] != "user":
+            raise SmcError("predict_user_at: no user model has been set")
+        particles = _f64(particles)
+        if particles.ndim != 2 or particles.shape[1] != self.dim:
+            raise ValueError(f"predict_user_at: particles must be (n, {self.dim}), got {particles.shape}")
+        t, cbuf, cargs, shape = self._design("predict_user_at", t, cond)
+        n = particles.shape[0]
+        pred = np.empty((n, shape[0], shape[1], self.user_n_obs))
+        nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._ck(self.L.smc_user_predict_at(self.ctx, _dp(particles), n, *cargs, _dp(pred), ctypes.byref(nf), ctypes.byref(att)),
+                 "smc_user_predict_at")
+        return pred, {"n_failed": nf.value, "rk_attempts": att.value}
+
+    def predictive_summary(self, which=SMC_SET_FILT, probs=(0.025, 0.5, 0.975), t=None, cond=None, noise=False, seed=0,
+                           global_offset=0, max_staging_bytes=0):
+        """Posterior predictive summaries of a resident particle set, formed on the device (include/smc_hip.h:
+        smc_user_predict_summary): per cell (experiment, time, output) of the design (t, cond; None: the data's) over the set's
+        equally weighted particles.  Returns {"mean", "sd", "n_finite": (n_ex, n_t, n_obs); "lower", "upper", "quantile":
+        (n_probs, n_ex, n_t, n_obs) - the order statistics np.nanquantile picks with method "lower" / "higher" and the linear
+        value lower + (upper - lower) * frac between them (user_models.quantile_ranks); "n_failed", "rk_attempts"; "kernel_ms":
+        {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
+        global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
+        With several ranks the summary describes this rank's block only."""
+        if self.model is None or self.model[0] != "user":
+            raise SmcError("predictive_summary: no user model has been set")
+        q = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))
+        if not 1 <= q.size <= B.SMC_PRED_MAX_PROBS or not np.all((q >= 0) & (q <= 1)):
+            raise ValueError(f"predictive_summary: 1 .. {B.SMC_PRED_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
+        t, cbuf, cargs, shape = self._design("predictive_summary", t, cond)
+        cells = (shape[0], shape[1], self.user_n_obs)
+        mean, sd = np.empty(cells), np.empty(cells)
+        lower, upper = np.empty((q.size,) + cells), np.empty((q.size,) + cells)
+        nfin = np.empty(cells, dtype=np.int64)
+        nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
+        ms = np.zeros(2)
+        self._ck(self.L.smc_user_predict_summary(self.ctx, int(which), *cargs, _dp(q), q.size, int(bool(noise)), int(seed),
+                                                 int(global_offset), int(max_staging_bytes), _dp(mean), _dp(sd), _dp(lower),
+                                                 _dp(upper), nfin.ctypes.data_as(B.c_i64p), ctypes.byref(nf), ctypes.byref(att),
+                                                 _dp(ms)), "smc_user_predict_summary")
+        from .user_models import quantile_ranks
+        frac = quantile_ranks(np.maximum(nfin, 1)[None], q[:, None, None, None])[2]
+        with np.errstate(invalid="ignore"):
+            quantile = np.where(upper == lower, lower, lower + (upper - lower) * frac)
+            quantile = np.minimum(np.maximum(quantile, lower), upper)       # rounding cannot leave the bracket
+        return {"mean": mean, "sd": sd, "n_finite": nfin, "lower": lower, "upper": upper, "quantile": quantile,
+                "n_failed": nf.value, "rk_attempts": att.value, "kernel_ms": {"predict": float(ms[0]), "summary": float(ms[1])}}
 
     # ---- weights / ESS -------------------------------------------------------------------------
     def max_lk_local(self):

@@ -109,3 +109,47 @@ def obs_layout(t, obs, obs_scale=None):
     seen = ~np.isnan(o)
     return {"n_t_e": n_t_e.astype(np.int64), "m_e": seen.sum(axis=(1, 2)).astype(np.int64),
             "sum_log_scale": np.sum(np.where(seen, np.log(scale)[None, None, :], 0.0), axis=(1, 2))}
+
+
+def design_layout(t_new, cond_new, n_cond):
+    """The rules of a prediction design (include/smc_hip.h: smc_user_predict_at), in NumPy: t_new (n_ex_new, n_t_new) by the row
+    rules of obs_layout - a strictly increasing run of finite times, possibly followed by NaN only; t_new[e][0] is the initial
+    time - and cond_new (n_ex_new, n_cond) finite numbers (None only for n_cond = 0).  Returns n_t_e (n_ex_new,) int, the finite
+    times per row; raises ValueError, in obs_layout's words where the rule is the same (a row "of t" is then a row of t_new), for a design the library refuses."""
+    import numpy as np
+    t = np.asarray(t_new, dtype=np.float64)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"design_layout: t_new must be (n_ex_new, n_t_new), got {t.shape}")
+    n_ex = t.shape[0]
+    n_cond = int(n_cond)
+    if cond_new is None:
+        if n_cond != 0:
+            raise ValueError(f"design_layout: cond_new must be ({n_ex}, {n_cond}), got None")
+    else:
+        c = np.asarray(cond_new, dtype=np.float64)
+        if c.shape != (n_ex, n_cond) and not (c.ndim == 1 and n_cond == 1 and c.shape == (n_ex,)):
+            raise ValueError(f"design_layout: cond_new must be ({n_ex}, {n_cond}), got {c.shape}")
+        if not np.all(np.isfinite(c)):
+            raise ValueError("design_layout: cond_new must be finite")
+    try:
+        return obs_layout(t, np.full(t.shape + (1,), np.nan))["n_t_e"]
+    except ValueError as e:
+        raise ValueError(str(e).replace("obs_layout: ", "design_layout: ", 1)) from None
+
+
+def quantile_ranks(m, probs):
+    """Which order statistics a quantile is made of (include/smc_hip.h: smc_user_predict_summary): for m >= 1 sorted values and
+    probabilities in [0, 1] returns (lo, hi, frac) with lo = floor((m - 1) q), hi = ceil((m - 1) q) - the elements
+    np.quantile(method="lower" / "higher") picks - and frac the weight of the upper one in the linear rule,
+    quantile = x[lo] + (x[hi] - x[lo]) * frac.  m may be an array (one count per cell): the results broadcast m against probs."""
+    import numpy as np
+    m = np.asarray(m, dtype=np.int64)
+    q = np.asarray(probs, dtype=np.float64)
+    if np.any(m < 1):
+        raise ValueError("quantile_ranks: m must be >= 1")
+    if not np.all((q >= 0) & (q <= 1)):
+        raise ValueError("quantile_ranks: probabilities must lie in [0, 1]")
+    pos = (m - 1).astype(np.float64) * q
+    lo = np.minimum(np.floor(pos).astype(np.int64), m - 1)
+    hi = np.minimum(np.where(lo.astype(np.float64) < pos, lo + 1, lo), m - 1)
+    return lo, hi, pos - lo.astype(np.float64)
