@@ -171,7 +171,7 @@ class DaeStats(ctypes.Structure):
 
 class DaePolicy(ctypes.Structure):
     """Control policy of the BDF integrator (oracle/meth_dae_oracle.c: dae_policy).  The default of the C side (NULL) is the
-    checker of rounds 1-4; K8_POLICY is what the HIP kernel K8 does since round 5 (csrc/meth_dae_elem.h: SMC_K8_POLICY 1)."""
+    checker of rounds 1-4; K8_POLICY is what the HIP kernel K8 does since round 5 (csrc/meth_dae_elem.h: dae_integrate_with)."""
     _fields_ = [("reuse", ctypes.c_int32), ("newton", ctypes.c_int32), ("stepctl", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("epcon", ctypes.c_double), ("xrate", ctypes.c_double)]
 

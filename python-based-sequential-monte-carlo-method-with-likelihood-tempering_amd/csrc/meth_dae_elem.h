@@ -1,6 +1,7 @@
-// meth_dae_elem.h -- K8 v3: one solve per wave; block elimination and the two substitution scans in ELEMENT layout.
+// meth_dae_elem.h -- K8: the step controller of the DAE integrator (dae_integrate_with, shared by the one-wave and the two-wave
+// kernel), and the one-wave solver: one solve per wave; block elimination and the two substitution scans in ELEMENT layout.
 //
-// Measured on v2 (meth_dae_wave.h, cycle counters, tools/meth_dae_bench.py): 78 % of a solve is the three scans
+// Measured on the first wave-per-solve version (lane = node everywhere, since removed; cycle counters): 78 % of a solve is the three scans
 // over the 51 nodes (forward 35 %, factorisation 27 %, backward 16 %), and a scan step is ISSUE-bound: with
 // lane = node only ONE lane works on the 7x7 block of the current node, yet every wave64 FP64 instruction
 // occupies the SIMD for >= 4 cycles whatever the exec mask says (174 instructions = 886 cycles per forward step).
@@ -22,7 +23,7 @@
 //     sides) and come back the same way.
 // LDS per wave: differences array 8 x 7 x 51, L/U coefficients 51 x 24, staging 357 + 408 doubles = 38.8 KB, so four
 // waves (one per SIMD) still share a CU.  Time stepping, Newton control and error tests are those of meth_dae.h.
-// PARITY UNPINNED against the reference's IDA (see meth_dae.h); checked against v2, the CPU build and the CPU checker.
+// PARITY UNPINNED against the reference's IDA (see meth_dae.h); checked against the CPU build and the CPU checker.
 //
 // Round 4: TWO-ENDED elimination.  K8 is bound by dependent chains at one wave per SIMD (vector ALUs busy 44 % of the cycles,
 // profiles/r04_k8_oneway_pmc_sq_summary.json): a scan step waits ~13 cycles for every dependent FP64 operation while the issue slots
@@ -38,16 +39,12 @@
 // lane layout, and are written side by side in one basic block so that the compiler interleaves the two dependency chains.
 // Without pivoting the two-ended elimination is as accurate as the one-way one on this matrix (180 iteration matrices over
 // prior-box parameters, states along solves and c = 1e-5 .. 10: worst relative error 3.8e-10 for both against a pivoted dense
-// solve; the check is described in DESIGN.md 4.5).  SMC_K8_TWISTED=0 builds the one-way scans of rounds 1-3 (A/B).
+// solve; the check is described in DESIGN.md 4.5, its NumPy statement is tests/test_k8_two_ended_elimination.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "meth_dae.h"
 #include "meth_dae_wave.h"
-
-#ifndef SMC_K8_TWISTED
-#define SMC_K8_TWISTED 1
-#endif
 
 namespace smc {
 namespace meth {
@@ -167,16 +164,10 @@ struct ElemLane {   // lane = 8 r + c
     template <int Q> __device__ __forceinline__ int mc() const { return Q ? r : c; }   // block column
 };
 __device__ __forceinline__ int min6(int v) { return v < 6 ? v : 6; }
-__device__ __forceinline__ double ipow_small(double x, int n) {   // x^n, 1 <= n <= kNewtonMaxIter
-    double r = x;
-    for (int q = 1; q < n; ++q) r *= x;
-    return r;
-}
 
 // ---- control policy of the integrator (round 5; its CPU statement and the study behind it: the test checker's dae_policy,
 // tools/k8_policy_study.py) ----------------------------------------------------------------------------------------------
-// SMC_K8_POLICY 1 (default): IDA's policy for the iteration matrix and the Newton iteration, restated inside the
-// quasi-constant-step BDF (the reference integrates with IDA: methanation_set_likelihood.py:167-198; SUNDIALS IDA,
+// IDA's policy for the iteration matrix and the Newton iteration, restated inside the quasi-constant-step BDF (the reference integrates with IDA: methanation_set_likelihood.py:167-198; SUNDIALS IDA,
 // "Mathematical considerations", idaNls / idaNewtonIter / idaLsSolve):
 //   * the factored iteration matrix is kept while cj / cj_at_evaluation stays inside ((1 - xrate) / (1 + xrate), its reciprocal),
 //     xrate = SMC_K8_XRATE (IDA: 0.25; here 0.15, by measurement), and the Newton correction is scaled by 2 / (1 + cjratio); a Newton failure on a kept matrix repeats
@@ -186,11 +177,8 @@ __device__ __forceinline__ double ipow_small(double x, int n) {   // x^n, 1 <= n
 //     iteration also converges on |dy| <= 0.33e-4; rate = (|dy_m| / |dy_0|)^(1/m) > 0.9 ends the iteration as failed.
 // IDA's step-size rule (double at a factor >= 2, hold below that) was studied as well and is NOT adopted: in this formulation it
 // costs 30 % more steps (profiles/r05_k8_policy_study_cpu.txt).
-// SMC_K8_POLICY 0: rounds 1-4 (SciPy's bdf.py: matrix kept only while c is unchanged, convergence rate from two iterations of
-// the same step, newton_tol = 1e-3) - A/B builds.
-#ifndef SMC_K8_POLICY
-#define SMC_K8_POLICY 1
-#endif
+// Rounds 1-4 followed SciPy's bdf.py instead (matrix kept only while c is unchanged, convergence rate from two iterations of the
+// same step); that policy is still a setting of the CPU checker's dae_policy.
 #ifndef SMC_K8_XRATE
 #define SMC_K8_XRATE 0.15    // IDA's own window is 0.25; measured on one box (profiles/r05_ab_k8_policy.log): 2048 x 30 solves at
 #endif                       // 0.25 -> 137.8 k solves/s, 0.15 -> 145.1 k, 0.10 -> 141.8 k (rounds 1-4's policy: 103.8 k)
@@ -198,20 +186,12 @@ constexpr double kEpcon = 0.33, kRateMax = 0.9, kSsAfterSetup = 20.0, kSsAfterCj
 constexpr double kCjRatioLo = (1.0 - SMC_K8_XRATE) / (1.0 + SMC_K8_XRATE), kCjRatioHi = (1.0 + SMC_K8_XRATE) / (1.0 - SMC_K8_XRATE);
 // must the matrix evaluated at c_lu be evaluated again for an attempt with c?  (cj = 1 / c: cjratio = c_lu / c)
 __device__ __forceinline__ bool matrix_is_stale(double c, double c_lu) {
-#if SMC_K8_POLICY
     const double cjratio = c_lu / c;
     return !(cjratio > kCjRatioLo && cjratio < kCjRatioHi);
-#else
-    return c != c_lu;
-#endif
 }
 // scale of the Newton correction computed with the matrix of c_lu in an attempt with c (exactly 1 when c == c_lu)
 __device__ __forceinline__ double correction_scale(double c, double c_lu) {
-#if SMC_K8_POLICY
     return 2.0 / (1.0 + c_lu / c);
-#else
-    return 1.0;
-#endif
 }
 // IDA's convergence test after Newton iteration kk (0-based) with correction norm dy_norm: 1 converged, -1 failed, 0 go on
 __device__ __forceinline__ int newton_verdict_ida(int kk, double dy_norm, double &first, double &ss) {
@@ -241,62 +221,6 @@ __device__ __forceinline__ double recip1_short(double a) {
     const double x = __builtin_amdgcn_rcp(a);
     return fma(x, fma(-a, x, 1.0), x);
 }
-
-// one node of the block elimination; Q = I & 1
-template <int I>
-__device__ __forceinline__ bool elem_factor_node(const ElemLane &L, const double *cf, double (&X)[kNX], double (&G)[kNX]) {
-    constexpr int Q = I & 1;
-    const int mr = L.template mr<Q>(), mc = L.template mc<Q>();
-    const double *cfi = cf + I * kCfRow;
-    double a = X[I];
-    if (I > 0) {
-        constexpr int IP = (I > 0) ? I - 1 : 0;
-        const int kap = mr < 6 ? 6 : 5;
-        const int srcK = Q ? (kap * 8 + L.r) : (L.c * 8 + kap);   // holder of G_{I-1}[kap][mc] (parity 1-Q)
-        const double gT = __shfl(G[IP], L.c * 8 + L.r);            // G_{I-1}[mr][mc]
-        const double gK = __shfl(G[IP], srcK);
-        const double ld = cfi[min6(mr)], lx = cfi[8 + min6(mr)];
-        a = fma(-lx, gK, fma(-ld, gT, a));
-    }
-    int ok = 1;
-    const double rowsign = Q ? -1.0 : 1.0;
-    // The next pivot element always takes the generic update, so its reciprocal starts from `gen` and runs
-    // beside the selects and the pivot row / column exchange of the next round (two chains instead of one).
-    double akk = lane_bcast(a, 0);
-    SMC_UNROLL
-    for (int kk = 0; kk < 7; ++kk) {
-        if (!(fabs(akk) > 1e-300) || !(fabs(akk) < 1e300)) ok = 0;
-        const double p = recip1(akk);
-        const double u = __shfl(a, (L.lane & ~7) | kk);   // lane (r, k)
-        const double v = __shfl(a, kk * 8 + L.c);         // lane (k, c)
-        const double gen = fma(-(u * v), p, a);
-        akk = lane_bcast(gen, kk < 6 ? 9 * kk + 9 : 0);
-        const double ap = a * p * rowsign;
-        const bool rk = L.r == kk, ck = L.c == kk;
-        const double on_row = ck ? p : ap, off_row = ck ? -ap : gen;
-        a = rk ? on_row : off_row;
-    }
-    X[I] = a;
-    {
-        const int src6 = Q ? (48 + L.c) : ((L.lane & ~7) | 6);   // holder of X_I[mr][6]
-        const double tU = __shfl(a, src6);
-        const double ud = cfi[16 + min6(mc)], u65 = cfi[23];
-        G[I] = fma(a, ud, (mc == 5) ? tU * u65 : 0.0);
-    }
-    return ok != 0;
-}
-
-template <int I>
-struct ElemFactorLoop {
-    static __device__ __forceinline__ bool run(const ElemLane &L, const double *cf, double (&X)[kNX], double (&G)[kNX]) {
-        const bool below = ElemFactorLoop<I - 1>::run(L, cf, X, G);
-        return elem_factor_node<I>(L, cf, X, G) && below;
-    }
-};
-template <>
-struct ElemFactorLoop<-1> {
-    static __device__ __forceinline__ bool run(const ElemLane &, const double *, double (&)[kNX], double (&)[kNX]) { return true; }
-};
 
 // ---------------------------------------------------------------------------------------------
 // two-ended elimination: node pair (K, 50 - K) side by side; Q = K & 1 is the parity of both
@@ -329,7 +253,7 @@ __device__ __forceinline__ bool elem_factor_pair(const ElemLane &L, const double
             aB = fma(-cu, (mr == 6) ? h5 : hT, aB);
         }
     }
-    // two Gauss-Jordan inversions, pivot by pivot side by side (see elem_factor_node for the single form).  No test per pivot
+    // two Gauss-Jordan inversions, pivot by pivot side by side (elem_factor_middle has the single form).  No test per pivot
     // (two compares and the scalar bookkeeping per pivot and chain were a fifth of the loop): a vanishing pivot shows in the
     // inverse - its reciprocal sits on the diagonal, and 0 or a non-finite pivot turns the block into inf / NaN - and is caught
     // by one magnitude test per element at the end.
@@ -562,52 +486,11 @@ __device__ __forceinline__ bool elem_build_and_factor(int lane, double *lds, con
         }
     }
     SMC_PROF_ADD(st, 7);   // Jacobian blocks + transposition
-#if SMC_K8_TWISTED
     bool ok = ElemFactorPairLoop<kMid - 1>::run(L, cf, X, G);
     ok = elem_factor_middle(L, cf, X, G) && ok;
-#else
-    const bool ok = ElemFactorLoop<kNX - 1>::run(L, cf, X, G);
-#endif
     SMC_PROF_ADD(st, 0);   // block elimination
     return __all(ok);
 }
-
-// Forward scan, tail-recursive over the nodes: z_I = X_I (b_I - L_I z_{I-1}).  The right-hand side and the L
-// coefficients of node I+1 are loaded BEFORE z_I is stored (the compiler must assume the store aliases them, and an
-// LDS round trip on the chain costs as much as the butterfly).  Returns z_50[mr] on every lane.
-template <int I>
-struct ElemForward {
-    static __device__ __forceinline__ double run(const ElemLane &L, const double *cf, const double *b, double *z,
-                                                 const double (&X)[kNX], double zprev, double bI, double ldI, double lxI) {
-        constexpr int Q = I & 1, QN = 1 - Q, IN = (I + 1 < kNX) ? I + 1 : I;
-        const int mr = L.template mr<Q>(), mc = L.template mc<Q>();
-        const int mcn = min6(L.template mc<QN>());
-        const double bN = b[IN * 7 + mcn], ldN = cf[IN * kCfRow + mcn], lxN = cf[IN * kCfRow + 8 + mcn];
-        double t = bI;
-        if (I > 0) {
-            const double z6 = lane_bcast(zprev, Q ? 48 : 6), z5 = lane_bcast(zprev, Q ? 40 : 5);
-            const double zx = (mc == 6) ? z5 : z6;
-            t = fma(-lxI, zx, fma(-ldI, zprev, t));
-        }
-        const double zi = allsum_over_mc<Q>(X[I] * t);
-        z[I * kZRow + ((mc == 0 && mr < 7) ? mr : 7)] = zi;   // one unconditional store: no exec-mask round trip per step
-        if constexpr (I + 1 < kNX) return ElemForward<IN>::run(L, cf, b, z, X, zi, bN, ldN, lxN);
-        else return zi;
-    }
-};
-
-// Backward scan: x_I = z_I - G_I x_{I+1}, I = 49 .. 0; `xnext` is x_{I+1}[mc], zI = z_I[mr] (loaded one step ahead)
-template <int I>
-struct ElemBackward {
-    static __device__ __forceinline__ void run(const ElemLane &L, double *z, const double (&G)[kNX], double xnext, double zI) {
-        constexpr int Q = I & 1, QN = 1 - Q, IN = (I > 0) ? I - 1 : 0;
-        const int mr = L.template mr<Q>(), mc = L.template mc<Q>();
-        const double zN = z[IN * kZRow + min6(L.template mr<QN>())];
-        const double xi = zI - allsum_over_mc<Q>(G[I] * xnext);
-        z[I * kZRow + ((mc == 0 && mr < 7) ? mr : 7)] = xi;
-        if constexpr (I > 0) ElemBackward<IN>::run(L, z, G, xi, zN);
-    }
-};
 
 // one modified-Newton iteration; returns RMS(dy/scale) over all unknowns, or -1 if the residual is not finite
 __device__ __forceinline__ double elem_newton_iteration(int lane, double *lds, double *y, double *dd, const double *yp,
@@ -638,25 +521,15 @@ __device__ __forceinline__ double elem_newton_iteration(int lane, double *lds, d
     if (!__all(finite)) return -1.0;
     wave_lds_sync();
     SMC_PROF_ADD(st, 1);
-#if SMC_K8_TWISTED
     elem_solve_twisted(L, cf, b, z, X, G);
     SMC_PROF_ADD(st, 2);   // both scans (slot 3 stays empty)
-#else
-    const double zlast = ElemForward<0>::run(L, cf, b, z, X, 0.0, b[min6(L.c)], 0.0, 0.0);
-    SMC_PROF_ADD(st, 2);
-    ElemBackward<kNX - 2>::run(L, z, G, zlast, z[(kNX - 2) * kZRow + min6(L.template mr<(kNX - 2) & 1>())]);
-#endif
     wave_lds_sync();
     SMC_PROF_ADD(st, 3);
     double sumsq = 0.0;
     if (node)
         SMC_UNROLL
         for (int f = 0; f < 7; ++f) {
-#if SMC_K8_POLICY
             const double dx = z[lane * kZRow + f] * corr;      // matrix of another cj: 2 / (1 + cjratio)
-#else
-            const double dx = z[lane * kZRow + f];
-#endif
             const double sc = atol + rtol * fabs(yp[f]);
             // weights of a convergence norm: the reciprocal with two Newton steps (~1 ulp) instead of the IEEE division's
             // scaling / fix-up sequence (13 instructions per component and iteration; sc is within [atol, atol + rtol |y|])
@@ -714,12 +587,37 @@ __device__ __forceinline__ void elem_change_D(const DViewE &D, int order, double
     }
 }
 
-// Integrate one solve (the whole wave cooperates).  lds: this wave's region of kLdsDoubles doubles, holding y0 in
-// row 0 of the differences array and zeros in rows 1..7 on entry; the state at tf is left in row 0.
-__device__ __forceinline__ void dae_elem_integrate(double *lds, int lane, const double *p, double tf, double rtol,
-                                                   double atol, double h0, int max_attempts, DaeStats &st) {
-    const double newton_tol = fmax(10 * 2.220446049250313e-16 / rtol, fmin(0.03, sqrt(rtol)));   // SMC_K8_POLICY 0 only
-    (void)newton_tol;
+// The one-wave solver of the step controller below: the factors of all 51 nodes in this wave's registers, both elimination chains
+// in its one instruction stream.  It keeps the predictor of the attempt (the weights of the Newton norm are formed from it).
+struct ElemSolver {
+    double X[kNX], G[kNX], yp[7];
+    __device__ __forceinline__ void predictor_is(const double (&y)[7]) {
+        SMC_UNROLL
+        for (int f = 0; f < 7; ++f) yp[f] = y[f];
+    }
+    __device__ __forceinline__ bool build_and_factor(int lane, double *lds, const double *, const double *psi, const double *p,
+                                                     double c, DaeStats &st) {
+        return elem_build_and_factor(lane, lds, yp, psi, p, c, X, G, st);
+    }
+    __device__ __forceinline__ double newton_iteration(int lane, double *lds, double *y, double *dd, const double *psi,
+                                                       const double *p, double c, double corr, double rtol, double atol,
+                                                       DaeStats &st) {
+        return elem_newton_iteration(lane, lds, y, dd, yp, psi, p, c, corr, rtol, atol, X, G, st);
+    }
+};
+
+// Integrate one solve: THE step loop of K8 (predictor, reuse window of the iteration matrix, Newton verdict, error test, order
+// selection, elem_change_D).  The calling wave holds the 51 nodes (lane = node); what differs between the kernels is the Solver:
+// it owns the block factors and provides
+//   predictor_is(y)        the predictor of this attempt is y;
+//   build_and_factor(...)  evaluate the iteration matrix at the predictor and factor it; false: a singular block;
+//   newton_iteration(...)  one modified-Newton iteration; RMS(dy / scale) over all unknowns, or -1 if the residual is not finite;
+// ElemSolver (above) does all of it in the calling wave, SplitSolver (meth_dae_split.h) shares it with a second wave.
+// lds: the solve's region (kLdsDoubles / kLdsSplitDoubles doubles), holding y0 in row 0 of the differences array and zeros in rows
+// 1..7 on entry; the state at tf is left in row 0.
+template <class Solver>
+__device__ __forceinline__ void dae_integrate_with(double *lds, int lane, const double *p, double tf, double rtol, double atol,
+                                                   double h0, int max_attempts, DaeStats &st) {
     const bool node = lane < kNX;
     const DViewE D{lds + kLdsD, lane};
     st.steps = st.rejects = st.newton_fail = st.nlu = st.newton_iters = 0;
@@ -730,21 +628,19 @@ __device__ __forceinline__ void dae_elem_integrate(double *lds, int lane, const 
 #endif
     double t = 0.0, h_abs = h0;
     int order = 1, n_equal = 0, attempts = 0;
-    double X[kNX], G[kNX];
+    Solver S;
     bool lu_valid = false, force_rebuild = false;
     double c_lu = 0.0;
-    double ss = kSsAfterSetup, c_last = 0.0;   // SMC_K8_POLICY 1: the carried convergence-rate factor, c of the previous attempt
-    double yp[7], y[7], psi[7], dd[7];
+    double ss = kSsAfterSetup, c_last = 0.0;   // the carried convergence-rate factor, c of the previous attempt
+    double y[7], psi[7], dd[7];
     for (;;) {  // one iteration = one step attempt
         // The state that steers the attempt, pinned to scalars (meth_dae_wave.h: wave_uniform): the values are equal in all
         // lanes anyway; this tells the compiler, so that every branch below is a scalar branch taken by the whole wave.
         t = wave_uniform(t);
         h_abs = wave_uniform(h_abs);
         c_lu = wave_uniform(c_lu);
-#if SMC_K8_POLICY
         ss = wave_uniform(ss);
         c_last = wave_uniform(c_last);
-#endif
         order = __builtin_amdgcn_readfirstlane(order);
         n_equal = __builtin_amdgcn_readfirstlane(n_equal);
         attempts = __builtin_amdgcn_readfirstlane(attempts);
@@ -783,27 +679,26 @@ __device__ __forceinline__ void dae_elem_integrate(double *lds, int lane, const 
             const double inv_alpha = 1.0 / bdf_alpha(order);
             SMC_UNROLL
             for (int f = 0; f < 7; ++f) {
-                yp[f] = y[f] = s[f];
+                y[f] = s[f];
                 psi[f] = q[f] * inv_alpha;
                 dd[f] = 0.0;
             }
         }
-        // The factored iteration matrix is kept while it is not stale (matrix_is_stale: policy 1 - cj within (0.6, 1.67) of the
-        // cj it was evaluated with; policy 0 - c unchanged, bdf.py:343-357); rebuilt at the current predictor otherwise, or - by
-        // repeating this attempt - when Newton failed on a kept matrix.
+        S.predictor_is(y);
+        // The factored iteration matrix is kept while it is not stale (matrix_is_stale: cj within the SMC_K8_XRATE window of the
+        // cj it was evaluated with); rebuilt at the current predictor otherwise, or - by repeating this attempt - when Newton
+        // failed on a kept matrix.
         // (Rounds 2-4 tried the pieces of IDA's policy one at a time inside SciPy's control and dropped each: keeping the matrix
         // while c drifts cut the factorisations but raised SciPy-test Newton iterations 720 -> 913; the carried rate alone cut
         // the iterations 720 -> 435.  Together, with IDA's own convergence constant, they pay: CPU study, then the GPU A/B
         // in profiles/r05_ab_k8_policy.log.)
         const bool fresh = !lu_valid || force_rebuild || matrix_is_stale(c, c_lu);
-#if SMC_K8_POLICY
         if (c != c_last) ss = kSsAfterCjChange;
         c_last = c;
-#endif
         SMC_PROF_ADD(st, 6);
         if (fresh) {
             ++st.nlu;
-            lu_valid = elem_build_and_factor(lane, lds, yp, psi, p, c, X, G, st);
+            lu_valid = S.build_and_factor(lane, lds, y, psi, p, c, st);
             c_lu = c;
             force_rebuild = false;
             ss = kSsAfterSetup;
@@ -812,33 +707,16 @@ __device__ __forceinline__ void dae_elem_integrate(double *lds, int lane, const 
         int n_iter = 0;
         if (lu_valid) {
             const double corr = wave_uniform(correction_scale(c, c_lu));
-#if SMC_K8_POLICY
             double dy_first = 0.0;
 #pragma unroll 1
             for (int kk = 0; kk < kNewtonMaxIter; ++kk) {
-                const double dy_norm = elem_newton_iteration(lane, lds, y, dd, yp, psi, p, c, corr, rtol, atol, X, G, st);
+                const double dy_norm = S.newton_iteration(lane, lds, y, dd, psi, p, c, corr, rtol, atol, st);
                 n_iter = kk + 1;
                 ++st.newton_iters;
                 if (dy_norm < 0) break;
                 const int verdict = newton_verdict_ida(kk, dy_norm, dy_first, ss);
                 if (verdict != 0) { converged = verdict > 0; break; }
             }
-#else
-            // bdf.py:365-382
-            double dy_norm_old = -1.0;
-#pragma unroll 1
-            for (int kk = 0; kk < kNewtonMaxIter; ++kk) {
-                const double dy_norm = elem_newton_iteration(lane, lds, y, dd, yp, psi, p, c, corr, rtol, atol, X, G, st);
-                n_iter = kk + 1;
-                ++st.newton_iters;
-                if (dy_norm < 0) break;
-                const double rate = (dy_norm_old >= 0) ? dy_norm / dy_norm_old : -1.0;
-                const double scaled = dy_norm / (1 - rate);      // dy_norm / (1 - rate): shared by both tests (one division, not two)
-                if (rate >= 0 && (rate >= 1 || ipow_small(rate, kNewtonMaxIter - kk) * scaled > newton_tol)) break;
-                if (dy_norm == 0 || (rate >= 0 && rate * scaled < newton_tol)) { converged = true; break; }
-                dy_norm_old = dy_norm;
-            }
-#endif
         }
         SMC_PROF_ADD(st, 8);   // factorisation + Newton loop incl. control (slots 0,7,1,2,3 are inside)
         if (!converged && !fresh) {   // stale matrix: same step again with a fresh one

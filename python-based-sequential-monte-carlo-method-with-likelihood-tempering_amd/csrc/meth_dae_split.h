@@ -5,8 +5,8 @@
 // (profiles/r04_k8_pmc_sq_summary.json): a dependent FP64 instruction waits for its predecessor and nothing else is there to
 // issue.  The two-ended elimination of round 4 put two chains into the one instruction stream; they cost 1.5 - 1.7 x a single
 // chain, i.e. the stream is then mostly issue-bound - the second chain is not free.  Here the two chains get a wave each:
-//   wave 0 ("main"):   the integrator of v3 - predictor, residuals, norms, error tests over all 51 nodes (lane = node) - and the
-//                      downward chain 0 -> 24 with the middle node 25;
+//   wave 0 ("main"):   the step controller of meth_dae_elem.h (dae_integrate_with) - predictor, residuals, norms, error tests
+//                      over all 51 nodes (lane = node) - and the downward chain 0 -> 24 with the middle node 25;
 //   wave 1 ("server"): the upward chain 50 -> 26, on wave 0's commands (FACTOR: Jacobian blocks of nodes 26 .. 50 from the
 //                      differences array, transposition, elimination;  SOLVE: inward and outward scan of one right-hand side).
 // Each wave holds HALF of the factors (26 + 25 doubles per lane), which brings the kernel to 256 VGPRs: two waves per SIMD, eight
@@ -29,8 +29,8 @@
 // vector instructions of v3 and 6 % slower - with two waves per SIMD the instruction count is what matters.  Here wave 1 is
 // idle while wave 0 evaluates residuals and norms, and the SIMD's other wave has the issue slots.)
 // Arithmetic per node and per norm is that of the two-ended v3, operation by operation (the masked coefficient of the unified
-// chain step multiplies by an exact zero), so v4 reproduces v3 BIT FOR BIT (tools/meth_v3_check.py N v4 v3).  PARITY UNPINNED
-// against the reference's IDA like every K8 version (see meth_dae.h).
+// chain step multiplies by an exact zero), so v4 reproduces v3 BIT FOR BIT (tools/meth_v3_check.py, tests/test_gpu_methanation.py).
+// PARITY UNPINNED against the reference's IDA like every K8 version (see meth_dae.h).
 #pragma once
 #include <cstdlib>
 
@@ -433,11 +433,7 @@ __device__ __forceinline__ double split_newton_iteration(int lane, double *lds, 
     if (node)
         SMC_UNROLL
         for (int f = 0; f < 7; ++f) {
-#if SMC_K8_POLICY
             const double dx = z[lane * kZRow + f] * corr;      // matrix of another cj: 2 / (1 + cjratio)
-#else
-            const double dx = z[lane * kZRow + f];
-#endif
             const double sc = atol + rtol * fabs(y[f] - dd[f]);      // the predictor: y = yp + dd (kept as y and dd only - 14 VGPRs)
             const double q = dx * recip1(sc);
             sumsq += q * q;
@@ -468,210 +464,23 @@ __device__ __forceinline__ void dae_split_server(double *lds, int lane) {
     }
 }
 
-// Integrate one solve (wave 0; wave 1 is in dae_split_server).  lds: the workgroup's region of kLdsSplitDoubles doubles, holding
-// y0 in row 0 of the differences array, zeros in rows 1..7 and the parameters in the kLdsPar row on entry; the state at tf is
-// left in row 0.  Time stepping, Newton control and error tests: meth_dae_elem.h (dae_elem_integrate), line by line.
-__device__ __forceinline__ void dae_split_integrate(double *lds, int lane, const double *p, double tf, double rtol, double atol,
-                                                    double h0, int max_attempts, DaeStats &st) {
-    const double newton_tol = fmax(10 * 2.220446049250313e-16 / rtol, fmin(0.03, sqrt(rtol)));   // SMC_K8_POLICY 0 only
-    (void)newton_tol;
-    const bool node = lane < kNX;
-    const DViewE D{lds + kLdsD, lane};
-    st.steps = st.rejects = st.newton_fail = st.nlu = st.newton_iters = 0;
-    st.status = 0;
-#ifdef SMC_METH_PROFILE
-    for (int q = 0; q < 12; ++q) st.prof[q] = 0;
-    const long long prof_start_ = clock64();
-#endif
-    double t = 0.0, h_abs = h0;
-    int order = 1, n_equal = 0, attempts = 0;
+// Wave 0's solver of the step controller (meth_dae_elem.h: dae_integrate_with): the factors of its own chain and the middle node;
+// every factorisation and every linear solve starts with a command to wave 1.  The predictor is not kept: the Newton norm
+// reconstructs it as y - dd.
+struct SplitSolver {
     double X[kMid + 1], G[kMid];
-    bool lu_valid = false, force_rebuild = false;
-    double c_lu = 0.0;
-    double ss = kSsAfterSetup, c_last = 0.0;   // SMC_K8_POLICY 1 (meth_dae_elem.h): carried convergence-rate factor, c of the previous attempt
-    double y[7], psi[7], dd[7];
-    for (;;) {  // one iteration = one step attempt
-        t = wave_uniform(t);
-        h_abs = wave_uniform(h_abs);
-        c_lu = wave_uniform(c_lu);
-#if SMC_K8_POLICY
-        ss = wave_uniform(ss);
-        c_last = wave_uniform(c_last);
-#endif
-        order = __builtin_amdgcn_readfirstlane(order);
-        n_equal = __builtin_amdgcn_readfirstlane(n_equal);
-        attempts = __builtin_amdgcn_readfirstlane(attempts);
-        lu_valid = __builtin_amdgcn_readfirstlane((int)lu_valid) != 0;
-        force_rebuild = __builtin_amdgcn_readfirstlane((int)force_rebuild) != 0;
-        if (!(t < tf)) break;
-        if (h_abs < 1e-14 * fmax(1.0, t) || attempts >= max_attempts) { st.status = 1; break; }
-        ++attempts;
-        double t_new = t + h_abs;
-        if (t_new - tf > 0) {
-            t_new = tf;
-            { SMC_PROF_BEGIN(); elem_change_D(D, order, fabs(t_new - t) / h_abs, node); SMC_PROF_ADD(st, 5); }
-            n_equal = 0;
-        }
-        t_new = wave_uniform(t_new);
-        n_equal = __builtin_amdgcn_readfirstlane(n_equal);
-        const double h = t_new - t;
-        h_abs = fabs(h);
-        const double c = h / bdf_alpha(order);
-        SMC_PROF_BEGIN();
-        {
-            double s[7], q[7];
-            SMC_UNROLL
-            for (int f = 0; f < 7; ++f) s[f] = q[f] = 0.0;
-            if (node) {
-                SMC_UNROLL
-                for (int kk = 0; kk <= kMaxOrder; ++kk)
-                    if (kk <= order)
-                        SMC_UNROLL
-                        for (int f = 0; f < 7; ++f) {
-                            const double dv = D(kk, f);
-                            s[f] += dv;
-                            if (kk >= 1) q[f] += dv * bdf_gamma(kk);
-                        }
-            }
-            const double inv_alpha = 1.0 / bdf_alpha(order);
-            SMC_UNROLL
-            for (int f = 0; f < 7; ++f) {
-                y[f] = s[f];
-                psi[f] = q[f] * inv_alpha;
-                dd[f] = 0.0;
-            }
-        }
-        const bool fresh = !lu_valid || force_rebuild || matrix_is_stale(c, c_lu);
-#if SMC_K8_POLICY
-        if (c != c_last) ss = kSsAfterCjChange;
-        c_last = c;
-#endif
-        SMC_PROF_ADD(st, 6);   // predictor
-        if (fresh) {
-            ++st.nlu;
-            split_command(lds, kCmdFactor);
-            lu_valid = split_build_and_factor(0, lane, lds, y, psi, p, c, X, G, st);      // y is the predictor here
-            c_lu = c;
-            force_rebuild = false;
-            ss = kSsAfterSetup;
-        }
-        bool converged = false;
-        int n_iter = 0;
-        if (lu_valid) {
-            const double corr = wave_uniform(correction_scale(c, c_lu));
-#if SMC_K8_POLICY
-            double dy_first = 0.0;
-#pragma unroll 1
-            for (int kk = 0; kk < kNewtonMaxIter; ++kk) {
-                const double dy_norm = split_newton_iteration(lane, lds, y, dd, psi, p, c, corr, rtol, atol, X, G, st);
-                n_iter = kk + 1;
-                ++st.newton_iters;
-                if (dy_norm < 0) break;
-                const int verdict = newton_verdict_ida(kk, dy_norm, dy_first, ss);
-                if (verdict != 0) { converged = verdict > 0; break; }
-            }
-#else
-            double dy_norm_old = -1.0;
-#pragma unroll 1
-            for (int kk = 0; kk < kNewtonMaxIter; ++kk) {
-                const double dy_norm = split_newton_iteration(lane, lds, y, dd, psi, p, c, corr, rtol, atol, X, G, st);
-                n_iter = kk + 1;
-                ++st.newton_iters;
-                if (dy_norm < 0) break;
-                const double rate = (dy_norm_old >= 0) ? dy_norm / dy_norm_old : -1.0;
-                const double scaled = dy_norm / (1 - rate);
-                if (rate >= 0 && (rate >= 1 || ipow_small(rate, kNewtonMaxIter - kk) * scaled > newton_tol)) break;
-                if (dy_norm == 0 || (rate >= 0 && rate * scaled < newton_tol)) { converged = true; break; }
-                dy_norm_old = dy_norm;
-            }
-#endif
-        }
-        SMC_PROF_ADD(st, 8);   // factorisation + Newton loop incl. control
-        if (!converged && !fresh) {   // stale matrix: same step again with a fresh one
-            force_rebuild = true;
-            continue;
-        }
-        if (!converged) {
-            ++st.newton_fail;
-            lu_valid = false;
-            h_abs *= 0.5;
-            { SMC_PROF_BEGIN(); elem_change_D(D, order, 0.5, node); SMC_PROF_ADD(st, 5); }
-            n_equal = 0;
-            continue;
-        }
-        const double safety = 0.9 * (2 * kNewtonMaxIter + 1) / (2.0 * kNewtonMaxIter + n_iter);
-        double se = 0.0;
-        if (node)
-            SMC_UNROLL
-            for (int f = 0; f < 6; ++f) {
-                const double isc = recip1(atol + rtol * fabs(y[f]));
-                const double e = bdf_error_const(order) * dd[f] * isc;
-                se += e * e;
-            }
-        const double error_norm = sqrt(allsum_wave(se) / (6 * kNX));
-        if (!(error_norm <= 1)) {
-            ++st.rejects;
-            const double factor = (error_norm == error_norm) ? fmax(0.2, safety * pow(error_norm, -1.0 / (order + 1))) : 0.2;
-            h_abs *= factor;
-            { SMC_PROF_BEGIN(); elem_change_D(D, order, factor, node); SMC_PROF_ADD(st, 5); }
-            n_equal = 0;
-            continue;
-        }
-        SMC_PROF_ADD(st, 9);   // error test
-        ++n_equal;
-        t = t_new;
-        ++st.steps;
-        const bool select = n_equal >= order + 1;
-        double sm = 0.0, sp = 0.0;
-        if (node) {
-            double acc[7], d_order[7], dnew2[7];
-            SMC_UNROLL
-            for (int f = 0; f < 7; ++f) {
-                dnew2[f] = dd[f] - D(order + 1, f);
-                D(order + 2, f) = dnew2[f];
-                D(order + 1, f) = dd[f];
-                acc[f] = dd[f];
-                d_order[f] = 0.0;
-            }
-            SMC_UNROLL
-            for (int kk = kMaxOrder; kk >= 0; --kk)
-                if (kk <= order)
-                    SMC_UNROLL
-                    for (int f = 0; f < 7; ++f) {
-                        acc[f] += D(kk, f);
-                        D(kk, f) = acc[f];
-                        if (kk == order) d_order[f] = acc[f];
-                    }
-            if (select)
-                SMC_UNROLL
-                for (int f = 0; f < 6; ++f) {
-                    const double isc = recip1(atol + rtol * fabs(y[f]));
-                    if (order > 1) { const double e = bdf_error_const(order - 1) * d_order[f] * isc; sm += e * e; }
-                    if (order < kMaxOrder) { const double e = bdf_error_const(order + 1) * dnew2[f] * isc; sp += e * e; }
-                }
-        }
-        SMC_PROF_ADD(st, 10);  // D update + order-selection norms
-        if (!select) continue;
-        const double inf = __longlong_as_double(0x7ff0000000000000LL);
-        const double em_s = sqrt(allsum_wave(sm) / (6 * kNX)), ep_s = sqrt(allsum_wave(sp) / (6 * kNX));
-        const double em = (order > 1) ? em_s : inf;
-        const double ep = (order < kMaxOrder) ? ep_s : inf;
-        const double fm = pow(em, -1.0 / order), f0 = pow(error_norm, -1.0 / (order + 1)), fp = pow(ep, -1.0 / (order + 2));
-        double best = fm;
-        int delta = -1;
-        if (f0 > best) { best = f0; delta = 0; }
-        if (fp > best) { best = fp; delta = 1; }
-        order += delta;
-        const double factor = fmin(10.0, safety * best);
-        h_abs *= factor;
-        { SMC_PROF_BEGIN(); elem_change_D(D, order, factor, node); SMC_PROF_ADD(st, 5); }
-        n_equal = 0;
+    __device__ __forceinline__ void predictor_is(const double (&)[7]) {}
+    __device__ __forceinline__ bool build_and_factor(int lane, double *lds, const double *y, const double *psi, const double *p,
+                                                     double c, DaeStats &st) {
+        split_command(lds, kCmdFactor);
+        return split_build_and_factor(0, lane, lds, y, psi, p, c, X, G, st);      // y is the predictor here
     }
-    st.status = __builtin_amdgcn_readfirstlane(st.status);
-#ifdef SMC_METH_PROFILE
-    st.prof[4] = clock64() - prof_start_;
-#endif
-}
+    __device__ __forceinline__ double newton_iteration(int lane, double *lds, double *y, double *dd, const double *psi,
+                                                       const double *p, double c, double corr, double rtol, double atol,
+                                                       DaeStats &st) {
+        return split_newton_iteration(lane, lds, y, dd, psi, p, c, corr, rtol, atol, X, G, st);
+    }
+};
 
 }  // namespace meth
 }  // namespace smc

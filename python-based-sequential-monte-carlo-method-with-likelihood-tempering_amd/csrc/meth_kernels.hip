@@ -67,84 +67,6 @@ __global__ void loglike_kernel(const double *__restrict__ y, const double *__res
     lk[j] = total;
 }
 
-// K8: one thread per (particle, experiment) solve; the per-solve workspace is interleaved across the
-// `nslots` threads of the launch (element idx of slot s at ws[idx*nslots + s]) so that the 64 lanes of a wave,
-// which execute the same statement on 64 independent solves, touch 64 consecutive doubles.
-__global__ void __launch_bounds__(64)
-dae_kernel(double *__restrict__ wsbuf, int64_t nslots, const double *__restrict__ p0_all,
-           const double *__restrict__ y0_all, int64_t n_solves, double tf, double rtol, double atol, double h0,
-           int max_attempts, double S, double P_stp, double *__restrict__ flows, double *__restrict__ y_final,
-           int *__restrict__ status, unsigned long long *__restrict__ counters) {
-    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= nslots) return;
-    const Ws ws{wsbuf + slot, nslots};
-    for (int64_t sidx = slot; sidx < n_solves; sidx += nslots) {
-        double p[18];
-        for (int q = 0; q < 18; ++q) p[q] = p0_all[sidx * 18 + q];
-        for (int x = 0; x < kNS; ++x) ws(OFF_D + x) = y0_all[sidx * kNS + x];
-        for (int x = kNS; x < 8 * kNS; ++x) ws(OFF_D + x) = 0.0;
-        DaeStats st;
-        dae_integrate(ws, p, tf, rtol, atol, h0, max_attempts, st);
-        double F[5];
-        if (st.status == 0) {
-            outlet_flows(ws, p, S, P_stp, F);
-        } else {
-            for (int f = 0; f < 5; ++f) F[f] = -10000.0;  // the reference's failure sentinel (:244-249)
-        }
-        for (int f = 0; f < 5; ++f) flows[sidx * 5 + f] = F[f];
-        if (y_final)
-            for (int x = 0; x < kNS; ++x) y_final[sidx * kNS + x] = ws(OFF_D + x);
-        status[sidx] = st.status;
-        atomicAdd(&counters[0], (unsigned long long)st.steps);
-        atomicAdd(&counters[1], (unsigned long long)st.rejects);
-        atomicAdd(&counters[2], (unsigned long long)st.newton_fail);
-        atomicAdd(&counters[3], (unsigned long long)st.newton_iters);
-    }
-}
-
-// K8 v2: one wave per solve, lane = axial node (meth_dae_wave.h).  Persistent waves walk the solve list.
-__global__ void __launch_bounds__(64)
-dae_wave_kernel(const double *__restrict__ p0_all, const double *__restrict__ y0_all, int64_t n_solves, double tf,
-                double rtol, double atol, double h0, int max_attempts, double S, double P_stp,
-                double *__restrict__ flows, double *__restrict__ y_final, int *__restrict__ status,
-                unsigned long long *__restrict__ counters) {
-    extern __shared__ double sD[];  // 8 x 7 x 64
-    const int lane = threadIdx.x;
-    const DView D{sD, lane};
-    for (int64_t sidx = blockIdx.x; sidx < n_solves; sidx += gridDim.x) {
-        double p[18];
-        for (int q = 0; q < 18; ++q) p[q] = p0_all[sidx * 18 + q];
-        if (lane < kNX)
-            for (int f = 0; f < 7; ++f) {
-                D(0, f) = y0_all[sidx * kNS + f * kNX + lane];
-                for (int kk = 1; kk < 8; ++kk) D(kk, f) = 0.0;
-            }
-        DaeStats st;
-        dae_wave_integrate(sD, lane, p, tf, rtol, atol, h0, max_attempts, st);
-        if (lane == kNX - 1) {
-            const double u = D(0, 6), T = D(0, 5);
-            const double P_total = (p[0] + p[1] + p[2] + p[3] + p[4]) * k::R * p[5];
-            for (int f = 0; f < 5; ++f) {
-                const double cc = D(0, f);
-                flows[sidx * 5 + f] = (st.status == 0)
-                                          ? cc * S * u * 60 * k::R * T / (P_total) * 1e6 * (P_total) / P_stp * 298 / T
-                                          : -10000.0;
-            }
-            status[sidx] = st.status;
-            atomicAdd(&counters[0], (unsigned long long)st.steps);
-            atomicAdd(&counters[1], (unsigned long long)st.rejects);
-            atomicAdd(&counters[2], (unsigned long long)st.newton_fail);
-            atomicAdd(&counters[3], (unsigned long long)st.newton_iters);
-            atomicAdd(&counters[4], (unsigned long long)st.nlu);
-#ifdef SMC_METH_PROFILE
-            for (int q = 0; q < 12; ++q) atomicAdd(&counters[8 + q], (unsigned long long)st.prof[q]);
-#endif
-        }
-        if (y_final && lane < kNX)
-            for (int f = 0; f < 7; ++f) y_final[sidx * kNS + f * kNX + lane] = D(0, f);
-    }
-}
-
 // K8 v3: one wave per solve, scans in element layout (meth_dae_elem.h); solves are handed out by an atomic counter
 // (a failed solve runs its whole attempt budget, ~9x an ordinary one, so a static split leaves waves idle).
 __global__ void __launch_bounds__(64)
@@ -167,7 +89,7 @@ dae_elem_kernel(const double *__restrict__ p0_all, const double *__restrict__ y0
                 for (int kk = 1; kk < 8; ++kk) D(kk, f) = 0.0;
             }
         DaeStats st;
-        dae_elem_integrate(lds, lane, p, tf, rtol, atol, h0, max_attempts, st);
+        dae_integrate_with<ElemSolver>(lds, lane, p, tf, rtol, atol, h0, max_attempts, st);
         if (lane == kNX - 1) {
             const double u = D(0, 6), T = D(0, 5);
             const double P_total = (p[0] + p[1] + p[2] + p[3] + p[4]) * k::R * p[5];
@@ -193,7 +115,6 @@ dae_elem_kernel(const double *__restrict__ p0_all, const double *__restrict__ y0
     }
     if (split && lane == 0) atomicAdd(&counters[7], 1ULL);
 }
-
 
 // K8 v4: one solve per workgroup of two waves (meth_dae_split.h): wave 0 runs the integrator and the downward chain, wave 1 serves
 // the upward chain.  Wave 0 takes the solves from the atomic counter; wave 1 only ever sees commands.
@@ -223,7 +144,7 @@ dae_split_kernel(const double *__restrict__ p0_all, const double *__restrict__ y
                 for (int kk = 1; kk < 8; ++kk) D(kk, f) = 0.0;
             }
         DaeStats st;
-        dae_split_integrate(lds, lane, p, tf, rtol, atol, h0, max_attempts, st);
+        dae_integrate_with<SplitSolver>(lds, lane, p, tf, rtol, atol, h0, max_attempts, st);
         if (lane == kNX - 1) {
             const double u = D(0, 6), T = D(0, 5);
             const double P_total = (p[0] + p[1] + p[2] + p[3] + p[4]) * k::R * p[5];
@@ -342,17 +263,11 @@ int smc_meth_dae_host(int device, const double *p0_all, const double *y0_all, in
     MH(hipSetDevice(device));
     hipDeviceProp_t prop;
     MH(hipGetDeviceProperties(&prop, device));
-    const bool v1 = getenv("SMC_METH_DAE_V1") != nullptr;   // debug: the thread-per-solve version (meth_dae.h)
-    const bool v2 = getenv("SMC_METH_DAE_V2") != nullptr;   // debug: lane = node scans (meth_dae_wave.h)
-    const bool v4 = smc::meth_split_enabled();               // two waves per solve (meth_dae_split.h)
+    const bool two_waves = smc::meth_split_enabled();        // two waves per solve (meth_dae_split.h), or one (meth_dae_elem.h)
     const int budget = getenv("SMC_METH_MAX_ATTEMPTS") ? atoi(getenv("SMC_METH_MAX_ATTEMPTS")) : kDaeMaxAttempts;
-    int64_t nslots = ((n_solves + 63) / 64) * 64;
-    const int64_t max_slots = (int64_t)prop.multiProcessorCount * 256;   // 4 waves per CU
-    if (nslots > max_slots) nslots = max_slots;
-    double *dws = nullptr, *dp, *dy0, *dfl, *dyf = nullptr;
+    double *dp, *dy0, *dfl, *dyf = nullptr;
     int *dst;
     unsigned long long *dcnt;
-    if (v1) { MH(hipMalloc(&dws, (size_t)nslots * kWsDoubles * sizeof(double))); bufs.push_back(dws); }
     MH(hipMalloc(&dp, (size_t)n_solves * 18 * 8)); bufs.push_back(dp);
     MH(hipMalloc(&dy0, (size_t)n_solves * kNS * 8)); bufs.push_back(dy0);
     MH(hipMalloc(&dfl, (size_t)n_solves * 5 * 8)); bufs.push_back(dfl);
@@ -366,10 +281,7 @@ int smc_meth_dae_host(int device, const double *p0_all, const double *y0_all, in
     MH(hipEventCreate(&e0));
     MH(hipEventCreate(&e1));
     MH(hipEventRecord(e0, 0));
-    if (v1) {
-        hipLaunchKernelGGL(dae_kernel, dim3((unsigned)(nslots / 64)), dim3(64), 0, 0, dws, nslots, dp, dy0, n_solves, tf,
-                           rtol, atol, h0, budget, S, P_stp, dfl, dyf, dst, dcnt);
-    } else if (v4 && !v2) {
+    if (two_waves) {
         const int gpc = getenv("SMC_METH_WAVES_PER_CU") ? atoi(getenv("SMC_METH_WAVES_PER_CU")) : 4;   // workgroups (solves) per CU
         int64_t ngroups = (int64_t)prop.multiProcessorCount * (gpc >= 1 && gpc <= 4 ? gpc : 4);
         if (ngroups > n_solves) ngroups = n_solves;
@@ -382,18 +294,13 @@ int smc_meth_dae_host(int device, const double *p0_all, const double *y0_all, in
         }
         hipLaunchKernelGGL(dae_split_kernel, dim3((unsigned)ngroups), dim3(kSplitThreads), kLdsSplitDoubles * sizeof(double), 0, dp,
                            dy0, n_solves, tf, rtol, atol, h0, budget, S, P_stp, dfl, dyf, dst, dcnt, smc::meth_split_role_policy());
-    } else if (!v2) {
+    } else {
         // one wave per SIMD is all that fits (512 VGPRs and 38.8 KB of LDS per wave); SMC_METH_WAVES_PER_CU < 4 thins the grid
         // for the occupancy-scaling measurement of profiles/r02_k8_occupancy.md
         const int wpc = getenv("SMC_METH_WAVES_PER_CU") ? atoi(getenv("SMC_METH_WAVES_PER_CU")) : 4;
         int64_t nwaves = (int64_t)prop.multiProcessorCount * (wpc >= 1 && wpc <= 4 ? wpc : 4);
         if (nwaves > n_solves) nwaves = n_solves;
         hipLaunchKernelGGL(dae_elem_kernel, dim3((unsigned)nwaves), dim3(64), kLdsDoubles * sizeof(double), 0, dp, dy0,
-                           n_solves, tf, rtol, atol, h0, budget, S, P_stp, dfl, dyf, dst, dcnt);
-    } else {
-        int64_t nwaves = (int64_t)prop.multiProcessorCount * 4;
-        if (nwaves > n_solves) nwaves = n_solves;
-        hipLaunchKernelGGL(dae_wave_kernel, dim3((unsigned)nwaves), dim3(64), 8 * 7 * 64 * sizeof(double), 0, dp, dy0,
                            n_solves, tf, rtol, atol, h0, budget, S, P_stp, dfl, dyf, dst, dcnt);
     }
     MH(hipGetLastError());
@@ -411,8 +318,8 @@ int smc_meth_dae_host(int device, const double *p0_all, const double *y0_all, in
         unsigned long long h[8];
         MH(hipMemcpy(h, dcnt, sizeof h, hipMemcpyDeviceToHost));
         if (stats)
-            for (int q = 0; q < 5; ++q) stats[q] = (int64_t)h[q];     // [4]: factorisations (0 from the debug kernels v1 / v2)
-        if (!v1 && !v2 && (h[6] != (unsigned long long)n_solves || h[7] != 0)) {   // every solve exactly once, whole waves only
+            for (int q = 0; q < 5; ++q) stats[q] = (int64_t)h[q];     // [4]: factorisations
+        if (h[6] != (unsigned long long)n_solves || h[7] != 0) {   // every solve exactly once, whole waves only
             g_meth_err = "dae_elem_kernel: " + std::to_string(h[6]) + " of " + std::to_string(n_solves) +
                          " solves finished, " + std::to_string(h[7]) + " waves split at a dequeue";
             for (void *q : bufs) (void)hipFree(q);

@@ -1,7 +1,7 @@
 // meth_smc.hip -- the methanation model inside the SMC loop (configs 4-5): likelihood sweep and Metropolis
 // iteration on the resident particle sets.  Same three-stage shape as the Michaelis-Menten sweep
 // (mm_kernels.hip): propose -> solve -> accept, where "solve" is K8, the DAE time integration of every
-// (particle, experiment) pair (meth_dae_wave.h; PARITY UNPINNED against the reference's IDA), followed by
+// (particle, experiment) pair (meth_dae_elem.h, meth_dae_split.h; PARITY UNPINNED against the reference's IDA), followed by
 // my_loglike (methanation_set_likelihood.py:280-300) per particle.
 //   sim_particle / cal_parallel_new   methanation_functions.py:44-92
 //   MH iteration                       SMC_methanation_main.py:295-391 (the taken branch: normal_pred False)
@@ -217,7 +217,7 @@ meth_particles_dae_kernel(MethModel m, const double *__restrict__ theta, int64_t
                 for (int kk = 1; kk < 8; ++kk) D(kk, f) = 0.0;
             }
         DaeStats st;
-        dae_elem_integrate(lds, lane, p, m.tf, m.rtol, m.atol, m.h0, kDaeMaxAttempts, st);
+        dae_integrate_with<ElemSolver>(lds, lane, p, m.tf, m.rtol, m.atol, m.h0, kDaeMaxAttempts, st);
         if (lane == kNX - 1) {
             const double u = D(0, 6), T = D(0, 5);
             const double P_total = (p[0] + p[1] + p[2] + p[3] + p[4]) * k::R * p[5];
@@ -297,7 +297,7 @@ meth_particles_dae_split_kernel(MethModel m, const double *__restrict__ theta, i
                 for (int kk = 1; kk < 8; ++kk) D(kk, f) = 0.0;
             }
         DaeStats st;
-        dae_split_integrate(lds, lane, p, m.tf, m.rtol, m.atol, m.h0, kDaeMaxAttempts, st);
+        dae_integrate_with<SplitSolver>(lds, lane, p, m.tf, m.rtol, m.atol, m.h0, kDaeMaxAttempts, st);
         if (lane == kNX - 1) {
             const double u = D(0, 6), T = D(0, 5);
             const double P_total = (p[0] + p[1] + p[2] + p[3] + p[4]) * k::R * p[5];

@@ -55,7 +55,7 @@ def test_tolerance_refinement_and_steady_state(M, setup, i):
 
 @pytest.mark.parametrize("i", [0, 7, 19, 29])
 def test_k8_control_policy_against_the_checker(M, setup, i):
-    """Round 5: K8 follows IDA's policy for the iteration matrix and the Newton iteration (csrc/meth_dae_elem.h, SMC_K8_POLICY 1;
+    """Round 5: K8 follows IDA's policy for the iteration matrix and the Newton iteration (csrc/meth_dae_elem.h, dae_integrate_with;
     stated on the CPU by dae_policy {2, 1, 0, 0.33, 0.15}).  Same equations, same tolerances, same step-size control: the outlet
     state stays within a few tolerance units of the checker's default policy (matrix at every attempt, SciPy's Newton test) and of
     a 1e-9 run, with a fraction of the factorisations and fewer than two Newton iterations per attempt."""

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Generic A/B runner (round 5; replaces the one-off ab_*.sh / k8_*.sh / r04_*.sh wrappers of rounds 2-4): runs ONE command REPS
 # times for each library, alternating between the libraries, on the box it is started on, and keeps every output.
-#   tools/ab_build.sh k8p0 -DSMC_K8_POLICY=0                         # a variant build under build/ab/<name>/
-#   tools/ab_run.sh gpurun_out/myab 2 "python3 tools/meth_dae_bench.py 512 2048" tree k8p0
+#   tools/ab_build.sh k8x25 -DSMC_K8_XRATE=0.25                      # a variant build under build/ab/<name>/
+#   tools/ab_run.sh build/myab_logs 2 "python3 tools/meth_dae_bench.py 512 2048" tree k8x25
 # `tree` = the in-tree libsmc_hip.so; any other name = build/ab/<name>/libsmc_hip.so (handed over through SMC_HIP_LIB).
 set -u
 out=$1; reps=$2; cmd=$3; shift 3
