@@ -152,6 +152,32 @@ int smc_set_model_user3(smc_ctx *ctx, const char *source, int n_states, int n_ob
                         double rtol, double atol, int method);
 int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap);
 int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir);
+/* A NOISE MODEL: a noise level per output, and noise that grows with the signal (additive; the functions above keep their
+ * behaviour).  Data, source and obs_scale as smc_set_model_user3.  Output k has an additive level a_k and a proportional
+ * coefficient b_k, each one of the particle's parameters or a fixed number: add_index[k] is a parameter number in [0, dim), or
+ * -1 for add_fixed[k], which must then be finite and > 0; prop_index / prop_fixed in the same way with prop_fixed[k] >= 0; NULL
+ * for both means no proportional part.  Several outputs may name one parameter.  With f_ik the model's output and s_k = obs_scale:
+ *   sd_ik^2 = (a_k s_k)^2 + (b_k f_ik)^2
+ *   logL    = sum over observed (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ]
+ * (any a_k <= 0 or b_k < 0: -inf; an experiment without an observation adds 0; NaN and ragged rows as smc_set_model_user3).
+ * Exact early rejection applies: the kernels accumulate the excess of every term over its floor log(a_k s_k).
+ * smc_user_predict, smc_user_predict_at and smc_user_predict_summary work as for every user model; the summary's noise != 0
+ * draws pred + sd_ik z with the particle's own a_k, b_k and prediction.  A specification that is the model of
+ * smc_set_model_user3 - no proportional part and every add_index dim - 1, or every output fixed to one value - takes that
+ * function's path and gives its bits.  Everything else that breaks a rule, and a data set whose image (40 + 8 n_ex words larger
+ * than smc_set_model_user3's) exceeds the LDS table, fails with the reason (for the table: bytes needed and available).
+ * Limits: model constants and noise parameters together number at most SMC_MAX_DIM; a purely proportional model (a_k = 0) does
+ * not exist - the floor needs a_k > 0 - and a small fixed a_k stands in for it.
+ * smc_user_noise_check applies the rules of the specification alone (no GPU, no context: the reason is in smc_last_error(NULL)).
+ * check4 / dump_source4: as check3 / dump_source3 for the source of a noise model, `proportional` != 0 with the proportional
+ * part compiled in (one log1p and one division per observed value; without it neither is compiled). */
+int smc_set_model_user4(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                        const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
+                        const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method);
+int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double *add_fixed, const int *prop_index,
+                         const double *prop_fixed);
+int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap);
+int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir);
 /* Model PREDICTIONS of a user model (any of the three set functions; RK45 or BDF), for n host particles (n x dim, AoS; any n -
  * run in chunks of n_local): lk[n] as smc_loglik computes it and, unless pred is NULL, pred[((p * n_ex + e) * n_t + i) * n_obs + k]
  * = output k at t[e][i], written for every finite time whether or not obs is measured there; NaN past a row's end and from

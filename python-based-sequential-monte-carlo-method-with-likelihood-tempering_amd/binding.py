@@ -65,6 +65,11 @@ SIGNATURES = {
                                     cint]),
     "smc_user_model_check3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source3": (cint, [ctypes.c_char_p, cint, cint, cint, cint, ctypes.c_char_p]),
+    "smc_set_model_user4": (cint, [c_ctx, ctypes.c_char_p, cint, cint, c_dp, c_dp, c_dp, c_dp, cint, cint, cint, c_ip, c_dp, c_ip, c_dp,
+                                    f64, f64, cint]),
+    "smc_user_noise_check": (cint, [cint, cint, c_ip, c_dp, c_ip, c_dp]),
+    "smc_user_model_check4": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, ctypes.c_char_p, cint]),
+    "smc_user_model_dump_source4": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, ctypes.c_char_p]),
     "smc_user_predict": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_at": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, cint, cint, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_summary": (cint, [c_ctx, cint, c_dp, c_dp, cint, cint, c_dp, cint, cint, u64, i64, ctypes.c_size_t, c_dp, c_dp,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "predictive_select.h"
+#include "user_obs_args.h"   // UserNoise
 
 struct smc_ctx;
 
@@ -26,6 +27,9 @@ struct PredSummaryArgs {
     int dim, est_sigma;
     double sigma_fixed;
     double scale[8];
+    // ... under a noise model (has_noise_model != 0): value = pred + sd z, sd^2 = (a_k s_k)^2 + (b_k pred)^2 with the particle's a_k, b_k
+    int has_noise_model;
+    UserNoise nz;
     uint64_t seed;
     int64_t global_offset;
     // order statistics

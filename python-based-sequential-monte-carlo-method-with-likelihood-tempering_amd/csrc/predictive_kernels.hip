@@ -40,7 +40,15 @@ __global__ void __launch_bounds__(256) pred_keys_kernel(const PredSummaryArgs a)
                 const u32x4 q = philox_block(a.seed, (uint64_t)(a.global_offset + p), (0x505245ull << 32) | (uint64_t)cell, 0);
                 const double u1 = 1.0 - u01_from(q.x, q.y), u2 = u01_from(q.z, q.w);
                 const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-                v = v + (sigma * a.scale[c % a.n_obs]) * z;
+                if (a.has_noise_model) {
+                    const int k = c % a.n_obs;
+                    const double ak = a.nz.add_index[k] >= 0 ? a.theta[(int64_t)a.nz.add_index[k] * a.stride + p] : a.nz.add_fixed[k];
+                    const double bk = !a.nz.prop ? 0.0 : (a.nz.prop_index[k] >= 0 ? a.theta[(int64_t)a.nz.prop_index[k] * a.stride + p] : a.nz.prop_fixed[k]);
+                    const double as = ak * a.nz.scale[k], bf = bk * v;
+                    v = v + sqrt(as * as + bf * bf) * z;
+                } else {
+                    v = v + (sigma * a.scale[c % a.n_obs]) * z;
+                }
             }
             key = smc_sel::key_of(v);
         }

@@ -96,6 +96,56 @@ user_finish_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, 
     if (attempts) atomicAdd(&counters->rk_attempts, attempts);
 }
 
+// ... under a noise model (smc_set_model_user4; user_obs_args.h): the items hold the excess sums X_e over the floors,
+//   lk = sum_e [ (-m_e / 2) log(2 pi) - sum_k m_ek log(a_k s_k) - X_e ],     -inf if any a_k <= 0 or any b_k < 0.
+// me: m_e; mek: [8 e + k].  The early-rejection bound of the run-time compiled kernels (smc_obs::noise_floor_of) evaluates the
+// bracket in this order, every product and difference rounded on its own.
+__global__ void __launch_bounds__(256)
+user_finish_noise_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, uint8_t *__restrict__ p0mask,
+                         const double *__restrict__ sum_x, const int *__restrict__ info, int n_ex, int n_obs,
+                         const double *__restrict__ me, const double *__restrict__ mek, const UserNoise nz,
+                         double *__restrict__ lk_out, SweepCounters *__restrict__ counters) {
+    unsigned long long attempts = 0, failed = 0;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const bool masked = p0mask && p0mask[p] == 0;
+        if (masked) continue;
+        double la[kUserMaxObs];
+        bool ok = true;
+        for (int k = 0; k < n_obs; ++k) {
+            const double a = nz.add_index[k] >= 0 ? theta[(int64_t)nz.add_index[k] * stride + p] : nz.add_fixed[k];
+            const double b = !nz.prop ? 0.0 : (nz.prop_index[k] >= 0 ? theta[(int64_t)nz.prop_index[k] * stride + p] : nz.prop_fixed[k]);
+            ok = ok && a > 0.0 && b >= 0.0;
+            la[k] = log(a * nz.scale[k]);
+        }
+        if (!ok) {
+            lk_out[p] = -__longlong_as_double(0x7ff0000000000000LL);
+            continue;
+        }
+        double lk = 0.0;
+        unsigned pf = 0, cancelled = 0;
+        for (int e = 0; e < n_ex; ++e) {
+            double c0 = (-0.5 * me[e]) * 1.8378770664093453;      // log(2 pi)
+            for (int k = 0; k < n_obs; ++k) {
+                const double term = mek[8 * e + k] * la[k];
+                c0 = c0 - term;
+            }
+            lk += c0 - sum_x[(int64_t)e * n + p];
+            const int fl = info[(int64_t)e * n + p];
+            attempts += (unsigned)(fl & 0x1fffffff);
+            pf |= (unsigned)(fl >> 30) & 1u;
+            cancelled |= (unsigned)(fl >> 29) & 1u;
+        }
+        failed += pf;
+        if (cancelled) {
+            lk = __longlong_as_double(0x7ff8000000000000LL);
+            if (p0mask) p0mask[p] = 2;
+        }
+        lk_out[p] = lk;
+    }
+    if (failed) atomicAdd(&counters->n_failed, failed);
+    if (attempts) atomicAdd(&counters->rk_attempts, attempts);
+}
+
 // BDF models: the per-item work counters of a sweep summed into four totals (smc_user_sweep_counters); masked proposals
 // (not solved: their items may hold an earlier sweep's counts) are left out
 __global__ void __launch_bounds__(256)
@@ -151,6 +201,9 @@ struct UserModel {
     // what a design other than the data's needs again on the host (smc_user_predict_at, smc_user_predict_summary)
     std::vector<double> h_t, h_cond;
     double scale[kUserMaxObs] = {1, 1, 1, 1, 1, 1, 1, 1};
+    // smc_set_model_user4: the noise model (user_obs_args.h); d_const then holds m_e, sum log s_k and m_ek [8 n_ex]
+    bool noise = false;
+    UserNoise nz{};
 };
 
 // an optional ingredient (smc_user_cost, smc_user_jac, smc_user_obs_vec; smc_div): a source that mentions it must define it
@@ -160,12 +213,14 @@ static bool mentions(const char *user_source, const char *name) { return strstr(
 // text, and the method's kernel file.  n_obs = 0: the one-output source of smc_set_model_user / 2.  n_obs >= 1: the
 // multi-output source (smc_set_model_user3) - SMC_USER_NOBS selects the kernel file's multi-output blocks, and the file is
 // appended twice: the sweep kernel, then with SMC_USER_PRED 1 the prediction kernel smc_user_predict_kernel.
-static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs) {
+static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs, int noise = 0) {
     const bool bdf = method == SMC_USER_METHOD_BDF;
     std::string s = "#define SMC_USER_NS " + std::to_string(n_states) + "\n#define SMC_USER_DIM " + std::to_string(dim) + "\n";
     if (n_obs > 0)
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
              ((n_obs > 1 || mentions(user_source, "smc_user_obs_vec")) ? "1\n" : "0\n");
+    // smc_set_model_user4: the SMC_USER_NOISE blocks of the kernel files and of user_obs_args.h (noise = 2: with log1p and the division)
+    if (n_obs > 0 && noise > 0) s += std::string("#define SMC_USER_NOISE 1\n#define SMC_USER_NOISE_PROP ") + (noise > 1 ? "1\n" : "0\n");
     if (mentions(user_source, "smc_user_cost")) s += "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n";
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
     if (!bdf) s += mentions(user_source, "smc_div") ? "#define SMC_USER_USES_DIV 1\n" : "#define SMC_USER_USES_DIV 0\n";
@@ -187,8 +242,8 @@ static int user_header_count(int n_obs) { return (int)(sizeof kUserHeaders / siz
 
 // compile build_source(...) for gfx950; on failure `log` holds hiprtc's diagnostics
 static bool compile_user(const char *user_source, int n_states, int dim, int method, int n_obs, std::vector<char> &code,
-                         std::string &log) {
-    const std::string src = build_source(user_source, n_states, dim, method, n_obs);
+                         std::string &log, int noise = 0) {
+    const std::string src = build_source(user_source, n_states, dim, method, n_obs, noise);
     hiprtcProgram prog;
     const char *headers[8], *names[8];
     const int n_headers = user_header_count(n_obs);
@@ -249,9 +304,10 @@ static size_t user_lds_bytes(int n_states, int n_ex, int n_t) {
     return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)2 * n_ex * (n_t + 1)) * sizeof(double);
 }
 // ... of the multi-output kernels: the pools, then the image of user_obs_args.h
-static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs) {
-    return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)obs_table_at(n_ex) + (size_t)n_ex * (n_t + 1) * obs_rec_words(n_obs)) *
-           sizeof(double);
+// (noise: plus the noise block of a model of smc_set_model_user4)
+static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs, bool noise = false) {
+    return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)obs_table_at(n_ex) + (size_t)n_ex * (n_t + 1) * obs_rec_words(n_obs) +
+            (noise ? (size_t)obs_noise_words(n_ex) : 0)) * sizeof(double);
 }
 static const size_t kUserLdsCap = 150 * 1024;
 
@@ -288,7 +344,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const bool multi = u->multi || pred;
-    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
+    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
     if (lists) {
         u->parity ^= 1;
         UserScanArgs sa{};
@@ -347,9 +403,13 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
         }
     }
     const int64_t g = (n + 255) / 256;
-    hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
-                       c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
-                       lk, c->d_counters);
+    if (u->noise)
+        hipLaunchKernelGGL(user_finish_noise_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
+                           p0mask, u->d_sum, u->d_info, u->n_ex, u->n_obs, u->d_const, u->d_const + 2 * u->n_ex, u->nz, lk, c->d_counters);
+    else
+        hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
+                           c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
+                           lk, c->d_counters);
     if (u->method == SMC_USER_METHOD_BDF) {
         if (!pred) (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
         const int64_t items = n * u->n_ex, gb = (items + 255) / 256;
@@ -415,10 +475,32 @@ static std::string obs_layout(const double *t, const double *obs, const double *
 }
 
 // the LDS image of user_obs_args.h for data obs_layout has accepted
+// m_ek [8 e + k]: the finite observations of output k at the finite times of experiment e
+static std::vector<double> count_mek(const double *t, const double *obs, int n_ex, int n_t, int n_obs) {
+    std::vector<double> mek(8 * (size_t)n_ex, 0.0);
+    for (int e = 0; e < n_ex; ++e)
+        for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
+            for (int k = 0; k < n_obs; ++k)
+                if (!std::isnan(obs[((size_t)e * n_t + i) * n_obs + k])) mek[8 * (size_t)e + k] += 1.0;
+    return mek;
+}
+
 static std::vector<double> build_obs_image(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
-                                           const std::vector<double> &me, const std::vector<double> &ls) {
+                                           const std::vector<double> &me, const std::vector<double> &ls, const UserNoise *nz = nullptr) {
     const int R = obs_rec_words(n_obs), at = obs_table_at(n_ex);
-    std::vector<double> img((size_t)at + (size_t)n_ex * (n_t + 1) * R, 0.0);
+    std::vector<double> img((size_t)at + (size_t)n_ex * (n_t + 1) * R + (nz ? (size_t)obs_noise_words(n_ex) : 0), 0.0);
+    if (nz) {      // the noise block (user_obs_args.h)
+        double *b = img.data() + obs_noise_at(n_ex, n_t, n_obs);
+        for (int k = 0; k < kUserMaxObs; ++k) {
+            b[k] = k < n_obs ? (double)nz->add_index[k] : -1.0;
+            b[8 + k] = k < n_obs ? nz->add_fixed[k] : 1.0;
+            b[16 + k] = (k < n_obs && nz->prop) ? (double)nz->prop_index[k] : -1.0;
+            b[24 + k] = (k < n_obs && nz->prop) ? nz->prop_fixed[k] : 0.0;
+            b[32 + k] = k < n_obs ? nz->scale[k] : 1.0;
+        }
+        const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs);
+        std::copy(mek.begin(), mek.end(), b + kNoiseHdr);
+    }
     for (int k = 0; k < kObsHdrMe; ++k) img[k] = (scale && k < n_obs) ? 1.0 / scale[k] : 1.0;
     for (int e = 0; e < n_ex; ++e) {
         img[kObsHdrMe + e] = me[e];
@@ -443,7 +525,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
 
 // occupancy and LDS limit of the prediction kernel (u->fn_pred)
 static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
-    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs);
+    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise);
     int nb = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu_pred = nb;
     if (lds > 48 * 1024 &&
@@ -493,10 +575,11 @@ struct DesignGroup {
 
 // experiments [e0, e0 + g) of the design (t: rows of n_t times, cond: rows of n_cond numbers) as a bundle on the device
 static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const double *t, const double *cond, int e0, int g, int n_t) {
-    const std::vector<double> nan_obs((size_t)g * n_t * u->n_obs, std::nan("")), zero(2 * (size_t)g, 0.0);
+    const std::vector<double> nan_obs((size_t)g * n_t * u->n_obs, std::nan("")), zero((u->noise ? 10 : 2) * (size_t)g, 0.0);
     std::vector<double> me, ls;
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
-    const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls);
+    const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls,
+                                                    u->noise ? &u->nz : nullptr);
     const size_t nc = (size_t)g * (u->n_cond > 0 ? u->n_cond : 1) * sizeof(double);
     dg.e0 = e0;
     dg.n_ex = g;
@@ -508,7 +591,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
               hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && u->n_cond > 0)
         ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * u->n_cond, nc, hipMemcpyHostToDevice) == hipSuccess;
-    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs);
+    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs, u->noise);
     int nb = 0;
     if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
     (void)c;
@@ -540,7 +623,7 @@ struct DesignScope {
 // the largest run of experiments whose image fits the LDS cap (0: not even one row)
 static int design_lds_group(const UserModel *u, int n_ex, int n_t) {
     int g = 0;
-    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs) <= kUserLdsCap) ++g;
+    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs, u->noise) <= kUserLdsCap) ++g;
     return g;
 }
 
@@ -586,11 +669,11 @@ static bool user_source_args_ok(const char *source, int n_states, int dim, int m
            (n_obs == 0 || user_obs_ok(n_obs));
 }
 
-static int user_model_check_impl(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap) {
+static int user_model_check_impl(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap, int noise = 0) {
     if (!user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
     std::vector<char> code;
     std::string lg;
-    const bool ok = compile_user(source, n_states, dim, method, n_obs, code, lg);
+    const bool ok = compile_user(source, n_states, dim, method, n_obs, code, lg, noise);
     if (log && log_cap > 0) {
         strncpy(log, lg.c_str(), (size_t)log_cap - 1);
         log[log_cap - 1] = 0;
@@ -607,11 +690,14 @@ int smc_user_model_check2(const char *source, int n_states, int dim, int method,
 int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap) {
     return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap);
 }
+int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap) {
+    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, proportional ? 2 : 1);
+}
 
 // everything hiprtc would read, as files: `hipcc -I <dir>` compiles <dir>/smc_user_model.hip off line
-static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir) {
+static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0) {
     if (!dir || !user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
-    const std::string src = build_source(source, n_states, dim, method, n_obs);
+    const std::string src = build_source(source, n_states, dim, method, n_obs, noise);
     for (int i = -1; i < user_header_count(n_obs); ++i) {
         FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : kUserHeaders[i].name)).c_str(), "w");
         if (!f) return 1;
@@ -630,13 +716,39 @@ int smc_user_model_dump_source2(const char *source, int n_states, int dim, int m
 int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir) {
     return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir);
 }
+int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir) {
+    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, proportional ? 2 : 1);
+}
+
+// the rules of a noise specification (include/smc_hip.h: smc_set_model_user4; user_models.noise_layout is the same in NumPy):
+// "" = valid, else what is wrong
+static std::string noise_spec_error(int n_obs, int dim, const int *add_index, const double *add_fixed, const int *prop_index,
+                                    const double *prop_fixed) {
+    if (!user_obs_ok(n_obs)) return "n_obs out of range (1 .. SMC_USER_MAX_OBS)";
+    if (dim < 1 || dim > SMC_MAX_DIM) return "dim out of range";
+    if (!add_index || !add_fixed) return "NULL add_index or add_fixed (one entry per output)";
+    if ((prop_index == nullptr) != (prop_fixed == nullptr)) return "prop_index and prop_fixed must both be given or both be NULL";
+    for (int k = 0; k < n_obs; ++k) {
+        const std::string o = "output " + std::to_string(k) + ": ";
+        if (add_index[k] < -1 || add_index[k] >= dim) return o + "add_index outside [0, dim) (-1 selects add_fixed)";
+        if (add_index[k] == -1 && !(std::isfinite(add_fixed[k]) && add_fixed[k] > 0.0)) return o + "add_fixed must be finite and > 0";
+        if (!prop_index) continue;
+        if (prop_index[k] < -1 || prop_index[k] >= dim) return o + "prop_index outside [0, dim) (-1 selects prop_fixed)";
+        if (prop_index[k] == -1 && !(std::isfinite(prop_fixed[k]) && prop_fixed[k] >= 0.0)) return o + "prop_fixed must be finite and >= 0";
+    }
+    return "";
+}
+int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double *add_fixed, const int *prop_index, const double *prop_fixed) {
+    const std::string bad = noise_spec_error(n_obs, dim, add_index, add_fixed, prop_index, prop_fixed);
+    return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_noise_check: " + bad).c_str());
+}
 
 // The models of all three set functions.  multi: smc_set_model_user3 (obs n_ex x n_t x n_obs, validated, the multi-output
 // source); else the one-output source and data exactly as before, plus the image for a later smc_user_predict when the data
 // allows one.
 static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
-                               double sigma_fixed, double rtol, double atol, int method, bool multi) {
+                               double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr) {
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
@@ -646,13 +758,18 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     std::vector<double> me, ls;
     std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls) : std::string("NULL t or obs");
     if (multi && !bad.empty()) return smc_fail(c, ("smc_set_model_user3: " + bad).c_str());
-    if (multi && user_lds_bytes3(n_states, n_ex, n_t, n_obs) > kUserLdsCap)
+    if (multi && !nz && user_lds_bytes3(n_states, n_ex, n_t, n_obs) > kUserLdsCap)
         return smc_fail(c, "smc_set_model_user3: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) "
                            "(n_obs + 2 rounded down to even)) x 8 B + pools > 150 KB)");
+    if (nz && user_lds_bytes3(n_states, n_ex, n_t, n_obs, true) > kUserLdsCap)
+        return smc_fail(c, ("smc_set_model_user4: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) (n_obs + 2 "
+                            "rounded down to even) + 40 + 8 n_ex) x 8 B + pools): " +
+                            std::to_string(user_lds_bytes3(n_states, n_ex, n_t, n_obs, true)) + " B needed, " + std::to_string(kUserLdsCap) +
+                            " B available").c_str());
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(source, n_states, c->dim, method, multi ? n_obs : 0, code, lg)) {
+    if (!compile_user(source, n_states, c->dim, method, multi ? n_obs : 0, code, lg, nz ? 1 + nz->prop : 0)) {
         std::string msg = "user model does not compile:\n" + lg;
         if (msg.size() > 3500) msg.resize(3500);
         return smc_fail(c, msg.c_str());
@@ -683,6 +800,10 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
             k[e] = multi ? me[e] : (double)n_t;
             k[n_ex + e] = multi ? ls[e] : 0.0;
         }
+        if (nz) {      // user_finish_noise_kernel: m_ek follows
+            const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs);
+            k.insert(k.end(), mek.begin(), mek.end());
+        }
         ok = ok && hipMalloc(&u->d_const, k.size() * sizeof(double)) == hipSuccess &&
              hipMemcpy(u->d_const, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
         if (bad.empty() && !multi) {
@@ -690,7 +811,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
                 if (me[e] != (double)n_t) bad = "a missing observation (NaN)";
         }
         if (bad.empty()) {
-            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls);
+            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz);
             u->img_len = (int)img.size();
             ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
                  hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
@@ -716,9 +837,13 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     }
     u->n_obs = n_obs;
     u->multi = multi;
+    if (nz) {
+        u->noise = true;
+        u->nz = *nz;
+    }
     {   // occupancy of the compiled kernel with its pool in LDS
         int nb = 0;
-        const size_t lds = multi ? user_lds_bytes3(n_states, n_ex, n_t, n_obs) : user_lds_bytes(n_states, n_ex, n_t);
+        const size_t lds = multi ? user_lds_bytes3(n_states, n_ex, n_t, n_obs, nz != nullptr) : user_lds_bytes(n_states, n_ex, n_t);
         if (lds > kUserLdsCap) {
             user_model_release(c);
             return smc_fail(c, "smc_set_model_user: data set too large for the kernel's LDS table (n_ex * n_t * 16 B + pools > 150 KB)");
@@ -769,6 +894,34 @@ int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs,
                         double atol, int method) {
     return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol,
                                atol, method, true);
+}
+
+int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
+                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    const std::string bad = noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed);
+    if (!bad.empty()) return smc_fail(c, ("smc_set_model_user4: " + bad).c_str());
+    if (!prop_index) {      // today's model: one sigma for every output - the smc_set_model_user3 path and its bits
+        bool last = true, fixed = true;
+        for (int k = 0; k < n_obs; ++k) {
+            last = last && add_index[k] == c->dim - 1;
+            fixed = fixed && add_index[k] == -1 && add_fixed[k] == add_fixed[0];
+        }
+        if (last || fixed)
+            return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, last ? 1 : 0,
+                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true);
+    }
+    UserNoise nz{};
+    for (int k = 0; k < kUserMaxObs; ++k) {
+        nz.add_index[k] = k < n_obs ? add_index[k] : -1;
+        nz.add_fixed[k] = (k < n_obs && add_index[k] < 0) ? add_fixed[k] : 1.0;
+        nz.prop_index[k] = (k < n_obs && prop_index) ? prop_index[k] : -1;
+        nz.prop_fixed[k] = (k < n_obs && prop_index && prop_index[k] < 0) ? prop_fixed[k] : 0.0;
+        nz.scale[k] = (k < n_obs && obs_scale) ? obs_scale[k] : 1.0;
+    }
+    nz.prop = prop_index ? 1 : 0;
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz);
 }
 
 int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts) {
@@ -860,7 +1013,7 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
 }
 static int design_too_large(smc_ctx *c, const UserModel *u, const char *who, int n_t) {
     return smc_fail(c, (std::string(who) + ": one row of the design does not fit the kernel's LDS table: " +
-                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs)) + " B needed, " + std::to_string(kUserLdsCap) +
+                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs, u->noise)) + " B needed, " + std::to_string(kUserLdsCap) +
                         " B available").c_str());
 }
 
@@ -1035,6 +1188,8 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
         a.est_sigma = u->est_sigma;
         a.sigma_fixed = u->sigma_fixed;
         for (int j = 0; j < kUserMaxObs; ++j) a.scale[j] = u->scale[j];
+        a.has_noise_model = u->noise ? 1 : 0;
+        a.nz = u->nz;
         a.seed = seed;
         a.global_offset = global_offset;
         a.n_probs = n_probs;

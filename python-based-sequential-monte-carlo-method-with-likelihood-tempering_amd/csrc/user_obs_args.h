@@ -12,6 +12,11 @@
 //                              zero padding) for the row's n_t_e finite times, then (+inf, t[e][n_t_e - 1], ...) up to and
 //                              including record n_t - the +inf sentinel of solve_sched's dense-output loop at the row's own end
 //                              and, in the last record, the row's end time.
+// A model with a NOISE MODEL (smc_set_model_user4; the source is compiled with SMC_USER_NOISE 1) appends to the table, at
+// obs_noise_at(n_ex, n_t, n_obs), kNoiseHdr + 8 n_ex words:
+//   [0, 8)    add_index[k] as a double (-1: fixed)     [8, 16)   add_fixed[k]
+//   [16, 24)  prop_index[k] (-1: fixed)                [24, 32)  prop_fixed[k] (0 without a proportional part)
+//   [32, 40)  s_k                                      [40 + 8 e + k]  m_ek, the finite observations of output k in experiment e
 #pragma once
 
 namespace smc {
@@ -21,6 +26,18 @@ constexpr int kObsHdrMe = 8;
 
 __host__ __device__ constexpr inline int obs_rec_words(int n_obs) { return (2 + n_obs) & ~1; }      // 16-byte records
 __host__ __device__ constexpr inline int obs_table_at(int n_ex) { return (kObsHdrMe + 2 * n_ex + 1) & ~1; }
+constexpr int kNoiseHdr = 40;
+__host__ __device__ constexpr inline int obs_noise_at(int n_ex, int n_t, int n_obs) { return obs_table_at(n_ex) + n_ex * (n_t + 1) * obs_rec_words(n_obs); }
+__host__ __device__ constexpr inline int obs_noise_words(int n_ex) { return kNoiseHdr + 8 * n_ex; }
+
+// The noise model of smc_set_model_user4 as the library's own kernels take it (user_finish_noise_kernel, pred_keys_kernel);
+// the run-time compiled kernels read the same numbers from the image.
+struct UserNoise {
+    int add_index[kUserMaxObs], prop_index[kUserMaxObs];      // a parameter number, or -1: the fixed value
+    double add_fixed[kUserMaxObs], prop_fixed[kUserMaxObs];
+    double scale[kUserMaxObs];                                // s_k
+    int prop;                                                 // 1: with a proportional part (SMC_USER_NOISE_PROP 1)
+};
 
 // The second argument block of the multi-output solve and prediction kernels.
 struct UserObsArgs {
@@ -84,5 +101,121 @@ __device__ __forceinline__ void emit(double &sr2, double *&pred, const double *y
         pred += kObs;
     }
 }
+
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+// ---- the noise model of smc_set_model_user4: sd_ik^2 = (a_k s_k)^2 + (b_k f_ik)^2, a_k and b_k a parameter or a fixed number ----
+// An item accumulates the EXCESS over the floor log(a_k s_k) every observation has before it is served:
+//   x_ik = 1/2 log1p((b_k f_ik / (a_k s_k))^2) + r_ik^2 / (2 sd_ik^2) >= 0,
+// so the sum only grows and the early-rejection bound stays exact.  Per item: w_k = 1 / (2 (a_k s_k)^2) and, with a
+// proportional part (SMC_USER_NOISE_PROP 1), q_k = (b_k / (a_k s_k))^2; then u = q_k f^2 and x = 1/2 log1p(u) + r^2 w_k / (1 + u):
+// one log1p and one division per observed value.  Without it x = r^2 w_k and neither is compiled.
+constexpr int kProp = SMC_USER_NOISE_PROP;
+struct Noise {
+    double w[kObs];
+#if SMC_USER_NOISE_PROP
+    double q[kObs];
+#endif
+};
+__device__ __forceinline__ const double *noise_lds(int n_ex, int n_t) { return lds() + smc::obs_noise_at(n_ex, n_t, kObs); }
+__device__ __forceinline__ double mek(int e, int k, int n_ex, int n_t) { return noise_lds(n_ex, n_t)[smc::kNoiseHdr + 8 * e + k]; }
+// parameter number idx (as a double) of th, or fixed: selects, so that th stays in registers
+__device__ __forceinline__ double noise_pick(const double *th, double idx, double fixed) {
+    double v = fixed;
+#pragma unroll
+    for (int c = 0; c < SMC_USER_DIM; ++c) v = (idx == (double)c) ? th[c] : v;
+    return v;
+}
+__device__ __forceinline__ double noise_add(const double *th, int k, int n_ex, int n_t) {
+    const double *nz = noise_lds(n_ex, n_t);
+    return noise_pick(th, nz[k], nz[8 + k]);
+}
+__device__ __forceinline__ double noise_prop(const double *th, int k, int n_ex, int n_t) {
+    const double *nz = noise_lds(n_ex, n_t);
+    return noise_pick(th, nz[16 + k], nz[24 + k]);
+}
+__device__ __forceinline__ double noise_scale(int k, int n_ex, int n_t) { return noise_lds(n_ex, n_t)[32 + k]; }
+// every a_k > 0 and every b_k >= 0 (NaN: no); else logL = -inf
+__device__ __forceinline__ bool noise_valid(const double *th, int n_ex, int n_t) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < kObs; ++k) ok = ok && noise_add(th, k, n_ex, n_t) > 0.0 && (!kProp || noise_prop(th, k, n_ex, n_t) >= 0.0);
+    return ok;
+}
+// the item's weights from its particle's parameters; zeros (no excess at all) for parameters that make logL -inf
+__device__ __forceinline__ void noise_weights(Noise &nz, const double *th, int n_ex, int n_t) {
+    const bool ok = noise_valid(th, n_ex, n_t);
+#pragma unroll
+    for (int k = 0; k < kObs; ++k) {
+        const double as = noise_add(th, k, n_ex, n_t) * noise_scale(k, n_ex, n_t);
+        const double as2 = as * as;
+        nz.w[k] = ok ? 1.0 / (2.0 * as2) : 0.0;
+#if SMC_USER_NOISE_PROP
+        const double b = noise_prop(th, k, n_ex, n_t);
+        const double b2 = b * b;
+        nz.q[k] = ok ? b2 / as2 : 0.0;
+#endif
+    }
+}
+// 1/2 log1p(u), NOT inlined: inlined into the output branch of the attempt its registers push the RK45 kernel's bulk attempt loop
+// into scratch (three reloads per attempt at four waves per SIMD); behind a call the loop is as free of scratch as without a noise
+// model.  A call per observed value, in the rare branch, next to the log1p itself.
+#if SMC_USER_NOISE_PROP
+__device__ __attribute__((noinline)) double noise_half_log1p(double u) { return 0.5 * log1p(u); }
+#endif
+// emit under a noise model: x_ik added to the item's sum.  FUSE as above: one contracted expression per step where the RK45
+// kernel's -ffp-contract=on allows it, every product and sum rounded on its own in the BDF kernel.
+template <bool PRED, bool FUSE>
+__device__ __forceinline__ void emit_noise(double &sx, double *&pred, const Noise &nz, const double *yy, const double *th, const double *c,
+                                           double t_out, const double *obs) {
+    double m[kObs];
+    model_obs(t_out, yy, th, c, m);
+#pragma unroll
+    for (int k = 0; k < kObs; ++k) {
+        const double r = obs[k] - m[k];
+#if SMC_USER_NOISE_PROP
+        double x;
+        if (FUSE) {
+            const double u = nz.q[k] * (m[k] * m[k]);
+            x = noise_half_log1p(u) + (r * r) * nz.w[k] / (1.0 + u);
+        } else {
+            const double f2 = m[k] * m[k];
+            const double u = nz.q[k] * f2;
+            const double r2 = r * r;
+            const double rw = r2 * nz.w[k];
+            const double den = 1.0 + u;
+            const double quad = rw / den;
+            const double half = noise_half_log1p(u);
+            x = half + quad;
+        }
+        sx = (obs[k] == obs[k]) ? sx + x : sx;              // NaN: not measured
+#else
+        if (FUSE) {
+            sx = (obs[k] == obs[k]) ? sx + (r * r) * nz.w[k] : sx;
+        } else {
+            const double r2 = r * r;
+            const double x = r2 * nz.w[k];
+            sx = (obs[k] == obs[k]) ? sx + x : sx;
+        }
+#endif
+    }
+    if (PRED) {
+#pragma unroll
+        for (int k = 0; k < kObs; ++k) pred[k] = m[k];
+        pred += kObs;
+    }
+}
+// The likelihood of a particle from the sums X_e, as user_finish_noise_kernel (user_model.hip) forms it, in its order:
+//   lk = sum_e [ (-m_e / 2) log(2 pi) - sum_k m_ek log(a_k s_k) - X_e ].
+// floor_of(e): the bracket without X_e.  Used by the early-rejection bound of both kernels.
+__device__ __forceinline__ double noise_floor_of(int e, const double *la, int n_ex, int n_t) {
+    double c0 = (-0.5 * me(e)) * 1.8378770664093453;
+#pragma unroll
+    for (int k = 0; k < kObs; ++k) {
+        const double term = mek(e, k, n_ex, n_t) * la[k];
+        c0 = c0 - term;
+    }
+    return c0;
+}
+#endif
 }  // namespace smc_obs
 #endif

@@ -72,6 +72,9 @@ struct Item {
 #ifdef SMC_USER_NOBS
     double *pred;   // prediction kernel: where the outputs of t_eval[i_out] go (UserOps::set_pred); else nullptr
 #endif
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+    smc_obs::Noise nz;   // noise model (user_obs_args.h): the particle's weights; sr2 then holds the excess sum X_e
+#endif
     int i_out, status;   // status: 0 running, 1 finished, -1 step size underflow (the reference's solver raises)
     bool rejected;
 };
@@ -81,7 +84,11 @@ struct Item {
 using DataRec = smc_obs::Rec;
 __device__ __forceinline__ double t_bound_of(const DataRec *tp, int n_t) { return tp[n_t].y[0]; }
 __device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, const double *obs) {
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+    smc_obs::emit_noise<SMC_USER_PRED, true>(it.sr2, it.pred, it.nz, yy, theta, cond, t_out, obs);
+#else
     smc_obs::emit<SMC_USER_PRED, true>(it.sr2, it.pred, yy, theta, cond, t_out, obs);
+#endif
 }
 #else
 // one output: n_t + 1 (time, observation) pairs, the last one the sentinel (+inf, 0) - as in the built-in kernel
@@ -329,6 +336,9 @@ struct UserOps {
     __device__ __forceinline__ void load_theta(Item &it, long long p) const {
 #pragma unroll
         for (int c = 0; c < SMC_USER_DIM; ++c) it.th[c] = a.theta[c * a.stride + p];
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+        smc_obs::noise_weights(it.s.nz, it.th, a.n_ex, a.n_t);
+#endif
     }
     __device__ __forceinline__ int start(long long p, int e, bool from_list, Item &nb) const {
         nb.out_idx = (long long)e * a.n + p;
@@ -417,6 +427,15 @@ struct UserOps {
         }
 #pragma unroll
         for (int c = 0; c < SMC_USER_DIM; ++c) u.th[c] = smc::lane_value(it.th[c], src);
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+#pragma unroll
+        for (int k = 0; k < smc_obs::kObs; ++k) {
+            u.s.nz.w[k] = smc::lane_value(it.s.nz.w[k], src);
+#if SMC_USER_NOISE_PROP
+            u.s.nz.q[k] = smc::lane_value(it.s.nz.q[k], src);
+#endif
+        }
+#endif
         u.out_idx = smc::lane_value_ll(it.out_idx, src);
         u.e = __builtin_amdgcn_readlane(it.e, src);
         u.attempts = (unsigned)__builtin_amdgcn_readlane((int)it.attempts, src);
@@ -428,6 +447,42 @@ struct UserOps {
     // residuals, lk1 and rr are fixed before the sweep, so a proposal that fails exp((lk2 - lk1) gamma) >= rr with the sums
     // accumulated SO FAR (0 for a sibling still running) is rejected whatever the rest would add.  The expression is the
     // one user_finish_kernel evaluates, in the same order.
+#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
+    // EXACT early rejection under a noise model (user_obs_args.h): every observation not yet served sits at its floor
+    // log(a_k s_k), known from theta, and the published sums are excesses over it, which only grow - so the likelihood formed
+    // from the sums SO FAR (0 for a sibling still running) is an upper bound.  user_finish_noise_kernel's expression, in its order.
+    __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
+        const long long p = it.out_idx - (long long)it.e * a.n;
+        if (!smc_obs::noise_valid(it.th, a.n_ex, a.n_t)) return false;
+        double la[smc_obs::kObs];
+#pragma unroll
+        for (int k = 0; k < smc_obs::kObs; ++k) la[k] = log(smc_obs::noise_add(it.th, k, a.n_ex, a.n_t) * smc_obs::noise_scale(k, a.n_ex, a.n_t));
+        double lk2_bound = 0.0;
+        for (int k = 0; k < a.n_ex; ++k) {
+            double S = 0.0;
+            if (k == it.e) {
+                S = it.s.sr2;
+            } else {
+                const double v = __longlong_as_double((long long)__hip_atomic_load(
+                    reinterpret_cast<unsigned long long *>(a.sum_r2) + (long long)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (v < 0.0) return true;      // a sibling has already established the rejection
+                if (v == v) S = v;             // finished; NaN = still running: counts as 0
+            }
+            lk2_bound += smc_obs::noise_floor_of(k, la, a.n_ex, a.n_t) - S;
+        }
+        const smc::RejectArgs &r = *a.rej;
+        double rr;
+        if (r.device_rng) {
+            const smc::u32x4 ru = smc::philox_block(r.seed, (unsigned long long)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
+            rr = smc::u01_from(ru.x, ru.y);
+        } else {
+            rr = r.rr[p];
+        }
+        double pp = exp((lk2_bound - r.lk1[p]) * r.gamma);
+        if (r.prior_mode != 0) pp = pp * r.pratio[p];
+        return pp < rr * (1.0 - 1e-12);
+    }
+#else
     __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
         const long long p = it.out_idx - (long long)it.e * a.n;
         const double sigma = a.est_sigma ? it.th[SMC_USER_DIM - 1] : a.sigma_fixed;
@@ -465,6 +520,7 @@ struct UserOps {
         if (r.prior_mode != 0) pp = pp * r.pratio[p];      // SMC_PRIOR_MODE_MASK == 0
         return pp < rr * (1.0 - 1e-12);
     }
+#endif
     __device__ __forceinline__ void cancel(Item &it) const {
         publish(it.out_idx, -1.0, (int)(it.attempts & 0x1fffffffu) | (1 << 29));
     }

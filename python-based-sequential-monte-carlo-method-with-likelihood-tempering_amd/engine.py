@@ -171,7 +171,7 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6, method="RK45", obs_scale=None):
+                       atol=1e-6, method="RK45", obs_scale=None, noise=None):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
@@ -180,12 +180,15 @@ class HipEngine:
         Several measured outputs, missing data, ragged rows (smc_set_model_user3): obs (n_ex, n_t, n_obs) with NaN for a value
         that was not measured, t rows that may end in NaN times, obs_scale (n_obs,) relative noise scales; the source then
         defines smc_user_obs_vec.  A 3-D obs or any obs_scale takes this path (ValueError for data it refuses, see
-        user_models.obs_layout); a 2-D obs without obs_scale goes through smc_set_model_user2 exactly as before."""
+        user_models.obs_layout); a 2-D obs without obs_scale goes through smc_set_model_user2 exactly as before.
+        A noise model (smc_set_model_user4): noise={"additive": [("param", j) | ("fixed", v), ...], "proportional": [...]}, one
+        entry per output, "proportional" optional - sd^2 = (a_k s_k)^2 + (b_k f)^2 (user_models.noise_loglik is the likelihood).
+        est_sigma and sigma_fixed are then not used; ValueError for a specification that breaks user_models.noise_layout's rules."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
         obs = np.asarray(obs)
-        multi = obs.ndim == 3 or obs_scale is not None
+        multi = obs.ndim == 3 or obs_scale is not None or noise is not None
         if multi:
             # several outputs, NaN = not measured, ragged rows (smc_set_model_user3); the same checks as the library's
             obs = _f64(obs if obs.ndim == 3 else obs.reshape(obs.shape + (1,)))
@@ -198,7 +201,19 @@ class HipEngine:
             n_obs = 1
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
-        if multi:
+        if noise is not None:
+            from .user_models import noise_layout
+            ai, af, pi, pf = noise_layout(noise, n_obs, self.dim)
+            ip = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(B.c_ip)
+            fp = lambda a: None if a is None else _dp(np.ascontiguousarray(a, dtype=np.float64))
+            ai, af = np.ascontiguousarray(ai, dtype=np.int32), np.ascontiguousarray(af)
+            pi = None if pi is None else np.ascontiguousarray(pi, dtype=np.int32)
+            pf = None if pf is None else np.ascontiguousarray(pf)
+            self._ck(self.L.smc_set_model_user4(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
+                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
+                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol),
+                                                B.USER_METHODS[method]), "smc_set_model_user4")
+        elif multi:
             self._ck(self.L.smc_set_model_user3(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
                                                 None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
                                                 int(bool(est_sigma)), float(sigma_fixed), float(rtol), float(atol),

@@ -111,6 +111,70 @@ def obs_layout(t, obs, obs_scale=None):
             "sum_log_scale": np.sum(np.where(seen, np.log(scale)[None, None, :], 0.0), axis=(1, 2))}
 
 
+def noise_layout(noise, n_obs, dim):
+    """The rules of a noise specification (include/smc_hip.h: smc_set_model_user4), in NumPy.  noise = {"additive": [entry per
+    output], "proportional": [entry per output] (optional)}, an entry ("param", j) - parameter j in [0, dim) - or ("fixed", v)
+    with v finite and > 0 (additive) or >= 0 (proportional).  Returns (add_index, add_fixed, prop_index, prop_fixed): int32 /
+    float64 arrays of n_obs entries, index -1 where the value is fixed; the last two None without a proportional part.  Raises
+    ValueError for a specification the library refuses."""
+    import numpy as np
+    if not isinstance(noise, dict) or "additive" not in noise or set(noise) - {"additive", "proportional"}:
+        raise ValueError('noise_layout: noise must be {"additive": [...], "proportional": [...] (optional)}')
+    n_obs, dim = int(n_obs), int(dim)
+
+    def part(name, lowest_ok):
+        entries = list(noise[name])
+        if len(entries) != n_obs:
+            raise ValueError(f"noise_layout: {name!r} must have n_obs = {n_obs} entries, got {len(entries)}")
+        index, fixed = np.full(n_obs, -1, dtype=np.int32), np.zeros(n_obs)
+        for k, entry in enumerate(entries):
+            if not (isinstance(entry, (tuple, list)) and len(entry) == 2 and entry[0] in ("param", "fixed")):
+                raise ValueError(f'noise_layout: {name}[{k}] must be ("param", j) or ("fixed", v), got {entry!r}')
+            if entry[0] == "param":
+                j = int(entry[1])
+                if j != entry[1] or not 0 <= j < dim:
+                    raise ValueError(f"noise_layout: {name}[{k}] names parameter {entry[1]!r} outside [0, {dim})")
+                index[k] = j
+            else:
+                v = float(entry[1])
+                if not (np.isfinite(v) and lowest_ok(v)):
+                    raise ValueError(f"noise_layout: {name}[{k}] fixed value {v!r} must be finite and "
+                                     + ("> 0" if name == "additive" else ">= 0"))
+                fixed[k] = v
+        return index, fixed
+
+    add_index, add_fixed = part("additive", lambda v: v > 0)
+    if noise.get("proportional") is None:
+        return add_index, add_fixed, None, None
+    prop_index, prop_fixed = part("proportional", lambda v: v >= 0)
+    return add_index, add_fixed, prop_index, prop_fixed
+
+
+def noise_loglik(pred, t, obs, theta, noise, obs_scale=None):
+    """The likelihood of a noise model (include/smc_hip.h: smc_set_model_user4) applied to given model outputs - its executable
+    definition.  pred (n, n_ex, n_t, n_obs) outputs f, t (n_ex, n_t), obs (n_ex, n_t, n_obs), theta (n, dim).  With a_k, b_k
+    taken from theta or fixed (noise_layout) and s_k = obs_scale:  sd^2 = (a_k s_k)^2 + (b_k f)^2,
+    logL = sum over observed (e, i, k) [-1/2 log(2 pi) - log sd - (obs - f)^2 / (2 sd^2)]; observed = obs finite at a finite
+    time of the row; -inf where any a_k <= 0 or any b_k < 0.  Returns (n,)."""
+    import numpy as np
+    pred = np.asarray(pred, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    n_obs = obs.shape[2]
+    ai, af, pi, pf = noise_layout(noise, n_obs, theta.shape[1])
+    scale = np.ones(n_obs) if obs_scale is None else np.asarray(obs_scale, dtype=np.float64).reshape(n_obs)
+    a = np.where(ai >= 0, theta[:, np.maximum(ai, 0)], af[None, :])                      # (n, n_obs)
+    b = np.zeros_like(a) if pi is None else np.where(pi >= 0, theta[:, np.maximum(pi, 0)], pf[None, :])
+    seen = ~np.isnan(obs) & ~np.isnan(np.asarray(t, dtype=np.float64))[:, :, None]
+    f = np.where(seen[None], pred, 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sd2 = (a * scale)[:, None, None, :] ** 2 + (b[:, None, None, :] * f) ** 2
+        r = np.where(seen[None], obs[None] - f, 0.0)
+        term = np.where(seen[None], -0.5 * np.log(2 * np.pi) - 0.5 * np.log(sd2) - r * r / (2 * sd2), 0.0)
+        lk = term.sum(axis=(1, 2, 3))
+    return np.where(np.all(a > 0, axis=1) & np.all(b >= 0, axis=1), lk, -np.inf)
+
+
 def design_layout(t_new, cond_new, n_cond):
     """The rules of a prediction design (include/smc_hip.h: smc_user_predict_at), in NumPy: t_new (n_ex_new, n_t_new) by the row
     rules of obs_layout - a strictly increasing run of finite times, possibly followed by NaN only; t_new[e][0] is the initial
