@@ -469,7 +469,7 @@ class HipEngine:
         smc_user_predict_summary): per cell (experiment, time, output) of the design (t, cond; None: the data's) over the set's
         equally weighted particles.  Returns {"mean", "sd", "n_finite": (n_ex, n_t, n_obs); "lower", "upper", "quantile":
         (n_probs, n_ex, n_t, n_obs) - the order statistics np.nanquantile picks with method "lower" / "higher" and the linear
-        value lower + (upper - lower) * frac between them (user_models.quantile_ranks); "n_failed", "rk_attempts"; "kernel_ms":
+        value between them (user_models.quantile_ranks, linear_quantile); "n_failed", "rk_attempts"; "kernel_ms":
         {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
         global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
         With several ranks the summary describes this rank's block only."""
@@ -489,11 +489,8 @@ class HipEngine:
                                                  int(global_offset), int(max_staging_bytes), _dp(mean), _dp(sd), _dp(lower),
                                                  _dp(upper), nfin.ctypes.data_as(B.c_i64p), ctypes.byref(nf), ctypes.byref(att),
                                                  _dp(ms)), "smc_user_predict_summary")
-        from .user_models import quantile_ranks
-        frac = quantile_ranks(np.maximum(nfin, 1)[None], q[:, None, None, None])[2]
-        with np.errstate(invalid="ignore"):
-            quantile = np.where(upper == lower, lower, lower + (upper - lower) * frac)
-            quantile = np.minimum(np.maximum(quantile, lower), upper)       # rounding cannot leave the bracket
+        from .user_models import linear_quantile, quantile_ranks
+        quantile = linear_quantile(lower, upper, quantile_ranks(np.maximum(nfin, 1)[None], q[:, None, None, None])[2])
         return {"mean": mean, "sd": sd, "n_finite": nfin, "lower": lower, "upper": upper, "quantile": quantile,
                 "n_failed": nf.value, "rk_attempts": att.value, "kernel_ms": {"predict": float(ms[0]), "summary": float(ms[1])}}
 
