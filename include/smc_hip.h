@@ -291,6 +291,24 @@ int smc_set_cost_order(smc_ctx *ctx, int enable);
  * bit (tests/test_gpu_parity.py compares on and off); 0 is for that comparison and for A/B timing.  Parity mode
  * (smc_set_exact_pow) never uses it. */
 int smc_set_fast_tail(smc_ctx *ctx, int enable);
+/* Replicate experiments of a Michaelis-Menten data set - the same S0 and the same n_t data times, BIT FOR BIT - integrate the same
+ * initial value problem for every particle: the same RK45 attempts, the same accept / reject decisions, the same dense-output
+ * values; only P_obs differs.  smc_set_model_mm groups them (smc_mm_group_replicates) and a sweep then integrates ONCE per group
+ * and accumulates the sums of squared residuals of both experiments of a pair (default: on; the environment variable
+ * SMC_SHARE_REPLICATES=0 turns it off whatever this switch says, for A/B runs of one build under an unchanged caller).  Every result is the same bit for bit
+ * (tests/test_gpu_shared_replicates.py compares on and off); the attempt counts keep their meaning "per experiment, as the
+ * reference counts them": the partner's record repeats its primary's count, so rk_attempts includes attempts nobody executed -
+ * smc_mm_share_info says how many.  A data set without replicates runs the same kernels whatever the switch says. */
+int smc_set_share_replicates(smc_ctx *ctx, int enable);
+/* The grouping itself, a pure host function (no device is touched): t is n_ex x n_t, S0 n_ex; primary[g] / partner[g] (-1: none)
+ * receive the experiments of solve group g (both arrays n_ex long, unused entries -1), groups in order of first appearance, the
+ * primary the lowest index, at most one partner: a condition that appears three or more times becomes pairs plus, if odd, a
+ * single.  Returns the number of groups, or -1 for bad arguments. */
+int smc_mm_group_replicates(const double *t, const double *S0, int n_ex, int n_t, int *primary, int *partner);
+/* n_solve: solves per particle a sweep schedules now (the groups when sharing is on, else n_ex); shared_attempts: device-counted
+ * RK45 attempts since the last smc_timing_reset that are in rk_attempts (smc_work_totals out[1], the sweeps' own counts) but were
+ * not executed - the partners' copies.  Either pointer may be NULL.  Synchronises the stream. */
+int smc_mm_share_info(smc_ctx *ctx, int *n_solve, int64_t *shared_attempts);
 /* Michaelis-Menten Metropolis sweeps over a homogeneous population (the previous sweep of the context had fewer than one
  * (particle, experiment) solve in 20 000 with more than 64 RK45 attempts - counted on the device) run their waves IN PHASE
  * (default: on): a wave waits up to 12 attempts for all 64 lanes to finish before it starts its next 64 items, so that the
@@ -322,6 +340,8 @@ int smc_download_accept_flags(smc_ctx *ctx, uint8_t *flags, int64_t n);
 /* Diagnostics (tools/sweep_tail_census.py): the per-(experiment, particle) record of the last Michaelis-Menten sweep over n
  * particles, info[e * n + p] = RK45 attempts | cancelled by early rejection << 29 | failed << 30.  n_ex * n entries. */
 int smc_download_item_info(smc_ctx *ctx, int32_t *info, int64_t n);
+/* ... and its sums of squared residuals, sums[e * n + p] (after a Metropolis sweep with early rejection: -1 for a cancelled solve). */
+int smc_download_item_sums(smc_ctx *ctx, double *sums, int64_t n);
 /* p_pred, lk = p_filt.copy(), lk1.copy() (Micmem_SMC_main.py:251-252): device-to-device. */
 int smc_commit_filt_to_pred(smc_ctx *ctx);
 /* Device-RNG prior draw into SMC_SET_PRED (replaces sample_prior, Micmem_settings.py:69-87, in

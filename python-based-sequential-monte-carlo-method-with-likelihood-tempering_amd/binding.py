@@ -85,6 +85,9 @@ SIGNATURES = {
     "smc_set_stiff_first": (cint, [c_ctx, cint]),
     "smc_set_cost_order": (cint, [c_ctx, cint]),
     "smc_set_fast_tail": (cint, [c_ctx, cint]),
+    "smc_set_share_replicates": (cint, [c_ctx, cint]),
+    "smc_mm_group_replicates": (cint, [c_dp, c_dp, cint, cint, c_ip, c_ip]),
+    "smc_mm_share_info": (cint, [c_ctx, c_ip, c_i64p]),
     "smc_set_in_phase": (cint, [c_ctx, cint]),
     "smc_set_exact_pow": (cint, [c_ctx, cint]),
     "smc_exchange_plan": (cint, [cint, cint, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
@@ -94,6 +97,7 @@ SIGNATURES = {
     "smc_download_lk": (cint, [c_ctx, cint, c_dp, i64]),
     "smc_download_accept_flags": (cint, [c_ctx, c_u8p, i64]),
     "smc_download_item_info": (cint, [c_ctx, ctypes.POINTER(ctypes.c_int32), i64]),
+    "smc_download_item_sums": (cint, [c_ctx, c_dp, i64]),
     "smc_debug_set_order": (cint, [c_ctx, ctypes.POINTER(ctypes.c_int32), i64, cint]),
     "smc_commit_filt_to_pred": (cint, [c_ctx]),
     "smc_sample_prior_device": (cint, [c_ctx, u64, i64]),

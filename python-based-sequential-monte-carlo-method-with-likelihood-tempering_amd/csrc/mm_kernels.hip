@@ -388,6 +388,7 @@ constexpr int kSolveBlock = 256;   // 4 waves
 // predecessor had (almost) none runs its waves in phase (SolveArgs::patience, solve_sched.h).  A posterior-like solve takes
 // 19 +- a few attempts, the stragglers of a prior-like population hundreds to thousands.
 constexpr int kLongItemAttempts = 64;
+constexpr int kFinishSharedWord = 1;   // accept kernel: 8-byte words from its arrival counter to the running total of shared attempts
 constexpr int kPoolWords = 15;     // 8-byte words of a pooled item: 11 doubles, 2 packed int pairs, out_idx, prediction pointer
 
 struct SolveArgs {              // everything the attempt loops do not touch stays behind a pointer (RejectArgs, StiffList)
@@ -410,6 +411,17 @@ struct SolveArgs {              // everything the attempt loops do not touch sta
     const SortedProposal *sorted;   // with n_ordered: the proposals in cost order, one 32-byte record per position (written by the
                                     // counting sort's scatter): a wave's 64 starts read 2 KB in a row instead of 192 scattered lines
     const MHControl *ctl;           // batch of iterations under device control: the kernel leaves at once when ctl->stop is set
+};
+
+// Replicate experiments - the same S0 and the same data times, bitwise (replicate_groups.h) - have the same trajectory for every
+// particle: the same attempts, the same accept / reject decisions, the same dense-output values; only the observations the
+// residuals are formed against differ.  A sharing sweep therefore schedules SOLVE GROUPS instead of experiments (the scheduler's
+// "n_ex" is their number): one item integrates once and accumulates the sums of its primary experiment and of the partner, and
+// publishes both, the partner's info word with the same attempt count (the counters stay "per experiment, as the reference
+// counts them").  groups: n_solve pairs (primary experiment, partner experiment or -1) in device memory.
+struct ShareArgs {
+    const int *groups;
+    int n_solve;
 };
 
 // A kernel argument as a scalar register of its OWN.  The kernel's arguments arrive in 4-, 8- and 16-dword loads, i.e. as
@@ -467,8 +479,9 @@ __device__ __forceinline__ void publish_item(const SolveArgs &a, int64_t idx, do
 // 469 of 470 of them (CPU replay of a 1e6-particle run) before the long solve has produced a single output.
 // Returns true only when rejection is certain; any NaN makes the comparison false.  `cancel_seen`: a sibling was already
 // cancelled, i.e. the particle is known to be rejected.
+// e_partner / partial_partner: the item also solves that experiment (a replicate, see ShareArgs); -1: none.
 __device__ __forceinline__ bool mm_certainly_rejected(const MMModel &mm, const SolveArgs &a, int64_t p, int e_self,
-                                                      double partial_self) {
+                                                      double partial_self, int e_partner = -1, double partial_partner = 0.0) {
     const double sigma = mm.est_sigma ? a.theta[2 * a.stride + p] : mm.sigma_fixed;
     if (!(sigma > 0.0)) return false;
     const double s2 = sigma * sigma;
@@ -478,6 +491,8 @@ __device__ __forceinline__ bool mm_certainly_rejected(const MMModel &mm, const S
         double S = 0.0;
         if (k == e_self) {
             S = partial_self;
+        } else if (k == e_partner) {
+            S = partial_partner;
         } else {
             const double v = __longlong_as_double((long long)__hip_atomic_load(
                 reinterpret_cast<unsigned long long *>(a.sum_r2) + (int64_t)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -505,7 +520,8 @@ __device__ __forceinline__ bool mm_certainly_rejected(const MMModel &mm, const S
 // selected at run time the block's registers cost the kernel its fourth wave per SIMD (140 instead of 128 VGPRs); as its own
 // instantiation it fits into 128, but its bulk loop is still ~6 % slower than the plain one's (register allocation around the
 // block), which a sweep over 10^6 particles does not notice and one over 10^7 does: launch_solve picks by the size of the sweep.
-template <bool WRITE_PRED, bool EXACT, bool FAST>
+// SHARE: the items are solve groups of replicate experiments (ShareArgs; mm_rk45.h: mm_dense_outputs).
+template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false>
 struct MMOps {
     struct Item {
         MMItem s;
@@ -528,6 +544,14 @@ struct MMOps {
     long long n_pos;            // positions of the index-ordered pass
     double *pub_sums;           // a.sum_r2 / a.info as registers of their own (own_sgpr): what finish() inside the attempt loop uses
     int *pub_info;
+    // SHARE: the block's lane-private words of LDS for the partner's running sum (one per thread), and the group table
+    double *s_sum2;
+    const int *s_grp;           // LDS: [2 s] primary experiment of solve group s, [2 s + 1] its partner or -1
+
+    __device__ __forceinline__ double *sum2_word() const { return SHARE ? s_sum2 + threadIdx.x : nullptr; }
+    // distance in experiments to the partner of the item (0: none), and the partner's sum so far
+    __device__ __forceinline__ int partner_distance(const Item &it) const { return SHARE ? it.s.t_off >> kSharePartnerShift : 0; }
+    __device__ __forceinline__ double partner_sum(const Item &it) const { return it.s.i_out == 0 ? 0.0 : *sum2_word(); }
 
     __device__ __forceinline__ int start(long long p, int e, bool from_list, Item &nb) const {
         // masked proposal: lk2 == lk1, no solve (a cost-ordered sweep holds none: the propose kernel has published them)
@@ -536,23 +560,41 @@ struct MMOps {
     }
     __device__ __forceinline__ int start_values(long long p, int e, bool from_list, bool masked, double Vmax, double Km, double sigma,
                                                 Item &nb) const {
+        int d_e = 0;                                     // SHARE: e is a solve group
+        if (SHARE) {
+            const int g = e;
+            e = s_grp[2 * g];
+            const int partner = s_grp[2 * g + 1];
+            d_e = partner < 0 ? 0 : partner - e;
+        }
+        const int n_ex_data = SHARE ? mm.n_ex : n_ex;    // experiments of the data set: the layout of the predictions
+        const int64_t out_idx2 = (int64_t)(e + d_e) * a.n + p;
         nb.out_idx = (int64_t)e * a.n + p;
         nb.pred = nullptr;
         // index-ordered pass: a particle of the stiff list has been handed out already
         if (!from_list && list && !masked && mm_is_stiff(Vmax, Km)) return kStartSkipped;
         if (masked || sigma <= 0.0) {                    // sigma <= 0: -inf without solving (:53-54)
             publish_item(a, nb.out_idx, 0.0, 0);
+            if (SHARE && d_e != 0) publish_item(a, out_idx2, 0.0, 0);
             if (WRITE_PRED) {
-                double *pp = a.pred + ((size_t)p * n_ex + e) * n_t;
+                double *pp = a.pred + ((size_t)p * n_ex_data + e) * n_t;
                 for (int i = 0; i < n_t; ++i) pp[i] = quiet_nan();
+                if (SHARE && d_e != 0)
+                    for (int i = 0; i < n_t; ++i) pp[d_e * n_t + i] = quiet_nan();
             }
             return kStartDone;
         }
-        if (WRITE_PRED) nb.pred = a.pred + ((size_t)p * n_ex + e) * n_t;
-        if (mm_item_begin<WRITE_PRED, EXACT>(nb.s, Vmax, Km, s_S0[e], s_tp, mm_table_row(e, n_t), n_t, rtol, atol, nb.pred))
+        if (WRITE_PRED) nb.pred = a.pred + ((size_t)p * n_ex_data + e) * n_t;
+        double sum2 = 0.0;
+        if (mm_item_begin<WRITE_PRED, EXACT, SHARE>(nb.s, Vmax, Km, s_S0[e], s_tp, mm_table_row(e, n_t), n_t, rtol, atol, nb.pred,
+                                                    d_e != 0, &sum2,
+                                                    WRITE_PRED ? nb.pred + d_e * n_t : nullptr)) {
+            if (SHARE) nb.s.t_off |= d_e << kSharePartnerShift;
             return kStartStarted;
+        }
         const bool ok = (nb.s.i_out == n_t);             // nothing to integrate: finished at once
         publish_item(a, nb.out_idx, ok ? nb.s.sum_r2 : quiet_nan(), ok ? 0 : kInfoFailed);
+        if (SHARE && d_e != 0) publish_item(a, out_idx2, ok ? sum2 : quiet_nan(), ok ? 0 : kInfoFailed);
         return kStartDone;
     }
     // word-major slots so that lanes reading or writing consecutive slots hit consecutive banks
@@ -594,7 +636,7 @@ struct MMOps {
         it.pred = WRITE_PRED ? (double *)__double_as_longlong(slot[14 * kWave]) : nullptr;
     }
     __device__ __forceinline__ int attempt(Item &it) const {
-        return mm_item_attempt<WRITE_PRED, kDivLean6, EXACT>(it.s, s_tp, n_t, rtol, atol, it.pred);
+        return mm_item_attempt<WRITE_PRED, kDivLean6, EXACT, SHARE>(it.s, s_tp, n_t, rtol, atol, it.pred, sum2_word());
     }
     __device__ __forceinline__ bool long_running(const Item &it) const { return it.s.attempts > kLongItemAttempts; }
     __device__ __forceinline__ long long positions() const { return n_pos; }
@@ -632,6 +674,15 @@ struct MMOps {
         publish_item(pub_sums, pub_info, it.out_idx, ok ? it.s.sum_r2 : quiet_nan(), it.s.attempts | (ok ? 0 : kInfoFailed));
         if (WRITE_PRED && !ok)
             for (int i = it.s.i_out; i < n_t; ++i) it.pred[i] = quiet_nan();
+        if (SHARE) {
+            const int d_e = partner_distance(it);
+            if (d_e != 0) {
+                publish_item(pub_sums, pub_info, it.out_idx + (int64_t)d_e * a.n, ok ? partner_sum(it) : quiet_nan(),
+                             it.s.attempts | (ok ? 0 : kInfoFailed));
+                if (WRITE_PRED && !ok)
+                    for (int i = it.s.i_out; i < n_t; ++i) it.pred[d_e * n_t + i] = quiet_nan();
+            }
+        }
     }
     __device__ __forceinline__ Item broadcast(const Item &it, int src) const {
         Item u;
@@ -652,38 +703,55 @@ struct MMOps {
         u.s.rejected = __builtin_amdgcn_readlane((int)it.s.rejected, src) != 0;
         u.out_idx = lane_value_ll(it.out_idx, src);
         u.pred = WRITE_PRED ? (double *)lane_value_ll((long long)it.pred, src) : nullptr;
+        if (SHARE) *sum2_word() = lane_value(*sum2_word(), src);   // the partner's sum follows the item into every lane
         return u;
     }
     __device__ __forceinline__ bool reject_enabled() const { return a.rej != nullptr; }
     __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
         const int e_self = (int)(it.out_idx / a.n);
+        if (SHARE) {
+            const int d_e = partner_distance(it);
+            return mm_certainly_rejected(mm, a, it.out_idx - (int64_t)e_self * a.n, e_self, it.s.sum_r2, d_e != 0 ? e_self + d_e : -1,
+                                         partner_sum(it));
+        }
         return mm_certainly_rejected(mm, a, it.out_idx - (int64_t)e_self * a.n, e_self, it.s.sum_r2);
     }
     __device__ __forceinline__ void cancel(Item &it) const {
         publish_item(a, it.out_idx, kSumCancelled, it.s.attempts | kInfoCancelled);
+        if (SHARE) {
+            const int d_e = partner_distance(it);
+            if (d_e != 0) publish_item(a, it.out_idx + (int64_t)d_e * a.n, kSumCancelled, it.s.attempts | kInfoCancelled);
+        }
     }
 };
 
-template <bool WRITE_PRED, bool EXACT, bool FAST>
-__device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs &a) {
+template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false>
+__device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs &a, const ShareArgs *sh = nullptr) {
     extern __shared__ double2 smem_tp[];
     if (a.ctl && __builtin_amdgcn_readfirstlane(a.ctl->stop)) return;   // the Metropolis loop has ended: nothing to solve (scalar branch)
     const int n_ex = mm.n_ex, n_t = mm.n_t;
     double2 *s_tp = smem_tp;                                        // n_ex rows of n_t + 1 (time, P_obs) pairs, mm_rk45.h
-    double *s_S0 = reinterpret_cast<double *>(s_tp + n_ex * (n_t + 1));   // n_ex
-    mm_table_fill(s_tp, mm.t, mm.P_obs, n_ex, n_t, threadIdx.x, blockDim.x);
+    double *s_S0 = reinterpret_cast<double *>(s_tp + (SHARE ? 2 : 1) * n_ex * (n_t + 1));   // n_ex
+    if (SHARE)
+        mm_table_fill_shared(s_tp, mm.t, mm.P_obs, n_ex, n_t, threadIdx.x, blockDim.x, sh->groups, sh->n_solve);
+    else
+        mm_table_fill(s_tp, mm.t, mm.P_obs, n_ex, n_t, threadIdx.x, blockDim.x);
     if (threadIdx.x < n_ex) s_S0[threadIdx.x] = mm.S0[threadIdx.x];
+    // SHARE, behind the pools: one word per thread for the partner's sum, then the group table
+    double *s_sum2 = s_S0 + ((n_ex + 1) & ~1) + (size_t)(kSolveBlock / kWave) * (kPoolWords * kWave);
+    int *s_grp = reinterpret_cast<int *>(s_sum2 + kSolveBlock);
+    if (SHARE && threadIdx.x < 2 * sh->n_solve) s_grp[threadIdx.x] = sh->groups[threadIdx.x];
     __syncthreads();
     // the wave's pool of STARTED items (solve_sched.h): a ring of 64 slots of kPoolWords words
     double *s_pool = s_S0 + ((n_ex + 1) & ~1) + (size_t)(threadIdx.x >> 6) * (kPoolWords * kWave);
     const unsigned n_stiff = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[0]) : 0u;
     unsigned n_solo = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[1]) : 0u;
     if (n_solo > a.solo_cap) n_solo = a.solo_cap;   // the overflow went onto the ordinary list (stiff_list_append)
-    MMOps<WRITE_PRED, EXACT, FAST> ops{mm, a, s_tp, s_S0, (long long)a.n, n_ex, own_sgpr(n_t), a.stiff_list, n_stiff,
+    MMOps<WRITE_PRED, EXACT, FAST, SHARE> ops{mm, a, s_tp, s_S0, (long long)a.n, SHARE ? sh->n_solve : n_ex, own_sgpr(n_t), a.stiff_list, n_stiff,
                                  a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, own_sgpr(mm.rtol), own_sgpr(mm.atol),
                                  own_sgpr(a.patience),
                                  a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : (long long)a.n,
-                                 own_sgpr(a.sum_r2), own_sgpr(a.info)};
+                                 own_sgpr(a.sum_r2), own_sgpr(a.info), SHARE ? s_sum2 : nullptr, SHARE ? s_grp : nullptr};
     solve_persistent(ops, a.queue, s_pool);
 }
 // The kernel: the primary template serves the parity arithmetic (EXACT: 164 VGPRs, three waves per SIMD); the default-mode
@@ -702,6 +770,22 @@ __global__ void __launch_bounds__(kSolveBlock) mm_solve_kernel(MMModel mm, Solve
 SMC_SOLVE_DEFAULT_MODE(false, false)     // (the WRITE_PRED instantiations - predictions for the drop-in's plots - stay with the primary template)
 SMC_SOLVE_DEFAULT_MODE(false, true)
 #undef SMC_SOLVE_DEFAULT_MODE
+#endif
+// The same kernels for a sweep that shares the solves of replicate experiments (ShareArgs): instantiations of their own, chosen at
+// launch, so that a data set without replicates (or smc_set_share_replicates(0)) runs exactly the code above.
+template <bool WRITE_PRED, bool EXACT, bool FAST>
+__global__ void __launch_bounds__(kSolveBlock) mm_solve_share_kernel(MMModel mm, SolveArgs a, ShareArgs sh) {
+    mm_solve_body<WRITE_PRED, EXACT, FAST, true>(mm, a, &sh);
+}
+#ifndef SMC_NO_OWN_SGPR
+#define SMC_SOLVE_SHARE_DEFAULT_MODE(WP, F)                                                                                        \
+    template <>                                                                                                                    \
+    __global__ void __launch_bounds__(kSolveBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) mm_solve_share_kernel<WP, false, F>(MMModel mm, SolveArgs a, ShareArgs sh) { \
+        mm_solve_body<WP, false, F, true>(mm, a, &sh);                                                                             \
+    }
+SMC_SOLVE_SHARE_DEFAULT_MODE(false, false)
+SMC_SOLVE_SHARE_DEFAULT_MODE(false, true)
+#undef SMC_SOLVE_SHARE_DEFAULT_MODE
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -762,11 +846,14 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                  const uint8_t *__restrict__ p0_in, double *lk_io, double *filt, int64_t fstride,
                  uint8_t *r_ac, SweepCounters *__restrict__ counters, double *__restrict__ dbg_lk2,
                  uint8_t *__restrict__ dbg_r, FinishTail tail) {
-    __shared__ unsigned long long s_cnt[4][5];
+    __shared__ unsigned long long s_cnt[4][6];
     __shared__ double s_mom[4][9];
     __shared__ int s_last;
     if (MODE == 1 && mh.ctl && mh.ctl->stop) return;   // after the loop's `break`: p_filt, lk1, r_ac and the counters stay as they are
     unsigned long long attempts = 0, failed = 0, acc_now = 0, acc_ever = 0, long_items = 0;
+    // attempts counted above that nobody executed: those of the partner experiments of a sharing sweep (ShareArgs), whose info words
+    // repeat their primary's count (mm.partner_mask: bit k = experiment k was solved as a partner; 0 when nothing is shared)
+    unsigned long long shared_attempts = 0;
     // (items whose solve ran to t_bound and produced its n_t dense outputs - bench.py's roofline numerator - are counted in a
     // 32-bit register and ride in the HIGH half of `failed` through the block reduction)
     unsigned solved = 0;
@@ -799,6 +886,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                 lk2 += mm_loglik_term(c0, NEX > 0 ? L.sum[NEX > 0 ? k : 0] : sum_r2[(int64_t)k * n + p], s2);          // :70-73
                 const int fl = NEX > 0 ? L.fl[NEX > 0 ? k : 0] : info[(int64_t)k * n + p];
                 attempts += (unsigned)(fl & kInfoAttemptsMask);
+                shared_attempts += ((unsigned)mm.partner_mask >> k) & 1u ? (unsigned)(fl & kInfoAttemptsMask) : 0u;
                 long_items += (unsigned)(fl & kInfoAttemptsMask) > (unsigned)kLongItemAttempts;
                 pf |= (unsigned)(fl >> 30) & 1u;
                 cancelled = cancelled || (fl & kInfoCancelled) != 0;
@@ -862,6 +950,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         acc_now += __shfl_down(acc_now, off);
         acc_ever += __shfl_down(acc_ever, off);
         long_items += __shfl_down(long_items, off);
+        shared_attempts += __shfl_down(shared_attempts, off);
     }
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -870,6 +959,7 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         s_cnt[w][2] = acc_now;
         s_cnt[w][3] = acc_ever;
         s_cnt[w][4] = long_items;
+        s_cnt[w][5] = shared_attempts;
     }
     if (acc_mom) {   // fixed-order block sums -> one row of 9 per block (deterministic; reduced by moments_reduce_kernel)
         double mv[9] = {m0, m1, m2, c00, c01, c02, c11, c12, c22};
@@ -890,12 +980,14 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
     if (acc_mom && threadIdx.x < 9)
         row_store(mh.moment_rows + (size_t)blockIdx.x * 9 + threadIdx.x,
                   ((s_mom[0][threadIdx.x] + s_mom[1][threadIdx.x]) + s_mom[2][threadIdx.x]) + s_mom[3][threadIdx.x]);
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < 6) {
         const unsigned long long v = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
         unsigned long long *row = tail.count_rows + (size_t)blockIdx.x * kFinishCountWords;
         if (threadIdx.x == 1) {      // low half: failed solves; high half: solves that produced their outputs
             row_store(row + 1, v & 0xffffffffULL);
             row_store(row + 5, v >> 32);
+        } else if (threadIdx.x == 5) {
+            row_store(row + 6, v);
         } else {
             row_store(row + threadIdx.x, v);
         }
@@ -906,13 +998,14 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
     __syncthreads();
     if (!s_last) return;
     {
-        unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
+        constexpr int kTot = 7;      // the six sweep counters, then the shared attempts
+        unsigned long long tot[kTot] = {0, 0, 0, 0, 0, 0, 0};
         for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
 #pragma unroll
-            for (int q = 0; q < 6; ++q) tot[q] += ctl_load<true>(tail.count_rows + (size_t)b * kFinishCountWords + q);
-        __shared__ unsigned long long s_tot[4][6];
+            for (int q = 0; q < kTot; ++q) tot[q] += ctl_load<true>(tail.count_rows + (size_t)b * kFinishCountWords + q);
+        __shared__ unsigned long long s_tot[4][kTot];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
+        for (int q = 0; q < kTot; ++q) {
             for (int off = 32; off > 0; off >>= 1) tot[q] += __shfl_down(tot[q], off);
             if ((threadIdx.x & 63) == 0) s_tot[w][q] = tot[q];
         }
@@ -926,6 +1019,10 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                                       : threadIdx.x == 4 ? &counters->long_items : &counters->solved_items;
             // (with its result: the addition has happened before the control step below reads the counters)
             if (v) s_tot[0][threadIdx.x] = atomicAdd(dst, v);
+        }
+        if (threadIdx.x == 6) {      // not a sweep counter: a running total beside the arrival counter (smc_mm_share_info)
+            const unsigned long long v = s_tot[0][6] + s_tot[1][6] + s_tot[2][6] + s_tot[3][6];
+            if (v) atomicAdd(reinterpret_cast<unsigned long long *>(tail.arrive) + kFinishSharedWord, v);
         }
         if (threadIdx.x == 0) __hip_atomic_store(tail.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -949,8 +1046,28 @@ static unsigned finish_grid(int64_t n) {
     const int64_t g = (n + 255) / 256, cap = SMC_FINISH_GRID_CAP;
     return (unsigned)(g < cap ? (g < 1 ? 1 : g) : cap);
 }
-// ctx->d_finish_rows: the count rows of the accept kernel's blocks, then its arrival counter (zero between kernels)
+// ctx->d_finish_rows: the count rows of the accept kernel's blocks, then its arrival counter (zero between kernels) and, one
+// 8-byte word behind it, the running total of shared attempts
+unsigned long long *finish_shared_attempts(const smc_ctx *ctx) {
+    return ctx->d_finish_rows + (size_t)SMC_FINISH_GRID_CAP * kFinishCountWords + kFinishSharedWord;
+}
 size_t finish_rows_bytes() { return ((size_t)SMC_FINISH_GRID_CAP * kFinishCountWords + 8) * sizeof(unsigned long long); }
+
+// dynamic LDS of the solve kernel: the (time, observation) table, S0, and the four waves' pools of started items
+// (sharing sweeps: the table widened by the partners' observations, one word per thread for the partner's sum, the group table)
+static size_t solve_lds_bytes(int n_ex, int n_t, bool share = false) {
+    return (size_t)(share ? 2 : 1) * n_ex * (n_t + 1) * sizeof(double2) + (size_t)((n_ex + 1) & ~1) * sizeof(double) +
+           (size_t)(kSolveBlock / kWave) * kPoolWords * kWave * sizeof(double) +
+           (share ? (size_t)kSolveBlock * sizeof(double) + 2 * kMaxEx * sizeof(int) : 0);
+}
+
+// Does a sweep of this context share the solves of replicate experiments, and how many solves per particle does it schedule?
+// (not where the widened table would not fit into the 128 KB of LDS a block may ask for: the largest data sets)
+static bool share_on(const smc_ctx *ctx) {
+    return ctx->share_replicates != 0 && !ctx->share_env_off && ctx->n_solve > 0 && ctx->n_solve < ctx->mm.n_ex && ctx->d_groups &&
+           solve_lds_bytes(ctx->mm.n_ex, ctx->mm.n_t, true) <= 128 * 1024;
+}
+int solves_per_particle(const smc_ctx *ctx) { return share_on(ctx) ? ctx->n_solve : ctx->mm.n_ex; }
 
 // accept kernel (MODE 0: likelihood only): n_ex of the data set as a template argument up to 8, any other through NEX = 0.
 // ctl_after: batch of iterations on one rank - the control step that follows this sweep, run by the kernel's last block.
@@ -969,7 +1086,9 @@ static void launch_finish(smc_ctx *ctx, const MHParams &mh, const double *theta,
         tail.ctl.n_rows = (int)grid;
         for (int i = 0; i < ctx->dim * ctx->dim; ++i) tail.wcov.w[i] = w_cov[i];
     }
-#define SMC_FIN(NEX) hipLaunchKernelGGL((mm_finish_kernel<MODE, NEX>), dim3(grid), dim3(256), 0, ctx->stream, ctx->mm, mh, theta, stride, n, \
+    MMModel mm = ctx->mm;
+    mm.partner_mask = share_on(ctx) ? ctx->partner_mask : 0;
+#define SMC_FIN(NEX) hipLaunchKernelGGL((mm_finish_kernel<MODE, NEX>), dim3(grid), dim3(256), 0, ctx->stream, mm, mh, theta, stride, n, \
                                         ctx->d_sum_r2, ctx->d_info, p0, lk, filt, fstride, r_ac, ctx->d_counters, dbg_lk2, dbg_r, tail)
     switch (ctx->mm.n_ex) {
         case 1: SMC_FIN(1); break;
@@ -983,12 +1102,6 @@ static void launch_finish(smc_ctx *ctx, const MHParams &mh, const double *theta,
         default: SMC_FIN(0); break;
     }
 #undef SMC_FIN
-}
-
-// dynamic LDS of the solve kernel: the (time, observation) table, S0, and the four waves' pools of started items
-static size_t solve_lds_bytes(int n_ex, int n_t) {
-    return (size_t)n_ex * (n_t + 1) * sizeof(double2) + (size_t)((n_ex + 1) & ~1) * sizeof(double) +
-           (size_t)(kSolveBlock / kWave) * kPoolWords * kWave * sizeof(double);
 }
 
 // Persistent grid of a sweep over n particles: enough blocks to fill every CU at the kernel's occupancy; for a small
@@ -1005,9 +1118,10 @@ static bool use_fast_tail(const smc_ctx *ctx, int64_t n) { return ctx->fast_tail
 
 static int64_t solve_grid_blocks(const smc_ctx *ctx, int64_t n) {
     const int64_t waves_per_block = kSolveBlock / kWave;
-    const int64_t items = ((n + kWave - 1) / kWave) * kWave * ctx->mm.n_ex;
+    const int n_solve = solves_per_particle(ctx);
+    const int64_t items = ((n + kWave - 1) / kWave) * kWave * n_solve;
     const int64_t chunks = (items + kChunk - 1) / kChunk;
-    const int64_t need = (chunks + waves_per_block - 1) / waves_per_block + (n * ctx->mm.n_ex + waves_per_block - 1) / waves_per_block;
+    const int64_t need = (chunks + waves_per_block - 1) / waves_per_block + (n * n_solve + waves_per_block - 1) / waves_per_block;
     int64_t blocks = (int64_t)ctx->cu_count * (use_fast_tail(ctx, n) ? ctx->solve_blocks_per_cu_fast : ctx->solve_blocks_per_cu);
     if (blocks > need) blocks = need;
     return blocks < 1 ? 1 : blocks;
@@ -1022,14 +1136,16 @@ static StiffList next_stiff_list(smc_ctx *ctx, int64_t n) {
     sl.count = ctx->d_stiff_count + 2 * ctx->stiff_parity;
     sl.count_next = ctx->d_stiff_count + 2 * (ctx->stiff_parity ^ 1);
     sl.cap = ctx->item_cap;
-    sl.solo_cap = (unsigned)(solve_grid_blocks(ctx, n) * (kSolveBlock / kWave) / ctx->mm.n_ex);   // one solo solve per wave
+    sl.solo_cap = (unsigned)(solve_grid_blocks(ctx, n) * (kSolveBlock / kWave) / solves_per_particle(ctx));   // one solo solve per wave
     return sl;
 }
 
 static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int64_t n, const uint8_t *p0, double *pred,
                          const StiffList &sl, bool queue_cleared = false, bool reject = false, int patience = 0,
                          const int32_t *order = nullptr, bool cost_ordered = false, const MHControl *ctl = nullptr) {
-    const MMModel &mm = ctx->mm;
+    const bool share = share_on(ctx);
+    MMModel mm = ctx->mm;
+    mm.partner_mask = 0;        // (read by the accept kernel only)
     SolveArgs a{};
     a.theta = theta;
     a.stride = stride;
@@ -1054,19 +1170,25 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
     if (const char *e = getenv("SMC_DEBUG_PATIENCE")) a.patience = atoi(e);
 #endif
     if (!queue_cleared) (void)hipMemsetAsync(ctx->d_queue, 0, sizeof(unsigned long long), ctx->stream);
-    const size_t lds = solve_lds_bytes(mm.n_ex, mm.n_t);
+    const size_t lds = solve_lds_bytes(mm.n_ex, mm.n_t, share);
     const bool exact = ctx->exact_pow != 0;
     const bool fast = use_fast_tail(ctx, n);
     void (*kern)(MMModel, SolveArgs) =
         pred ? (exact ? mm_solve_kernel<true, true, false> : fast ? mm_solve_kernel<true, false, true> : mm_solve_kernel<true, false, false>)
              : (exact ? mm_solve_kernel<false, true, false> : fast ? mm_solve_kernel<false, false, true> : mm_solve_kernel<false, false, false>);
+    void (*kern_share)(MMModel, SolveArgs, ShareArgs) =
+        pred ? (exact ? mm_solve_share_kernel<true, true, false> : fast ? mm_solve_share_kernel<true, false, true> : mm_solve_share_kernel<true, false, false>)
+             : (exact ? mm_solve_share_kernel<false, true, false> : fast ? mm_solve_share_kernel<false, false, true> : mm_solve_share_kernel<false, false, false>);
     if (lds > 48 * 1024 && !ctx->solve_lds_raised) {
         // the largest data set (16 x 256) needs 66 + 30 KB of the CU's 160 KB: above the default dynamic limit.  The
         // attribute belongs to the (function, device) pair, so the flag lives in the context, not in the process.
         hipError_t e = hipSuccess;
         for (const void *f : {reinterpret_cast<const void *>(&mm_solve_kernel<true, true, false>), reinterpret_cast<const void *>(&mm_solve_kernel<true, false, false>),
                               reinterpret_cast<const void *>(&mm_solve_kernel<true, false, true>), reinterpret_cast<const void *>(&mm_solve_kernel<false, true, false>),
-                              reinterpret_cast<const void *>(&mm_solve_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_kernel<false, false, true>)})
+                              reinterpret_cast<const void *>(&mm_solve_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_kernel<false, false, true>),
+                              reinterpret_cast<const void *>(&mm_solve_share_kernel<true, true, false>), reinterpret_cast<const void *>(&mm_solve_share_kernel<true, false, false>),
+                              reinterpret_cast<const void *>(&mm_solve_share_kernel<true, false, true>), reinterpret_cast<const void *>(&mm_solve_share_kernel<false, true, false>),
+                              reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, true>)})
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (e != hipSuccess) {
             smc_fail(ctx, "mm_solve_kernel: raising the dynamic LDS limit failed (hipFuncSetAttribute)");
@@ -1077,7 +1199,10 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
     }
     const int64_t blocks = solve_grid_blocks(ctx, n);   // the waves go on until the queue is empty
     ScopedTimer tm(ctx, SMC_T_SOLVE);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kSolveBlock), lds, ctx->stream, mm, a);
+    if (share)
+        hipLaunchKernelGGL(kern_share, dim3((unsigned)blocks), dim3(kSolveBlock), lds, ctx->stream, mm, a, ShareArgs{ctx->d_groups, ctx->n_solve});
+    else
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kSolveBlock), lds, ctx->stream, mm, a);
 }
 
 void launch_mm_loglik(smc_ctx *ctx, const double *theta, int64_t stride, int64_t n, double *lk, double *pred) {

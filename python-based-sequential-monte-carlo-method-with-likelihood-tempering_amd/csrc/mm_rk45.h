@@ -96,20 +96,40 @@ __device__ __forceinline__ void mm_table_fill(double2 *s_tp, const double *t, co
                             : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);
     }
 }
+// The table of a sweep that shares the solves of replicate experiments (mm_dense_outputs, SHARE): every entry is widened by a
+// second pair that holds the observation of the experiment's PARTNER (its own where it has none) - the dense-output loop
+// fetches it from the address it already has.  groups: n_solve pairs (primary, partner or -1).
+template <bool SHARE>
+__device__ __forceinline__ const double2 &mm_table_at(const double2 *s_tp, int i) { return s_tp[SHARE ? 2 * i : i]; }
+__device__ __forceinline__ void mm_table_fill_shared(double2 *s_tp, const double *t, const double *P_obs, int n_ex, int n_t, int tid,
+                                                     int n_threads, const int *groups, int n_solve) {
+    for (int i = tid; i < n_ex * (n_t + 1); i += n_threads) {
+        const int e = i / (n_t + 1), k = i - e * (n_t + 1);
+        int e2 = e;
+        for (int g = 0; g < n_solve; ++g)
+            if (groups[2 * g] == e && groups[2 * g + 1] >= 0) e2 = groups[2 * g + 1];
+        s_tp[2 * i] = (k < n_t) ? make_double2(t[e * n_t + k], P_obs[e * n_t + k])
+                                : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);
+        s_tp[2 * i + 1] = make_double2(k < n_t ? P_obs[e2 * n_t + k] : 0.0, 0.0);
+    }
+}
 
 // Start an item: RungeKutta.__init__ (rk.py:96-104) incl. select_initial_step (common.py:68-134,
 // direction +1, order 4, max_step inf) and the head of the first _step_impl (rk.py:120-127).
 // Returns false when there is nothing to integrate (t0 == t_bound, base.py:181-187): all outputs
 // are then already accumulated.
-template <bool WRITE_PRED, bool EXACT = false>
+// SHARE (a replicate pair solved once, see mm_dense_outputs), has_partner: the sum of the partner experiment on the
+// nothing-to-integrate path goes to *sum2, its predictions go to pred2.
+template <bool WRITE_PRED, bool EXACT = false, bool SHARE = false>
 __device__ __forceinline__ bool mm_item_begin(MMItem &it, double Vmax, double Km, double S0, const double2 *s_tp,
-                                              int t_off, int n_t, double rtol, double atol, double *pred) {
+                                              int t_off, int n_t, double rtol, double atol, double *pred, bool has_partner = false,
+                                              double *sum2 = nullptr, double *pred2 = nullptr) {
     it.negVmax = -Vmax;
     it.Km = Km;
     it.S0 = S0;
     it.t_off = t_off;
-    const double t0 = s_tp[t_off].x;
-    it.t_bound = s_tp[t_off + n_t - 1].x;
+    const double t0 = mm_table_at<SHARE>(s_tp, t_off).x;
+    it.t_bound = mm_table_at<SHARE>(s_tp, t_off + n_t - 1).x;
     it.t = t0;
     it.y = S0;
     it.f = mm_rhs(S0, it.negVmax, Km);
@@ -136,11 +156,16 @@ __device__ __forceinline__ bool mm_item_begin(MMItem &it, double Vmax, double Km
         it.h_abs = py_min(py_min(100.0 * h0, h1), interval);
     }
     if (it.t == it.t_bound) {  // every t_eval <= t gets y
-        while (it.i_out < n_t && s_tp[t_off + it.i_out].x <= it.t) {
+        while (it.i_out < n_t && mm_table_at<SHARE>(s_tp, t_off + it.i_out).x <= it.t) {
             const double P_model = S0 - it.y;
             if (WRITE_PRED) pred[it.i_out] = P_model;
-            const double r = s_tp[t_off + it.i_out].y - P_model;
+            const double r = mm_table_at<SHARE>(s_tp, t_off + it.i_out).y - P_model;
             it.sum_r2 += r * r;
+            if (SHARE && has_partner) {
+                if (WRITE_PRED) pred2[it.i_out] = P_model;
+                const double r2 = s_tp[2 * (t_off + it.i_out) + 1].x - P_model;
+                *sum2 += r2 * r2;
+            }
             ++it.i_out;
         }
         return false;
@@ -208,14 +233,30 @@ __device__ __forceinline__ RkStages rk_attempt_core_exact(double y, double k0, d
 
 // The outputs with t_eval in (t_old, t_new] of an accepted step (ivp.py:700-720, rk.py:561-574): quartic interpolant,
 // residual against the observation, running sum.  LEAN_X: see the caller.
-template <bool WRITE_PRED, bool LEAN_X>
+// SHARE: the item stands for a PAIR of replicate experiments (same S0, same times, bitwise: the same trajectory attempt for
+// attempt), of which only the observations differ: S and P_model are computed once and the residual is formed against both
+// rows - the partner's observation sits beside the primary's in the widened table (mm_table_fill_shared: one more ds_read_b64
+// from the address the loop already has; an experiment without partner finds its own observation there and the second sum is
+// never published).  it.t_off then carries the partner's distance in experiments in its bits 16.. (kSharePartnerShift; 0 = no
+// partner: where the partner's predictions and results go), and the partner's running sum lives in a lane-private word of LDS (*sum2_word: loaded here, stored back here, read when the item is published) so that it does not
+// occupy a register pair across the attempt.  The word needs no reset: an item without outputs so far (i_out == 0) has sum 0.
+constexpr int kSharePartnerShift = 16;
+template <bool WRITE_PRED, bool LEAN_X, bool SHARE>
 __device__ __forceinline__ void mm_dense_outputs(MMItem &it, const double2 *s_tp, double t_old, double t_new, double hd,
-                                                 double y_old, double Q0, double Q1, double Q2, double Q3, double *pred) {
+                                                 double y_old, double Q0, double Q1, double Q2, double Q3, double *pred, int n_t,
+                                                 double *sum2_word) {
     int i_out = it.i_out;
-    const int base = it.t_off;
+    const int base = SHARE ? (it.t_off & ((1 << kSharePartnerShift) - 1)) : it.t_off;
+    const int d_e = SHARE ? (it.t_off >> kSharePartnerShift) : 0;
     double t_next = it.t_next;
     double sum_r2 = it.sum_r2;
-    double P_obs = s_tp[base + i_out].y;
+    double P_obs = mm_table_at<SHARE>(s_tp, base + i_out).y;
+    double sum2 = 0.0, P_obs2 = 0.0;
+    if (SHARE) {
+        const double carried = *sum2_word;
+        sum2 = i_out == 0 ? 0.0 : carried;
+        P_obs2 = s_tp[2 * (base + i_out) + 1].x;
+    }
     do {
         const double num = t_next - t_old;
         const double x = LEAN_X ? lean_div6(num, hd) : num / hd;
@@ -225,20 +266,27 @@ __device__ __forceinline__ void mm_dense_outputs(MMItem &it, const double2 *s_tp
         if (WRITE_PRED) pred[i_out] = P_model;
         const double r = P_obs - P_model;
         sum_r2 += r * r;
+        if (SHARE) {
+            if (WRITE_PRED && d_e != 0) pred[d_e * n_t + i_out] = P_model;
+            const double r2 = P_obs2 - P_model;
+            sum2 += r2 * r2;
+        }
         ++i_out;
-        const double2 nx = s_tp[base + i_out];   // i_out == n_t reads the sentinel (+inf, 0)
+        const double2 nx = mm_table_at<SHARE>(s_tp, base + i_out);   // i_out == n_t reads the sentinel (+inf, 0)
         t_next = nx.x;
         P_obs = nx.y;
+        if (SHARE) P_obs2 = s_tp[2 * (base + i_out) + 1].x;
     } while (t_next <= t_new);
+    if (SHARE) *sum2_word = sum2;
     it.sum_r2 = sum_r2;
     it.i_out = i_out;
     it.t_next = t_next;
 }
 
 // The dense output of an accepted step that covers data times: Q = K.T.dot(P) (rk.py:179), then mm_dense_outputs.
-template <bool WRITE_PRED, int DIV>
+template <bool WRITE_PRED, int DIV, bool SHARE>
 __device__ __forceinline__ void mm_attempt_outputs(MMItem &it, const double2 *s_tp, const RkStages &st, double k0, double t_old,
-                                                   double t_new, double y_old, double *pred) {
+                                                   double t_new, double y_old, double *pred, int n_t, double *sum2_word) {
     const double k2 = st.k2, k3 = st.k3, k4 = st.k4, k5 = st.k5, k6 = st.k6;
     // P[1][:] = 0 and P[j][0] = 0 for j > 0
     const double Q0 = k0;
@@ -258,16 +306,16 @@ __device__ __forceinline__ void mm_attempt_outputs(MMItem &it, const double2 *s_
     // ulp of |t_old| >= 2^-400.  Two copies of the loop rather than a select per output.
     const bool lean_x = (DIV != kDivIeee) && hd >= 0x1p-400 && hd <= 0x1p400 && (t_old == 0.0 || fabs(t_old) >= 0x1p-400);
     if (lean_x)
-        mm_dense_outputs<WRITE_PRED, true>(it, s_tp, t_old, t_new, hd, y_old, Q0, Q1, Q2, Q3, pred);
+        mm_dense_outputs<WRITE_PRED, true, SHARE>(it, s_tp, t_old, t_new, hd, y_old, Q0, Q1, Q2, Q3, pred, n_t, sum2_word);
     else
-        mm_dense_outputs<WRITE_PRED, false>(it, s_tp, t_old, t_new, hd, y_old, Q0, Q1, Q2, Q3, pred);
+        mm_dense_outputs<WRITE_PRED, false, SHARE>(it, s_tp, t_old, t_new, hd, y_old, Q0, Q1, Q2, Q3, pred, n_t, sum2_word);
 }
 
 // One step attempt.  Returns 0 while the item is still running, 1 when it finished (t reached
 // t_bound), 2 when it failed (step size underflow, rk.py:133-134; SciPy status -1).
-template <bool WRITE_PRED, int DIV = kDivLean6, bool EXACT = false>
+template <bool WRITE_PRED, int DIV = kDivLean6, bool EXACT = false, bool SHARE = false>
 __device__ __forceinline__ int mm_item_attempt(MMItem &it, const double2 *s_tp, int n_t, double rtol, double atol,
-                                               double *pred) {
+                                               double *pred, double *sum2_word = nullptr) {
     // rk.py:133-134 TOO_SMALL_STEP (plus the hard attempt bound): tested together with the other rare
     // conditions in the single branch below; the stages computed meanwhile are simply discarded
     const bool fail = it.h_abs < it.min_step || it.attempts >= RK_MAX_ATTEMPTS;
@@ -298,7 +346,7 @@ __device__ __forceinline__ int mm_item_attempt(MMItem &it, const double2 *s_tp, 
             accept = st.error_norm < 1.0;
         }
         // ---- outputs with t_eval in (t_old, t] (ivp.py:700-720) by the quartic interpolant ----
-        if (accept && it.t_next <= t_new) mm_attempt_outputs<WRITE_PRED, DIV>(it, s_tp, st, k0, t, t_new, y, pred);
+        if (accept && it.t_next <= t_new) mm_attempt_outputs<WRITE_PRED, DIV, SHARE>(it, s_tp, st, k0, t, t_new, y, pred, n_t, sum2_word);
     }
     double fac_acc = py_min(10.0, pw);
     fac_acc = it.rejected ? py_min(1.0, fac_acc) : fac_acc;

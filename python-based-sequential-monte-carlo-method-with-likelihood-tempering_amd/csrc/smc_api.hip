@@ -14,6 +14,7 @@
 #include <new>
 
 #include "exchange_plan.h"
+#include "replicate_groups.h"
 #include "smc_internal.h"
 #include "stage_kernels.h"
 
@@ -184,6 +185,10 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
     c->dim = dim;
     c->n_local = n_local;
     c->n_global = n_global;
+    {   // unset = on; 0 = off whatever smc_set_share_replicates says later (A/B runs of one build under an unchanged caller)
+        const char *e = getenv("SMC_SHARE_REPLICATES");
+        c->share_env_off = e ? atoi(e) == 0 : false;
+    }
 #define CK(call)                                   \
     do {                                           \
         hipError_t e_ = (call);                    \
@@ -209,6 +214,7 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
     CK(hipMalloc(&c->d_finish_rows, finish_rows_bytes()));
     CK(hipMemsetAsync(c->d_finish_rows, 0, finish_rows_bytes(), c->stream));   // the arrival counter is zero between kernels
     CK(hipMalloc(&c->d_reject, sizeof(RejectArgs)));
+    CK(hipMalloc(&c->d_groups, 2 * kMaxEx * sizeof(int)));
     CK(hipMalloc(&c->d_stiff_count, 4 * sizeof(unsigned)));
     CK(hipMemsetAsync(c->d_stiff_count, 0, 4 * sizeof(unsigned), c->stream));
     CK(hipMalloc(&c->d_p0, (size_t)n_local));
@@ -312,6 +318,7 @@ void smc_destroy(smc_ctx *c) {
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_finish_rows);
     (void)hipFree(c->d_reject);
+    (void)hipFree(c->d_groups);
     (void)hipFree(c->d_stiff_count);
     (void)hipFree(c->d_order);
     (void)hipFree(c->d_bucket);
@@ -381,6 +388,17 @@ int smc_set_model_mm(smc_ctx *c, const double *t, const double *P_obs, const dou
     HIPC(c, hipMemcpyAsync(c->d_t, t, nb, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_P, P_obs, nb, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_S0, S0, n_ex * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    {   // replicate experiments: one solve per group (replicate_groups.h; mm_kernels.hip: ShareArgs)
+        int primary[kMaxEx], partner[kMaxEx];
+        c->n_solve = group_replicates(t, S0, n_ex, n_t, primary, partner);
+        c->partner_mask = 0;
+        for (int g = 0; g < kMaxEx; ++g) {
+            c->groups[2 * g] = g < c->n_solve ? primary[g] : -1;
+            c->groups[2 * g + 1] = g < c->n_solve ? partner[g] : -1;
+            if (g < c->n_solve && partner[g] >= 0) c->partner_mask |= 1 << partner[g];
+        }
+        HIPC(c, hipMemcpyAsync(c->d_groups, c->groups, sizeof c->groups, hipMemcpyHostToDevice, c->stream));
+    }
     HIPC(c, hipStreamSynchronize(c->stream));
     c->mm.t = c->d_t;
     c->mm.P_obs = c->d_P;
@@ -538,6 +556,28 @@ int smc_set_fast_tail(smc_ctx *c, int enable) {
     c->fast_tail = enable != 0;
     return 0;
 }
+int smc_set_share_replicates(smc_ctx *c, int enable) {
+    if (!c) return fail(nullptr, "NULL context");
+    c->share_replicates = enable != 0;
+    return 0;
+}
+int smc_mm_group_replicates(const double *t, const double *S0, int n_ex, int n_t, int *primary, int *partner) {
+    if (!t || !S0 || !primary || !partner || n_ex < 1 || n_t < 1) return -1;
+    return group_replicates(t, S0, n_ex, n_t, primary, partner);
+}
+int smc_mm_share_info(smc_ctx *c, int *n_solve, int64_t *shared_attempts) {
+    if (!c) return fail(nullptr, "NULL context");
+    if (!c->have_model || c->model_kind != 1) return fail(c, "smc_set_model_mm has not been called");
+    HIPC(c, hipSetDevice(c->device));
+    if (n_solve) *n_solve = solves_per_particle(c);
+    if (shared_attempts) {
+        unsigned long long v = 0;
+        HIPC(c, hipMemcpyAsync(&v, finish_shared_attempts(c), sizeof v, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        *shared_attempts = (int64_t)v;
+    }
+    return 0;
+}
 int smc_set_stiff_first(smc_ctx *c, int enable) {
     if (!c) return fail(nullptr, "NULL context");
     c->stiff_first = enable != 0;
@@ -611,6 +651,14 @@ int smc_download_item_info(smc_ctx *c, int32_t *info, int64_t n) {
     HIPC(c, hipSetDevice(c->device));
     // the last sweep wrote item (e, p) at e * n_sweep + p; the caller passes the particle count of that sweep
     HIPC(c, hipMemcpyAsync(info, c->d_info, (size_t)n * c->mm.n_ex * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+int smc_download_item_sums(smc_ctx *c, double *sums, int64_t n) {
+    if (!c) return fail(nullptr, "NULL context");
+    if (c->model_kind != 1 || !c->d_sum_r2 || n < 0 || n > c->item_cap) return fail(c, "smc_download_item_sums: Michaelis-Menten sweeps only, n <= particles of the last sweep");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(sums, c->d_sum_r2, (size_t)n * c->mm.n_ex * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1813,6 +1861,8 @@ int smc_timing_reset(smc_ctx *c) {
         c->t_ms[i] = 0.0;
     }
     c->w_solved_items = c->w_rk_attempts = c->w_solve_launches = c->w_noop_launches = 0;
+    HIPC(c, hipMemsetAsync(finish_shared_attempts(c), 0, sizeof(unsigned long long), c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 int smc_timing_get(smc_ctx *c, int which, int64_t *launches, double *total_ms) {

@@ -26,6 +26,7 @@ struct MMModel {     // passed by value to the sweep kernel
     const double *P_obs;  // n_ex*n_t (device)
     const double *S0;     // n_ex (device)
     int n_ex, n_t, est_sigma;
+    int partner_mask;     // accept kernel of a sweep that shared replicate solves: bit k = experiment k was a partner (else 0)
     double sigma_fixed, rtol, atol;
 };
 
@@ -245,6 +246,12 @@ struct smc_ctx {
     int stiff_first = 1;                   // hand the predictably long solves out first (smc_set_stiff_first)
     int in_phase = 1;                      // let homogeneous Metropolis sweeps run their waves in phase (solve_sched.h: patience)
     int64_t last_sweep_items = 0, last_sweep_long_items = 0, pending_sweep_items = 0;   // of the last finished MM Metropolis sweep
+    // replicate experiments (replicate_groups.h): solve groups of the data set, as (primary, partner or -1) pairs on host and device
+    int share_replicates = 1;              // one integration per group (smc_set_share_replicates) ...
+    bool share_env_off = false;            // ... unless the environment says SMC_SHARE_REPLICATES=0
+    int n_solve = 0, partner_mask = 0;
+    int groups[2 * smc::kMaxEx]{};
+    int *d_groups = nullptr;
     int exact_pow = 0;                     // parity mode: correctly rounded pow(x, -0.2) in the step controller (smc_set_exact_pow)
     bool solve_lds_raised = false;         // hipFuncAttributeMaxDynamicSharedMemorySize raised on THIS device
     int cu_count = 0, solve_blocks_per_cu = 0, solve_blocks_per_cu_fast = 0;   // persistent blocks per CU of the two kinds of mm_solve_kernel
@@ -296,6 +303,8 @@ void launch_mm_loglik(smc_ctx *ctx, const double *theta, int64_t stride, int64_t
 // this sweep on one rank (its rows / n_rows are filled in here); the accept kernel's last block runs it, no launch of its own
 void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh, const MHControlArgs *ctl_after = nullptr, const double *w_cov = nullptr);
 size_t finish_rows_bytes();                 // mm_kernels.hip: size of ctx->d_finish_rows
+int solves_per_particle(const smc_ctx *ctx);   // mm_kernels.hip: solves a sweep schedules per particle (groups of replicates, or n_ex)
+unsigned long long *finish_shared_attempts(const smc_ctx *ctx);   // ... and its running total of shared attempts (smc_mm_share_info)
 int query_solve_blocks_per_cu(bool fast);
 // in-phase patience of homogeneous and of cost-ordered sweeps (solve_sched.h; profiles/r03_ab_patience.log, r03_ab_cost_order.log)
 constexpr int kInPhasePatience = 12;

@@ -60,6 +60,8 @@ class SMCSettings:
     ess_search: str = "backoff"       # the reference's geometric back-off (main:111-144) | "bisection"
     ess_bisect_tol: float = 1e-9      # bisection: bracket width in gamma at which the search stops
     early_reject: bool = True         # stop a solve once its proposal is certainly rejected (exact; HipEngine.set_early_reject)
+    share_replicates: bool = True     # one integration per pair of replicate experiments (same results; HipEngine.set_share_replicates;
+                                      # the environment variable SMC_SHARE_REPLICATES=0 turns it off whatever this says)
     stiff_first: bool = True          # hand the predictably long solves out first (same results; HipEngine.set_stiff_first)
     in_phase: bool = True             # homogeneous Metropolis sweeps run their waves in phase (same results; HipEngine.set_in_phase)
     cost_order: bool = True           # heterogeneous ones hand their solves out by cost class, in phase (same results; set_cost_order)
@@ -349,6 +351,10 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
         engine.set_early_reject(s.early_reject)
     if hasattr(engine, "set_stiff_first"):
         engine.set_stiff_first(s.stiff_first)
+    mm_shared0 = None                 # Michaelis-Menten: the engine's running count of attempts that were shared, not executed
+    if getattr(engine, "model", ("",))[0] == "mm" and hasattr(engine, "set_share_replicates"):
+        engine.set_share_replicates(s.share_replicates)
+        mm_shared0 = engine.share_info()["rk_attempts_shared"]
     if hasattr(engine, "set_in_phase"):
         engine.set_in_phase(s.in_phase)
     if hasattr(engine, "set_cost_order"):
@@ -545,6 +551,8 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     if gamma_new < 1.0 and verbose and rank == 0:
         log("tempering does't complete: last gamma =", gamma_new)             # :270-271
     engine.synchronize()
+    if mm_shared0 is not None:        # rk_attempts counts per experiment, as the reference does: this many of them were not executed
+        stats["rk_attempts_shared"] = engine.share_info()["rk_attempts_shared"] - mm_shared0
     if dump_dir:                                                              # SavePosteriorcsv, :434-436
         final = engine.download_particles(SMC_SET_PRED)
         _dump(dump_dir, "pred/last_p_pred", final, rank, world)

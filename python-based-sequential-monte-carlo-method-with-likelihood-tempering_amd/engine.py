@@ -336,6 +336,21 @@ class HipEngine:
             return
         self._ck(self.L.smc_set_fast_tail(self.ctx, int(bool(enable))), "smc_set_fast_tail")
 
+    def set_share_replicates(self, enable=True):
+        """One integration per group of replicate Michaelis-Menten experiments (include/smc_hip.h: smc_set_share_replicates)."""
+        if "smc_set_share_replicates" in B.MISSING:    # A/B build of an earlier revision (SMC_HIP_LIB)
+            return
+        self._ck(self.L.smc_set_share_replicates(self.ctx, int(bool(enable))), "smc_set_share_replicates")
+
+    def share_info(self):
+        """{"n_solve": solves per particle a Michaelis-Menten sweep schedules now, "rk_attempts_shared": device-counted attempts
+        since timing_reset() that rk_attempts contains but nobody executed - the partners' copies} (smc_mm_share_info)."""
+        if "smc_mm_share_info" in B.MISSING:           # A/B build of an earlier revision (SMC_HIP_LIB)
+            return {"n_solve": self.model[1], "rk_attempts_shared": 0}
+        ns, sh = ctypes.c_int(0), ctypes.c_int64(0)
+        self._ck(self.L.smc_mm_share_info(self.ctx, ctypes.byref(ns), ctypes.byref(sh)), "smc_mm_share_info")
+        return {"n_solve": ns.value, "rk_attempts_shared": sh.value}
+
     def set_stiff_first(self, enable=True):
         """Hand the predictably long Michaelis-Menten solves out first (include/smc_hip.h: smc_set_stiff_first)."""
         if "smc_set_stiff_first" in B.MISSING:     # A/B build of a revision before the stiff list (SMC_HIP_LIB)
@@ -389,6 +404,13 @@ class HipEngine:
         n = self.n_local if n is None else int(n)
         out = np.empty((self.model[1], n), dtype=np.int32)
         self._ck(self.L.smc_download_item_info(self.ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n), "smc_download_item_info")
+        return out
+
+    def download_item_sums(self, n=None):
+        """(n_ex, n) sums of squared residuals of the last Michaelis-Menten sweep (diagnostics; -1: cancelled solve)."""
+        n = self.n_local if n is None else int(n)
+        out = np.empty((self.model[1], n), dtype=np.float64)
+        self._ck(self.L.smc_download_item_sums(self.ctx, _dp(out), n), "smc_download_item_sums")
         return out
 
     def commit_filt_to_pred(self):
