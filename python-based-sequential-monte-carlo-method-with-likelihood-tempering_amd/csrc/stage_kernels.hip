@@ -313,6 +313,7 @@ struct ResampleArgs {
     int scheme;                // SMC_RESAMPLE_*
     const double *thr;         // multinomial: the N sorted thresholds (order statistics of N uniforms)
     int64_t n_thr;
+    double s_full;             // systematic / multinomial: a cumulative weight >= this is the final one, 1 by definition
 };
 
 __device__ __forceinline__ void resample_item(const ResampleArgs &a, double lk, double &resid, int64_t &cnt) {
@@ -376,16 +377,42 @@ __global__ void __launch_bounds__(kScanBlock) tile_exclusive_scan_kernel(T *__re
 }
 
 // number of systematic thresholds wrand + k/N (k >= 0) that are <= S   (:168-174)
+// The project's own schemes (systematic, multinomial: the running sum is the cumulative weight) hand out exactly the N
+// thresholds k = 0 .. N-1, each to a particle of positive weight:
+//   S == 0    nothing of positive weight lies below: no threshold yet - threshold 0 of wrand == 0 (RandomState.rand() can return
+//             0.0) waits for the first particle that carries weight instead of going to a weightless particle 0;
+//   S >= s_full = 1 - (N + 8) EPS    the final cumulative weight is 1 by definition and every threshold is below 1.  The computed
+//             sum of the w_i = e_i / sum_w differs from 1 by (2 N - 1) EPS / 2 at most, whatever the order of the two summations
+//             (N - 1 roundings in sum_w, one per quotient, N - 1 in the running sum, all terms positive), so the running sum of
+//             the last particle that carries weight - on whichever rank it lives - is at or above s_full, and every particle
+//             after it starts there: it receives the thresholds that a sum rounded below 1 would have left unassigned (the
+//             gather then filled their rows with zeros or stale rows), the weightless ones behind it nothing;
+//   min(.., N)    a sum rounded above 1, or wrand == 0 at S == 1, would otherwise count a threshold k = N: N + 1 offspring.
+// What this costs and what it does not promise.  The window (N + 8) EPS is sized by the bound for ANY order of summation; the
+// block trees used here are far more accurate, so the window is wider than it needs to be: at 10^8 particles it is 2.2e-8,
+// a little over two threshold spacings, and the last two or three thresholds can go to an earlier particle (one that carries
+// weight) than exact arithmetic would name.  "Only to a particle of positive weight" holds exactly where the running sum is
+// carried as S + w; the last item of a thread ends on the next thread's start value from the block scan, which may lie an ulp
+// above the carried sum, so a weightless particle in that slot can still catch a threshold that lies within that ulp (older than
+// this rule, and the tests cannot reach it: their weightless particles sit in patterns whose sums are exact).
+// The residual-systematic scheme keeps the reference's arithmetic, quirks included.
 __device__ __forceinline__ int64_t thresholds_below(double S, const ResampleArgs &a) {
+    if (a.scheme == SMC_RESAMPLE_RESIDUAL_SYSTEMATIC)
+        return (S >= a.wrand) ? (int64_t)floor((S - a.wrand) * a.n_global) + 1 : 0;
+    if (!(S > 0.0)) return 0;
+    if (S >= a.s_full) return a.n_thr;
+    int64_t m;
     if (a.scheme == SMC_RESAMPLE_MULTINOMIAL) {   // upper_bound over the sorted thresholds
         int64_t lo = 0, hi = a.n_thr;
         while (lo < hi) {
             const int64_t mid = (lo + hi) >> 1;
             if (a.thr[mid] <= S) lo = mid + 1; else hi = mid;
         }
-        return lo;
+        m = lo;
+    } else {
+        m = (S >= a.wrand) ? (int64_t)floor((S - a.wrand) * a.n_global) + 1 : 0;
     }
-    return (S >= a.wrand) ? (int64_t)floor((S - a.wrand) * a.n_global) + 1 : 0;
+    return m < a.n_thr ? m : a.n_thr;
 }
 
 // Multinomial thresholds: the order statistics of N iid uniforms are the normalised partial sums of N+1 iid
@@ -755,6 +782,7 @@ static ResampleArgs make_args(smc_ctx *c, double max_lk, double gm, double sum_w
     a.scheme = c->resampling;
     a.thr = c->d_mn_thr;
     a.n_thr = c->n_global;
+    a.s_full = 1.0 - ((double)c->n_global + 8.0) * 2.220446049250313e-16;
     return a;
 }
 void launch_resample_phase1(smc_ctx *c, double max_lk, double gm, double sum_w) {

@@ -337,6 +337,11 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     if predictive is not None and (getattr(engine, "model", None) is None or engine.model[0] != "user"):
         raise ValueError("run_smc: predictive= applies to a user model (HipEngine.set_model_user) only")
     s = s or SMCSettings()
+    # device RNG: iteration j of tempering step `step` draws from the Philox stream (step << 16) | j - one stream per iteration
+    # only while j < 2**16, and below the prior's and the predictive streams only while step < 2**16
+    if rng == "device" and max(s.mhstep_num, s.ad_mhstep_num, s.itr_max) > 65536:
+        raise ValueError("run_smc(rng='device'): mhstep_num, ad_mhstep_num and itr_max must not exceed 65536 - the Metropolis "
+                         "stream (step << 16) | j would repeat")
     comm = comm or SingleComm()
     n = s.n_particle
     d = s.num_est_params

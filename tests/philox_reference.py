@@ -70,3 +70,82 @@ def pred_noise_z(seed, global_offset, n, cells):
     x, y, z, w = philox_block_np(seed, g, stream, 0)
     u1, u2 = 1.0 - u01_from(x, y), u01_from(z, w)
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+# ---- the sampler's own draws (stage_kernels.hip, mm_kernels.hip, meth_smc.hip) ------------------------------------------
+# Integer work and the uniforms are exact; what goes through ln, sqrt, cos and sin is evaluated in np.longdouble, on the
+# doubles the kernels form (u1, u2 and the rounded product 6.283185307179586 u2), so the restatement is the more precise side.
+
+PRIOR_STREAM = 0xFFFFFFFF00000000       # sample_prior_kernel: | the component
+MN_STREAM = 0x5EED << 32                # mn_spacings_kernel's stream, under a key of its own (the bits of wrand)
+MN_BLOCK = 7
+BLOCK_UNIFORM = 255                     # SMC_PHILOX_BLOCK_UNIFORM: the acceptance uniform
+
+
+def _gidx(goff, n):
+    return np.uint64(goff) + np.arange(n, dtype=np.uint64)
+
+
+def box_muller(r):
+    """The pair (rad cos, rad sin) every normal of the sampler comes from, of one block r = (x, y, z, w): u1 = 1 - u01(x, y) in
+    (0, 1], u2 = u01(z, w), rad = sqrt(-2 ln u1), angle = the DOUBLE 6.283185307179586 u2; in np.longdouble."""
+    u1 = (1.0 - u01_from(r[0], r[1])).astype(np.longdouble)
+    ang = (6.283185307179586 * u01_from(r[2], r[3])).astype(np.longdouble)
+    rad = np.sqrt(-2 * np.log(u1))
+    return rad * np.cos(ang), rad * np.sin(ang)
+
+
+def prior_draw(seed, goff, n, kinds, a, b):
+    """sample_prior_kernel for particles goff .. goff + n - 1: component c from block 0 of the stream PRIOR_STREAM | c.
+    kinds: "uniform" (a = low, b = high) or anything else = drawn as a normal (a = mu, b = sigma).  Returns (x, u): x (n, d) in
+    np.longdouble - a + (b - a) u with the width b - a rounded to a double as the kernel forms it, a + b z for a normal - and u
+    (n, d), the exact first uniform of every block (what a test needs to round the uniform components itself)."""
+    g = _gidx(goff, n)
+    d = len(kinds)
+    x, u = np.empty((n, d), dtype=np.longdouble), np.empty((n, d))
+    for c in range(d):
+        r = philox_block_np(seed, g, PRIOR_STREAM | c, 0)
+        u[:, c] = u01_from(r[0], r[1])
+        if kinds[c] == "uniform":
+            x[:, c] = np.longdouble(a[c]) + np.longdouble(np.float64(b[c]) - np.float64(a[c])) * u[:, c].astype(np.longdouble)
+        else:
+            x[:, c] = np.longdouble(a[c]) + np.longdouble(b[c]) * box_muller(r)[0]
+    return x, u
+
+
+def mm_proposal_normals(seed, goff, n, stream):
+    """mm_propose_one: (n, 3) standard normals - cosine and sine of block 0, cosine of block 1."""
+    g = _gidx(goff, n)
+    c0, s0 = box_muller(philox_block_np(seed, g, stream, 0))
+    c1, _ = box_muller(philox_block_np(seed, g, stream, 1))
+    return np.stack([c0, s0, c1], axis=1)
+
+
+def generic_proposal_normals(seed, goff, n, stream, d):
+    """generic_propose_kernel: (n, d) standard normals - block b gives components 2 b (cosine) and 2 b + 1 (sine); for an odd d
+    the last sine is not used."""
+    g = _gidx(goff, n)
+    out = np.empty((n, d), dtype=np.longdouble)
+    for blk in range((d + 1) // 2):
+        cs, sn = box_muller(philox_block_np(seed, g, stream, blk))
+        out[:, 2 * blk] = cs
+        if 2 * blk + 1 < d:
+            out[:, 2 * blk + 1] = sn
+    return out
+
+
+def accept_uniform(seed, goff, n, stream):
+    """The acceptance uniform rr of particles goff .. goff + n - 1: u01 of the first two words of block 255.  Exact."""
+    r = philox_block_np(seed, _gidx(goff, n), stream, BLOCK_UNIFORM)
+    return u01_from(r[0], r[1])
+
+
+def multinomial_thresholds(wrand, N):
+    """mn_spacings_kernel + mn_thresholds_kernel: the key is the 64 bits of the double wrand = u / N; item i = 0 .. N (N + 1
+    spacings) draws block 7 of the stream 0x5EED << 32 and gives e_i = -ln(1 - u01); the thresholds are the first N partial sums
+    divided by the sum of all N + 1.  np.longdouble, sorted by construction."""
+    seed = int(np.array([wrand], dtype=np.float64).view(np.uint64)[0])
+    r = philox_block_np(seed, np.arange(N + 1, dtype=np.uint64), MN_STREAM, MN_BLOCK)
+    e = -np.log((1.0 - u01_from(r[0], r[1])).astype(np.longdouble))
+    c = np.cumsum(e)
+    return c[:N] / c[N]
