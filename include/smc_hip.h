@@ -178,6 +178,50 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
                          const double *prop_fixed);
 int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap);
 int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir);
+/* TIME-VARYING MEASURED INPUTS (additive; the functions above keep their behaviour): a feed rate, a temperature ramp, a logged
+ * inlet concentration - n_in = 1 .. SMC_USER_MAX_INPUTS profiles u_k(t) per experiment, linear between their knots, which the
+ * model reads from any of its functions (smc_user_y0, smc_user_rhs, smc_user_jac, smc_user_obs, smc_user_obs_vec) as
+ *   double smc_input(const double *cond, int k, double t);      input k in [0, n_in) of this experiment at time t
+ * `cond` is the pointer the function was handed - the handle to the experiment; cond[0 .. n_cond) read as before.  The value is
+ * np.interp(t, tk, u_k) over the row's finite knots tk[0] < ... < tk[m-1]: u[0] for t <= tk[0], u[m-1] for t >= tk[m-1], else
+ * with j the last knot <= t
+ *   u[j] + s_j (t - tk[j]),   s_j = (u[j+1] - u[j]) / (tk[j+1] - tk[j])   (the slope is formed once, on the host, by IEEE division);
+ * m = 1 is a constant.  It EQUALS u[j] at t == tk[j] and NEVER LEAVES [min(u[j], u[j+1]), max(u[j], u[j+1])] (clamped), and it
+ * is the same number in both namespaces of an RK45 source.  user_models.input_value is the definition in NumPy.  The
+ * integrators do NOT stop at knots: as solve_ivp with np.interp inside f, they step over the kinks under their own step
+ * control (a switch is a steep ramp between two close knots) - this is not SciPy-with-tstops, and there are no state resets.
+ * Data: in_t n_ex x n_knot, a row by the row rules of t (a strictly increasing finite run of at least one knot, then only NaN);
+ * in_u n_ex x n_knot x n_in, finite at the row's finite knots (and every slope finite) and ignored past them; n_knot <=
+ * SMC_USER_MAX_KNOTS.  Anything else fails with the row, the knot and the rule.  smc_user_input_check applies these rules alone
+ * (no GPU, no context: the reason is in smc_last_error(NULL)).
+ * smc_set_model_user5: the arguments of smc_set_model_user4, then est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot.  add_index ==
+ * NULL (then add_fixed, prop_index, prop_fixed NULL too) selects the sigma rule of smc_set_model_user3 (est_sigma / sigma_fixed),
+ * otherwise the noise model of smc_set_model_user4 applies.  n_in == 0 with in_t == in_u == NULL takes the existing function's
+ * path and gives its bits.  The table lies behind each experiment's cond numbers in device memory (n_cond + K + n_in (2 K + 1)
+ * doubles per experiment, K = the power of two >= n_knot: the compiled knot capacity); the LDS table and its limits are those
+ * of the function without inputs.  A source that calls smc_input is compiled only for a model with inputs: without them the
+ * compilation stops with "smc_input: this model has no inputs".  smc_loglik, smc_mh_step_*, early rejection, the cost hint,
+ * smc_user_predict and the BDF counters work as for every user model.
+ * check5 / dump_source5: as check4 / dump_source4 with noise = 0 (the sigma rule: the source of smc_set_model_user3), 1 (a noise
+ * model) or 2 (with a proportional part) and the geometry the source is compiled for: n_cond, n_in and n_knot (n_in = 0: a model
+ * without inputs; n_cond and n_knot are then not used).  dump_source5 also writes user_input.h.  No GPU needed.
+ * DESIGNS: t_new == NULL (the data's design) uses the data's inputs.  An explicit design of smc_user_predict_at /
+ * smc_user_predict_summary needs design inputs with the same n_ex_new, set beforehand by smc_user_set_design_inputs (in_t_new
+ * n_ex_new x n_knot_new, in_u_new n_ex_new x n_knot_new x n_in, the rules above; no row may hold more finite knots than K) and
+ * held until replaced; both pointers NULL clears them.  Without matching design inputs the call fails with the reason.  A design
+ * that runs in groups of experiments carries each group's rows of the table. */
+#define SMC_USER_MAX_INPUTS 8
+#define SMC_USER_MAX_KNOTS 4096
+int smc_set_model_user5(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                        const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
+                        const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
+                        int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot);
+int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n_in, int n_knot);
+int smc_user_model_check5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          char *log, int log_cap);
+int smc_user_model_dump_source5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, const char *dir);
+int smc_user_set_design_inputs(smc_ctx *ctx, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new);
 /* Model PREDICTIONS of a user model (any of the three set functions; RK45 or BDF), for n host particles (n x dim, AoS; any n -
  * run in chunks of n_local): lk[n] as smc_loglik computes it and, unless pred is NULL, pred[((p * n_ex + e) * n_t + i) * n_obs + k]
  * = output k at t[e][i], written for every finite time whether or not obs is measured there; NaN past a row's end and from

@@ -168,6 +168,23 @@ user_bdf_count_kernel(const uint8_t *__restrict__ p0mask, const unsigned *__rest
     if (threadIdx.x < 4 && s[threadIdx.x][0]) atomicAdd(totals + threadIdx.x, s[threadIdx.x][0]);
 }
 
+// The compile-time geometry of a model with inputs (user_input.h): the model's n_cond, n_in inputs, kcap = the power of two >=
+// n_knot.  n_in = 0: a model without inputs - its source and its cond rows are what they always were.
+struct UserInputGeom {
+    int n_cond = 0, n_in = 0, kcap = 0;
+    int row_words() const { return n_cond + kcap + n_in * (2 * kcap + 1); }
+};
+// the inputs as a set function receives them (nullptr: none)
+struct UserInputs {
+    const double *in_t, *in_u;      // n_ex x n_knot, n_ex x n_knot x n_in
+    int n_in, n_knot;
+};
+static int knot_capacity(int n_knot) {
+    int k = 1;
+    while (k < n_knot) k <<= 1;
+    return k;
+}
+
 struct UserModel {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
@@ -204,6 +221,12 @@ struct UserModel {
     // smc_set_model_user4: the noise model (user_obs_args.h); d_const then holds m_e, sum log s_k and m_ek [8 n_ex]
     bool noise = false;
     UserNoise nz{};
+    // smc_set_model_user5: time-varying inputs (user_input.h).  The table lies behind each experiment's cond row, so d_cond holds
+    // rows of geom.row_words() doubles; h_rows keeps the data's rows and design_* the inputs of an explicit design
+    UserInputGeom geom{};
+    std::vector<double> h_rows, design_t, design_u;
+    int design_n_ex = 0, design_n_knot = 0;
+    int cond_stride() const { return geom.n_in > 0 ? geom.row_words() : n_cond; }
 };
 
 // an optional ingredient (smc_user_cost, smc_user_jac, smc_user_obs_vec; smc_div): a source that mentions it must define it
@@ -213,9 +236,18 @@ static bool mentions(const char *user_source, const char *name) { return strstr(
 // text, and the method's kernel file.  n_obs = 0: the one-output source of smc_set_model_user / 2.  n_obs >= 1: the
 // multi-output source (smc_set_model_user3) - SMC_USER_NOBS selects the kernel file's multi-output blocks, and the file is
 // appended twice: the sweep kernel, then with SMC_USER_PRED 1 the prediction kernel smc_user_predict_kernel.
-static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs, int noise = 0) {
+// geom.n_in > 0 (smc_set_model_user5): SMC_USER_NCOND / NIN / KCAP and user_input.h in front, and smc_input made visible in the
+// namespace(s) of the user's text.  A source that calls smc_input without inputs is stopped by an #error that says so.
+static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs, int noise = 0,
+                                const UserInputGeom &geom = UserInputGeom()) {
     const bool bdf = method == SMC_USER_METHOD_BDF;
-    std::string s = "#define SMC_USER_NS " + std::to_string(n_states) + "\n#define SMC_USER_DIM " + std::to_string(dim) + "\n";
+    std::string s;
+    if (geom.n_in > 0)
+        s = "#define SMC_USER_NCOND " + std::to_string(geom.n_cond) + "\n#define SMC_USER_NIN " + std::to_string(geom.n_in) +
+            "\n#define SMC_USER_KCAP " + std::to_string(geom.kcap) + "\n#include \"user_input.h\"\n";
+    else if (mentions(user_source, "smc_input"))
+        s = "#error \"smc_input: this model has no inputs (n_in = 0) - set it with in_t / in_u through smc_set_model_user5\"\n";
+    s += "#define SMC_USER_NS " + std::to_string(n_states) + "\n#define SMC_USER_DIM " + std::to_string(dim) + "\n";
     if (n_obs > 0)
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
              ((n_obs > 1 || mentions(user_source, "smc_user_obs_vec")) ? "1\n" : "0\n");
@@ -225,7 +257,7 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
     if (!bdf) s += mentions(user_source, "smc_div") ? "#define SMC_USER_USES_DIV 1\n" : "#define SMC_USER_USES_DIV 0\n";
     // #line: hiprtc's diagnostics point into the user's text
-    const std::string text = std::string("#line 1 \"user_model\"\n") + user_source + "\n";
+    const std::string text = std::string(geom.n_in > 0 ? "using smc_in::smc_input;\n" : "") + "#line 1 \"user_model\"\n" + user_source + "\n";
     s += bdf ? kUserBdfPrelude + text : kUserPreludeLean + text + kUserPreludeIeee + text;
     s += "}  // namespace smc_user_ieee\n";
     const char *kernel = bdf ? k_user_bdf_kernel_h : k_user_rk45_kernel_h;
@@ -236,21 +268,25 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
 // the in-memory headers of a compilation, and with the source itself the files of a dump (smc_user_model_dump_source*)
 static const struct { const char *name, *text; } kUserHeaders[] = {
     {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"solve_sched.h", k_solve_sched_h},
-    {"rk45_math.h", k_rk45_math_h}, {"user_obs_args.h", k_user_obs_args_h}};
-// user_obs_args.h, the last one, goes with a multi-output source only
-static int user_header_count(int n_obs) { return (int)(sizeof kUserHeaders / sizeof *kUserHeaders) - (n_obs > 0 ? 0 : 1); }
+    {"rk45_math.h", k_rk45_math_h}, {"user_obs_args.h", k_user_obs_args_h}, {"user_input.h", k_user_input_h}};
+// user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs
+static int user_headers(int n_obs, const UserInputGeom &geom, const char **texts, const char **names) {
+    int n = 0;
+    for (const auto &h : kUserHeaders) {
+        if ((h.text == k_user_obs_args_h && n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0)) continue;
+        texts[n] = h.text;
+        names[n++] = h.name;
+    }
+    return n;
+}
 
 // compile build_source(...) for gfx950; on failure `log` holds hiprtc's diagnostics
 static bool compile_user(const char *user_source, int n_states, int dim, int method, int n_obs, std::vector<char> &code,
-                         std::string &log, int noise = 0) {
-    const std::string src = build_source(user_source, n_states, dim, method, n_obs, noise);
+                         std::string &log, int noise = 0, const UserInputGeom &geom = UserInputGeom()) {
+    const std::string src = build_source(user_source, n_states, dim, method, n_obs, noise, geom);
     hiprtcProgram prog;
     const char *headers[8], *names[8];
-    const int n_headers = user_header_count(n_obs);
-    for (int i = 0; i < n_headers; ++i) {
-        headers[i] = kUserHeaders[i].text;
-        names[i] = kUserHeaders[i].name;
-    }
+    const int n_headers = user_headers(n_obs, geom, headers, names);
     if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", n_headers, headers, names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return false;
@@ -325,7 +361,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     a.cond = u->d_cond;
     a.n_ex = u->n_ex;
     a.n_t = u->n_t;
-    a.n_cond = u->n_cond;
+    a.n_cond = u->cond_stride();      // the kernels know it as the stride of a cond row only
     a.dim = c->dim;
     a.est_sigma = u->est_sigma;
     a.sigma_fixed = u->sigma_fixed;
@@ -580,7 +616,8 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
     const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls,
                                                     u->noise ? &u->nz : nullptr);
-    const size_t nc = (size_t)g * (u->n_cond > 0 ? u->n_cond : 1) * sizeof(double);
+    const int cs = u->cond_stride();      // a model with inputs: cond holds whole rows, the table included
+    const size_t nc = (size_t)g * (cs > 0 ? cs : 1) * sizeof(double);
     dg.e0 = e0;
     dg.n_ex = g;
     dg.n_t = n_t;
@@ -589,8 +626,8 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
               hipMalloc(&dg.d_const, zero.size() * sizeof(double)) == hipSuccess &&
               hipMemcpy(dg.d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && u->n_cond > 0)
-        ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * u->n_cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && cs > 0)
+        ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * cs, nc, hipMemcpyHostToDevice) == hipSuccess;
     const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs, u->noise);
     int nb = 0;
     if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
@@ -632,7 +669,7 @@ static int ensure_pred_kernel(smc_ctx *c, UserModel *u, const char *who) {
     if (u->fn_pred) return 0;
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg))
+    if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg, 0, u->geom))
         return smc_fail(c, (std::string(who) + ": the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
     if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
         hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
@@ -669,11 +706,12 @@ static bool user_source_args_ok(const char *source, int n_states, int dim, int m
            (n_obs == 0 || user_obs_ok(n_obs));
 }
 
-static int user_model_check_impl(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap, int noise = 0) {
+static int user_model_check_impl(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap, int noise = 0,
+                                 const UserInputGeom &geom = UserInputGeom()) {
     if (!user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
     std::vector<char> code;
     std::string lg;
-    const bool ok = compile_user(source, n_states, dim, method, n_obs, code, lg, noise);
+    const bool ok = compile_user(source, n_states, dim, method, n_obs, code, lg, noise, geom);
     if (log && log_cap > 0) {
         strncpy(log, lg.c_str(), (size_t)log_cap - 1);
         log[log_cap - 1] = 0;
@@ -693,15 +731,34 @@ int smc_user_model_check3(const char *source, int n_states, int dim, int method,
 int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap) {
     return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, proportional ? 2 : 1);
 }
+// the geometry of check5 / dump_source5: false for arguments that are refused (return 2); n_in = 0 is a model without inputs
+static bool user_geom_of(int noise, int n_cond, int n_in, int n_knot, UserInputGeom &geom) {
+    if (noise < 0 || noise > 2 || n_cond < 0 || n_in < 0 || n_in > SMC_USER_MAX_INPUTS) return false;
+    if (n_in == 0) return true;
+    if (n_knot < 1 || n_knot > SMC_USER_MAX_KNOTS) return false;
+    geom.n_cond = n_cond;
+    geom.n_in = n_in;
+    geom.kcap = knot_capacity(n_knot);
+    return true;
+}
+int smc_user_model_check5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          char *log, int log_cap) {
+    UserInputGeom geom;
+    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
+    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
+}
 
 // everything hiprtc would read, as files: `hipcc -I <dir>` compiles <dir>/smc_user_model.hip off line
-static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0) {
+static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0,
+                                const UserInputGeom &geom = UserInputGeom()) {
     if (!dir || !user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
-    const std::string src = build_source(source, n_states, dim, method, n_obs, noise);
-    for (int i = -1; i < user_header_count(n_obs); ++i) {
-        FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : kUserHeaders[i].name)).c_str(), "w");
+    const std::string src = build_source(source, n_states, dim, method, n_obs, noise, geom);
+    const char *texts[8], *names[8];
+    const int n_headers = user_headers(n_obs, geom, texts, names);
+    for (int i = -1; i < n_headers; ++i) {
+        FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : names[i])).c_str(), "w");
         if (!f) return 1;
-        const bool ok = fputs(i < 0 ? src.c_str() : kUserHeaders[i].text, f) >= 0;
+        const bool ok = fputs(i < 0 ? src.c_str() : texts[i], f) >= 0;
         if (fclose(f) != 0 || !ok) return 1;
     }
     return 0;
@@ -718,6 +775,75 @@ int smc_user_model_dump_source3(const char *source, int n_states, int dim, int m
 }
 int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir) {
     return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, proportional ? 2 : 1);
+}
+int smc_user_model_dump_source5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, const char *dir) {
+    UserInputGeom geom;
+    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
+    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+}
+
+// the data rules of a model's inputs (include/smc_hip.h: smc_set_model_user5; user_models.input_layout is the same in NumPy):
+// in_t n_ex x n_knot, a row by the row rules of t; in_u n_ex x n_knot x n_in, finite at the row's finite knots.  On success m[e]
+// holds the knots of row e; "" = valid, else what is wrong.
+static std::string input_layout_error(const double *in_t, const double *in_u, int n_ex, int n_in, int n_knot, std::vector<int> &m) {
+    if (n_in < 1 || n_in > SMC_USER_MAX_INPUTS) return "n_in = " + std::to_string(n_in) + " outside 1 .. 8 (SMC_USER_MAX_INPUTS)";
+    if (n_knot < 1) return "n_knot = " + std::to_string(n_knot) + ": a row needs at least one knot";
+    if (n_knot > SMC_USER_MAX_KNOTS)
+        return "n_knot = " + std::to_string(n_knot) + " above the knot capacity " + std::to_string(SMC_USER_MAX_KNOTS) + " (SMC_USER_MAX_KNOTS)";
+    if (n_ex < 1) return "n_ex = " + std::to_string(n_ex) + ": no experiment";
+    if (!in_t || !in_u) return "NULL in_t or in_u";
+    m.assign(n_ex, 0);
+    for (int e = 0; e < n_ex; ++e) {
+        const double *te = in_t + (size_t)e * n_knot;
+        int len = 0;
+        while (len < n_knot && !std::isnan(te[len])) ++len;
+        const std::string row = "row " + std::to_string(e) + " of in_t ";
+        for (int i = len; i < n_knot; ++i)
+            if (!std::isnan(te[i]))
+                return row + "has a NaN knot before a number at knot " + std::to_string(i) + " (only a trailing run of NaN may shorten a row)";
+        if (len == 0) return row + "has no finite knot";
+        for (int i = 0; i < len; ++i) {
+            if (!std::isfinite(te[i])) return row + "holds an infinite knot at knot " + std::to_string(i);
+            if (i > 0 && !(te[i] > te[i - 1])) return row + "is not strictly increasing at knot " + std::to_string(i);
+        }
+        for (int i = 0; i < len; ++i)
+            for (int k = 0; k < n_in; ++k) {
+                const double *ue = in_u + ((size_t)e * n_knot + i) * n_in + k;
+                if (!std::isfinite(*ue))
+                    return "row " + std::to_string(e) + " of in_u is not finite at knot " + std::to_string(i) + " of input " + std::to_string(k);
+                if (i > 0 && !std::isfinite((ue[0] - ue[-(ptrdiff_t)n_in]) / (te[i] - te[i - 1])))
+                    return "row " + std::to_string(e) + " of in_u has a slope that overflows at knot " + std::to_string(i) + " of input " + std::to_string(k);
+            }
+        m[e] = len;
+    }
+    return "";
+}
+int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n_in, int n_knot) {
+    std::vector<int> m;
+    const std::string bad = input_layout_error(in_t, in_u, n_ex, n_in, n_knot, m);
+    return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_input_check: " + bad).c_str());
+}
+// The cond rows of a model with inputs (user_input.h) for inputs input_layout_error has accepted: per experiment the model's
+// n_cond numbers, the knots padded with +inf, and per input the values (u[m - 1] repeated past the end) and the slopes (IEEE
+// division, here and nowhere else; 0 from the last knot on).
+static std::vector<double> build_input_rows(const double *cond, const UserInputGeom &g, const double *in_t, const double *in_u, int n_ex,
+                                            int n_knot, const std::vector<int> &m) {
+    const int K = g.kcap, W = g.row_words();
+    std::vector<double> rows((size_t)n_ex * W, 0.0);
+    for (int e = 0; e < n_ex; ++e) {
+        double *r = rows.data() + (size_t)e * W;
+        for (int j = 0; j < g.n_cond; ++j) r[j] = cond[(size_t)e * g.n_cond + j];
+        const double *te = in_t + (size_t)e * n_knot;
+        double *tk = r + g.n_cond;
+        for (int j = 0; j < K; ++j) tk[j] = j < m[e] ? te[j] : HUGE_VAL;
+        for (int k = 0; k < g.n_in; ++k) {
+            double *u = r + g.n_cond + K + (size_t)k * (2 * K + 1), *sl = u + K + 1;
+            for (int j = 0; j <= K; ++j) u[j] = in_u[((size_t)e * n_knot + (j < m[e] ? j : m[e] - 1)) * g.n_in + k];
+            for (int j = 0; j < K; ++j) sl[j] = j < m[e] - 1 ? (u[j + 1] - u[j]) / (tk[j + 1] - tk[j]) : 0.0;
+        }
+    }
+    return rows;
 }
 
 // the rules of a noise specification (include/smc_hip.h: smc_set_model_user4; user_models.noise_layout is the same in NumPy):
@@ -748,7 +874,8 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
 // allows one.
 static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
-                               double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr) {
+                               double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr,
+                               const UserInputs *in = nullptr) {
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
@@ -766,10 +893,22 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
                             "rounded down to even) + 40 + 8 n_ex) x 8 B + pools): " +
                             std::to_string(user_lds_bytes3(n_states, n_ex, n_t, n_obs, true)) + " B needed, " + std::to_string(kUserLdsCap) +
                             " B available").c_str());
+    UserInputGeom geom;
+    std::vector<double> rows;      // the cond rows of a model with inputs, the table behind each
+    if (in) {
+        std::vector<int> knots;
+        const std::string bad_in = input_layout_error(in->in_t, in->in_u, n_ex, in->n_in, in->n_knot, knots);
+        if (!bad_in.empty()) return smc_fail(c, ("smc_set_model_user5: " + bad_in).c_str());
+        if (n_cond > 0 && !cond) return smc_fail(c, "smc_set_model_user5: n_cond > 0 and cond is NULL");
+        geom.n_cond = n_cond;
+        geom.n_in = in->n_in;
+        geom.kcap = knot_capacity(in->n_knot);
+        rows = build_input_rows(cond, geom, in->in_t, in->in_u, n_ex, in->n_knot, knots);
+    }
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(source, n_states, c->dim, method, multi ? n_obs : 0, code, lg, nz ? 1 + nz->prop : 0)) {
+    if (!compile_user(source, n_states, c->dim, method, multi ? n_obs : 0, code, lg, nz ? 1 + nz->prop : 0, geom)) {
         std::string msg = "user model does not compile:\n" + lg;
         if (msg.size() > 3500) msg.resize(3500);
         return smc_fail(c, msg.c_str());
@@ -788,12 +927,14 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         user_model_release(c);
         return smc_fail(c, "smc_set_model_user: the source mentions smc_user_cost but the scan kernel is missing from the module");
     }
-    const size_t nt = (size_t)n_ex * n_t * sizeof(double), nc = (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
+    const size_t nt = (size_t)n_ex * n_t * sizeof(double);
+    const size_t nc = in ? rows.size() * sizeof(double) : (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
     bool ok = hipMalloc(&u->d_cond, nc) == hipSuccess;
     if (ok && !multi)      // the one-output kernel reads the data itself
         ok = hipMalloc(&u->d_t, nt) == hipSuccess && hipMalloc(&u->d_obs, nt) == hipSuccess &&
              hipMemcpy(u->d_t, t, nt, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(u->d_obs, obs, nt, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && in) ok = hipMemcpy(u->d_cond, rows.data(), nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !in && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
     {   // likelihood constants; and the image (one-output model: only if its data is what smc_set_model_user3 would accept)
         std::vector<double> k(2 * (size_t)n_ex, 0.0);
         for (int e = 0; e < n_ex; ++e) {
@@ -856,6 +997,8 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         }
     }
     u->source = source;
+    u->geom = geom;
+    u->h_rows.swap(rows);
     if (t) u->h_t.assign(t, t + (size_t)n_ex * n_t);
     if (n_cond > 0) u->h_cond.assign(cond, cond + (size_t)n_ex * n_cond);
     for (int k = 0; k < n_obs && obs_scale; ++k) u->scale[k] = obs_scale[k];
@@ -896,12 +1039,14 @@ int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs,
                                atol, method, true);
 }
 
-int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
-                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
-                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method) {
+// a model with a noise specification: smc_set_model_user4, and smc_set_model_user5 (`in`: its inputs)
+static int set_model_user_noise(smc_ctx *c, const char *who, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
+                                const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol,
+                                int method, const UserInputs *in) {
     if (!c) return smc_fail(nullptr, "NULL context");
     const std::string bad = noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed);
-    if (!bad.empty()) return smc_fail(c, ("smc_set_model_user4: " + bad).c_str());
+    if (!bad.empty()) return smc_fail(c, (std::string(who) + ": " + bad).c_str());
     if (!prop_index) {      // today's model: one sigma for every output - the smc_set_model_user3 path and its bits
         bool last = true, fixed = true;
         for (int k = 0; k < n_obs; ++k) {
@@ -910,7 +1055,7 @@ int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs,
         }
         if (last || fixed)
             return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, last ? 1 : 0,
-                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true);
+                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true, nullptr, in);
     }
     UserNoise nz{};
     for (int k = 0; k < kUserMaxObs; ++k) {
@@ -921,7 +1066,60 @@ int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs,
         nz.scale[k] = (k < n_obs && obs_scale) ? obs_scale[k] : 1.0;
     }
     nz.prop = prop_index ? 1 : 0;
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz);
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in);
+}
+
+int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
+                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method) {
+    return set_model_user_noise(c, "smc_set_model_user4", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
+                                add_fixed, prop_index, prop_fixed, rtol, atol, method, nullptr);
+}
+
+int smc_set_model_user5(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
+                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
+                        double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    const UserInputs inputs{in_t, in_u, n_in, n_knot};
+    const UserInputs *in = &inputs;
+    if (n_in == 0) {      // no inputs: the existing functions' paths and their bits
+        if (in_t || in_u) return smc_fail(c, "smc_set_model_user5: n_in = 0 with in_t or in_u given (both must be NULL)");
+        in = nullptr;
+    }
+    if (add_index)
+        return set_model_user_noise(c, in ? "smc_set_model_user5" : "smc_set_model_user4", source, n_states, n_obs, t, obs, cond, obs_scale,
+                                    n_ex, n_t, n_cond, add_index, add_fixed, prop_index, prop_fixed, rtol, atol, method, in);
+    if (add_fixed || prop_index || prop_fixed)
+        return smc_fail(c, "smc_set_model_user5: add_index is NULL (the sigma rule) and another part of a noise model is given");
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
+                               method, true, nullptr, in);
+}
+
+int smc_user_set_design_inputs(smc_ctx *c, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_set_design_inputs: no user model has been set");
+    if (!in_t_new && !in_u_new) {
+        u->design_t.clear();
+        u->design_u.clear();
+        u->design_n_ex = u->design_n_knot = 0;
+        return 0;
+    }
+    if (u->geom.n_in == 0) return smc_fail(c, "smc_user_set_design_inputs: the model has no inputs (set it through smc_set_model_user5)");
+    std::vector<int> knots;
+    const std::string bad = input_layout_error(in_t_new, in_u_new, n_ex_new, u->geom.n_in, n_knot_new, knots);
+    if (!bad.empty()) return smc_fail(c, ("smc_user_set_design_inputs: " + bad + " (of the design)").c_str());
+    for (int e = 0; e < n_ex_new; ++e)
+        if (knots[e] > u->geom.kcap)
+            return smc_fail(c, ("smc_user_set_design_inputs: row " + std::to_string(e) + " of in_t has " + std::to_string(knots[e]) +
+                                " knots, above the knot capacity " + std::to_string(u->geom.kcap) +
+                                " the model was compiled for (the power of two >= its n_knot)").c_str());
+    u->design_t.assign(in_t_new, in_t_new + (size_t)n_ex_new * n_knot_new);
+    u->design_u.assign(in_u_new, in_u_new + (size_t)n_ex_new * n_knot_new * u->geom.n_in);
+    u->design_n_ex = n_ex_new;
+    u->design_n_knot = n_knot_new;
+    return 0;
 }
 
 int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts) {
@@ -939,7 +1137,7 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
             return smc_fail(c, "smc_user_predict: data set too large for the prediction kernel's LDS table");
         std::vector<char> code;
         std::string lg;
-        if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg))
+        if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg, 0, u->geom))
             return smc_fail(c, ("smc_user_predict: the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
         if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
             hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
@@ -993,12 +1191,15 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
     return 0;
 }
 // the design of a call: (t_new, cond_new) checked by the rules of smc_set_model_user3, or the data's own
-static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const double *&t, const double *&cond, int &n_ex, int &n_t) {
+// A model with inputs: cond becomes whole rows (cond_stride words, the table behind the numbers) - the data's own, or in `rows`
+// those of cond_new and the design inputs of smc_user_set_design_inputs, which an explicit design must have.
+static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const double *&t, const double *&cond, int &n_ex, int &n_t,
+                          std::vector<double> &rows) {
     const std::string w = std::string(who) + ": ";
     if (!t) {
         if (!u->d_img) return smc_fail(c, u->img_error.c_str());
         t = u->h_t.data();
-        cond = u->h_cond.data();
+        cond = u->geom.n_in > 0 ? u->h_rows.data() : u->h_cond.data();
         n_ex = u->n_ex;
         n_t = u->n_t;
         return 0;
@@ -1009,6 +1210,19 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
     std::vector<double> me, ls;
     const std::string bad = obs_layout(t, nan_obs.data(), u->scale, n_ex, n_t, u->n_obs, me, ls);
     if (!bad.empty()) return smc_fail(c, (w + bad + " (t_new)").c_str());
+    if (u->geom.n_in > 0) {
+        if (u->design_n_ex != n_ex)
+            return smc_fail(c, (w + "the model has inputs and the design has no matching design inputs: " +
+                                (u->design_n_ex ? "smc_user_set_design_inputs holds " + std::to_string(u->design_n_ex) + " rows"
+                                                : std::string("none are set")) +
+                                ", the design has " + std::to_string(n_ex) + " experiments (smc_user_set_design_inputs)").c_str());
+        std::vector<int> knots;
+        if (!input_layout_error(u->design_t.data(), u->design_u.data(), n_ex, u->geom.n_in, u->design_n_knot, knots).empty())
+            return smc_fail(c, (w + "the design inputs are no longer valid").c_str());
+        // a row whose finite knots fit the capacity may still be stored wider (trailing NaN): only its knots are copied
+        rows = build_input_rows(cond, u->geom, u->design_t.data(), u->design_u.data(), n_ex, u->design_n_knot, knots);
+        cond = rows.data();
+    }
     return 0;
 }
 static int design_too_large(smc_ctx *c, const UserModel *u, const char *who, int n_t) {
@@ -1032,7 +1246,8 @@ int smc_user_predict_at(smc_ctx *c, const double *particle, int64_t n, const dou
     if (attempts) *attempts = 0;
     const double *t = t_new, *cond = cond_new;
     int n_ex = n_ex_new, n_t = n_t_new;
-    if (resolve_design(c, u, "smc_user_predict_at", t, cond, n_ex, n_t) != 0) return 1;
+    std::vector<double> design_rows;
+    if (resolve_design(c, u, "smc_user_predict_at", t, cond, n_ex, n_t, design_rows) != 0) return 1;
     if (n == 0) return 0;
     const int g_max = design_lds_group(u, n_ex, n_t);
     if (g_max < 1) return design_too_large(c, u, "smc_user_predict_at", n_t);
@@ -1114,7 +1329,8 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
     const double *t = t_new, *cond = cond_new;
     int n_ex = n_ex_new, n_t = n_t_new;
-    if (resolve_design(c, u, who, t, cond, n_ex, n_t) != 0) return 1;
+    std::vector<double> design_rows;
+    if (resolve_design(c, u, who, t, cond, n_ex, n_t, design_rows) != 0) return 1;
     const int64_t n = c->n_local;
     const int g_lds = design_lds_group(u, n_ex, n_t);
     if (g_lds < 1) return design_too_large(c, u, who, n_t);

@@ -125,6 +125,7 @@ class HipEngine:
         self.model = None
         self.user_n_obs = 1     # outputs per data time of a user model (set_model_user)
         self.user_n_cond = 0    # ... and its numbers per experiment
+        self.user_n_in = 0      # ... and its time-varying inputs (set_model_user(inputs=))
         if "smc_ess_search_global" in B.MISSING:   # A/B build of an older revision (SMC_HIP_LIB): the driver falls back
             self.ess_search_global = None
         self._peer_barrier = None
@@ -171,7 +172,7 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6, method="RK45", obs_scale=None, noise=None):
+                       atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
@@ -183,12 +184,17 @@ class HipEngine:
         user_models.obs_layout); a 2-D obs without obs_scale goes through smc_set_model_user2 exactly as before.
         A noise model (smc_set_model_user4): noise={"additive": [("param", j) | ("fixed", v), ...], "proportional": [...]}, one
         entry per output, "proportional" optional - sd^2 = (a_k s_k)^2 + (b_k f)^2 (user_models.noise_loglik is the likelihood).
-        est_sigma and sigma_fixed are then not used; ValueError for a specification that breaks user_models.noise_layout's rules."""
+        est_sigma and sigma_fixed are then not used; ValueError for a specification that breaks user_models.noise_layout's rules.
+        Time-varying measured inputs (smc_set_model_user5): inputs={"t": (n_ex, n_knot), "u": (n_ex, n_knot, n_in)} - knot times (a
+        row may end in NaN) and the values of n_in inputs at them (2-D for one input); the source reads them as
+        smc_input(cond, k, t), linear between knots (user_models.input_value is the definition, input_layout the rules: ValueError
+        for inputs that break them).  With obs, obs_scale, noise / est_sigma as above.  inputs=None goes through the calls above
+        exactly as before."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
         obs = np.asarray(obs)
-        multi = obs.ndim == 3 or obs_scale is not None or noise is not None
+        multi = obs.ndim == 3 or obs_scale is not None or noise is not None or inputs is not None
         if multi:
             # several outputs, NaN = not measured, ragged rows (smc_set_model_user3); the same checks as the library's
             obs = _f64(obs if obs.ndim == 3 else obs.reshape(obs.shape + (1,)))
@@ -201,14 +207,24 @@ class HipEngine:
             n_obs = 1
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
+        ai = af = pi = pf = None
+        ip = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(B.c_ip)
+        fp = lambda a: None if a is None else _dp(np.ascontiguousarray(a, dtype=np.float64))
         if noise is not None:
             from .user_models import noise_layout
             ai, af, pi, pf = noise_layout(noise, n_obs, self.dim)
-            ip = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(B.c_ip)
-            fp = lambda a: None if a is None else _dp(np.ascontiguousarray(a, dtype=np.float64))
             ai, af = np.ascontiguousarray(ai, dtype=np.int32), np.ascontiguousarray(af)
             pi = None if pi is None else np.ascontiguousarray(pi, dtype=np.int32)
             pf = None if pf is None else np.ascontiguousarray(pf)
+        n_in = 0
+        if inputs is not None:
+            in_t, in_u, n_in = self._inputs("set_model_user", inputs, t.shape[0])
+            self._ck(self.L.smc_set_model_user5(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
+                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
+                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
+                                                int(bool(est_sigma)), float(sigma_fixed), _dp(in_t), _dp(in_u), n_in, in_t.shape[1]),
+                     "smc_set_model_user5")
+        elif noise is not None:
             self._ck(self.L.smc_set_model_user4(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
                                                 None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
                                                 ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol),
@@ -225,6 +241,19 @@ class HipEngine:
         self.model = ("user", t.shape[0], t.shape[1])      # the driver indexes this 3-tuple
         self.user_n_obs = n_obs
         self.user_n_cond = cond.shape[1]
+        self.user_n_in = n_in
+
+    @staticmethod
+    def _inputs(what, inputs, n_ex):
+        """inputs = {"t", "u"} checked by user_models.input_layout: contiguous in_t (n_ex, n_knot), in_u (n_ex, n_knot, n_in), n_in."""
+        if not isinstance(inputs, dict) or set(inputs) != {"t", "u"}:
+            raise ValueError(f'{what}: inputs must be {{"t": (n_ex, n_knot), "u": (n_ex, n_knot, n_in)}}')
+        from .user_models import input_layout
+        in_t, in_u = _f64(inputs["t"]), _f64(inputs["u"])
+        if in_u.ndim == 2 and in_t.ndim == 2:
+            in_u = in_u.reshape(in_u.shape + (1,))
+        input_layout(in_t, in_u, n_ex)
+        return in_t, np.ascontiguousarray(in_u), in_u.shape[2]
 
     def set_model_methanation(self, cond, guess, obs, base_params, est_position, est_sigma=True, sigma_fixed=5.0,
                               tf=75.0, rtol=1e-6, atol=1e-6):
@@ -453,31 +482,45 @@ class HipEngine:
                  "smc_user_predict")
         return lk, pred, {"n_failed": nf.value, "rk_attempts": att.value}
 
-    def _design(self, what, t, cond):
-        """(t, cond) of a prediction design as contiguous arrays and their C arguments; (None, None): the data's own design."""
+    def _design(self, what, t, cond, inputs=None):
+        """(t, cond) of a prediction design as contiguous arrays and their C arguments; (None, None): the data's own design.
+        inputs: the design's inputs ({"t", "u"} as set_model_user's), handed to the library (smc_user_set_design_inputs) before
+        the call; None with an explicit design clears them, and a model with inputs then refuses the design with the reason."""
         if t is None:
-            if cond is not None:
-                raise ValueError(f"{what}: cond without t (a design is both, or neither for the data's own)")
+            if cond is not None or inputs is not None:
+                raise ValueError(f"{what}: cond or inputs without t (a design is all of them, or none for the data's own)")
             return None, None, (None, None, 0, 0), (self.model[1], self.model[2])
         from .user_models import design_layout
         t = _f64(t)
         design_layout(t, cond, self.user_n_cond)
+        if inputs is not None:
+            if self.user_n_in == 0:
+                raise ValueError(f"{what}: inputs for a model that has none")
+            in_t, in_u, n_in = self._inputs(what, inputs, t.shape[0])
+            if n_in != self.user_n_in:
+                raise ValueError(f"{what}: the model has {self.user_n_in} inputs, the design's u holds {n_in}")
+            self._ck(self.L.smc_user_set_design_inputs(self.ctx, _dp(in_t), _dp(in_u), t.shape[0], in_t.shape[1]),
+                     "smc_user_set_design_inputs")
+        elif self.user_n_in:
+            self._ck(self.L.smc_user_set_design_inputs(self.ctx, None, None, 0, 0), "smc_user_set_design_inputs")
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond, dtype=np.float64).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
         return t, cbuf, (_dp(t), _dp(cbuf), t.shape[0], t.shape[1]), t.shape
 
-    def predict_user_at(self, particles, t=None, cond=None):
+    def predict_user_at(self, particles, t=None, cond=None, inputs=None):
         """A user model's predictions for host particles (n, dim) on a design of its own (include/smc_hip.h: smc_user_predict_at):
         t (n_ex_new, n_t_new) rows of output times (the first is the initial time; a row may end in NaN), cond
         (n_ex_new, n_cond) - other times, a longer horizon, an experiment that was never run.  Without a design: the data's,
         with predict_user's bits.  Returns pred (n, n_ex_new, n_t_new, n_obs), NaN past a row's end and from where a solve
-        failed, and {"n_failed", "rk_attempts"}.  ValueError for a design that breaks the rules (user_models.design_layout)."""
+        failed, and {"n_failed", "rk_attempts"}.  ValueError for a design that breaks the rules (user_models.design_layout).
+        A model with inputs (set_model_user(inputs=)): an explicit design brings its own, inputs={"t": (n_ex_new, n_knot_new),
+        "u": (n_ex_new, n_knot_new, n_in)} - "what if I feed like this instead"; without them it is refused (SmcError)."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("predict_user_at: no user model has been set")
         particles = _f64(particles)
         if particles.ndim != 2 or particles.shape[1] != self.dim:
             raise ValueError(f"predict_user_at: particles must be (n, {self.dim}), got {particles.shape}")
-        t, cbuf, cargs, shape = self._design("predict_user_at", t, cond)
+        t, cbuf, cargs, shape = self._design("predict_user_at", t, cond, inputs)
         n = particles.shape[0]
         pred = np.empty((n, shape[0], shape[1], self.user_n_obs))
         nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -486,7 +529,7 @@ class HipEngine:
         return pred, {"n_failed": nf.value, "rk_attempts": att.value}
 
     def predictive_summary(self, which=SMC_SET_FILT, probs=(0.025, 0.5, 0.975), t=None, cond=None, noise=False, seed=0,
-                           global_offset=0, max_staging_bytes=0):
+                           global_offset=0, max_staging_bytes=0, inputs=None):
         """Posterior predictive summaries of a resident particle set, formed on the device (include/smc_hip.h:
         smc_user_predict_summary): per cell (experiment, time, output) of the design (t, cond; None: the data's) over the set's
         equally weighted particles.  Returns {"mean", "sd", "n_finite": (n_ex, n_t, n_obs); "lower", "upper", "quantile":
@@ -494,13 +537,13 @@ class HipEngine:
         value between them (user_models.quantile_ranks, linear_quantile); "n_failed", "rk_attempts"; "kernel_ms":
         {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
         global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
-        With several ranks the summary describes this rank's block only."""
+        With several ranks the summary describes this rank's block only.  inputs: as predict_user_at's."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("predictive_summary: no user model has been set")
         q = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))
         if not 1 <= q.size <= B.SMC_PRED_MAX_PROBS or not np.all((q >= 0) & (q <= 1)):
             raise ValueError(f"predictive_summary: 1 .. {B.SMC_PRED_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
-        t, cbuf, cargs, shape = self._design("predictive_summary", t, cond)
+        t, cbuf, cargs, shape = self._design("predictive_summary", t, cond, inputs)
         cells = (shape[0], shape[1], self.user_n_obs)
         mean, sd = np.empty(cells), np.empty(cells)
         lower, upper = np.empty((q.size,) + cells), np.empty((q.size,) + cells)

@@ -175,6 +175,77 @@ def noise_loglik(pred, t, obs, theta, noise, obs_scale=None):
     return np.where(np.all(a > 0, axis=1) & np.all(b >= 0, axis=1), lk, -np.inf)
 
 
+def input_layout(in_t, in_u, n_ex):
+    """The data rules of a model's time-varying inputs (include/smc_hip.h: smc_set_model_user5), in NumPy: in_t (n_ex, n_knot) knot
+    times, a row by the row rules of obs_layout's t - a strictly increasing finite run of at least one knot, possibly followed by
+    NaN only; in_u (n_ex, n_knot, n_in) the values of n_in = 1 .. 8 inputs at the knots ((n_ex, n_knot) for one input), finite at a
+    row's finite knots - with every slope between neighbours finite - and ignored past them; n_knot <= 4096.  Returns the knots
+    per row, (n_ex,) int; raises ValueError, in the library's words (smc_user_input_check), for inputs the library refuses."""
+    import numpy as np
+    t = np.asarray(in_t, dtype=np.float64)
+    u = np.asarray(in_u, dtype=np.float64)
+    if u.ndim == 2 and t.ndim == 2:
+        u = u.reshape(u.shape + (1,))
+    n_ex = int(n_ex)
+    if t.ndim != 2 or u.ndim != 3 or u.shape[:2] != t.shape or t.shape[0] != n_ex:
+        raise ValueError(f"input_layout: in_t must be ({n_ex}, n_knot) and in_u ({n_ex}, n_knot, n_in), got {t.shape} and {u.shape}")
+    n_knot, n_in = t.shape[1], u.shape[2]
+    if not 1 <= n_in <= 8:
+        raise ValueError(f"input_layout: n_in = {n_in} outside 1 .. 8 (SMC_USER_MAX_INPUTS)")
+    if n_knot < 1:
+        raise ValueError(f"input_layout: n_knot = {n_knot}: a row needs at least one knot")
+    if n_knot > 4096:
+        raise ValueError(f"input_layout: n_knot = {n_knot} above the knot capacity 4096 (SMC_USER_MAX_KNOTS)")
+    if n_ex < 1:
+        raise ValueError(f"input_layout: n_ex = {n_ex}: no experiment")
+    m = np.zeros(n_ex, dtype=np.int64)
+    for e in range(n_ex):
+        nan = np.isnan(t[e])
+        k = int(nan.argmax()) if nan.any() else n_knot
+        late = np.flatnonzero(~nan[k:])
+        if late.size:
+            raise ValueError(f"input_layout: row {e} of in_t has a NaN knot before a number at knot {k + late[0]} "
+                             "(only a trailing run of NaN may shorten a row)")
+        if k == 0:
+            raise ValueError(f"input_layout: row {e} of in_t has no finite knot")
+        for i in range(k):
+            if not np.isfinite(t[e, i]):
+                raise ValueError(f"input_layout: row {e} of in_t holds an infinite knot at knot {i}")
+            if i > 0 and not t[e, i] > t[e, i - 1]:
+                raise ValueError(f"input_layout: row {e} of in_t is not strictly increasing at knot {i}")
+        with np.errstate(over="ignore", invalid="ignore"):
+            steep = np.zeros((k, n_in), dtype=bool)
+            steep[1:] = ~np.isfinite(np.diff(u[e, :k], axis=0) / np.diff(t[e, :k])[:, None])
+        for i in range(k):
+            for j in range(n_in):
+                if not np.isfinite(u[e, i, j]):
+                    raise ValueError(f"input_layout: row {e} of in_u is not finite at knot {i} of input {j}")
+                if steep[i, j]:
+                    raise ValueError(f"input_layout: row {e} of in_u has a slope that overflows at knot {i} of input {j}")
+        m[e] = k
+    return m
+
+
+def input_value(tk, u, t):
+    """smc_input (include/smc_hip.h: smc_set_model_user5) for one row and one input - its executable definition: tk (m,) strictly
+    increasing finite knots, u (m,) values, t any shape.  u[0] for t <= tk[0], u[m-1] for t >= tk[m-1], else with j the last knot
+    <= t:  u[j] + s_j (t - tk[j]),  s_j = (u[j+1] - u[j]) / (tk[j+1] - tk[j]),  clamped to [min(u[j], u[j+1]), max(u[j], u[j+1])] -
+    what np.interp(t, tk, u) computes, up to rounding.  Equal to u[j] at t == tk[j]; never outside the bracket."""
+    import numpy as np
+    tk = np.asarray(tk, dtype=np.float64).reshape(-1)
+    u = np.asarray(u, dtype=np.float64).reshape(-1)
+    t = np.asarray(t, dtype=np.float64)
+    m = tk.size
+    if m < 1 or u.size != m:
+        raise ValueError(f"input_value: tk and u must hold the same number (>= 1) of entries, got {tk.size} and {u.size}")
+    j = np.clip(np.searchsorted(tk, t, side="right") - 1, 0, m - 1)          # the last knot <= t
+    j1 = np.minimum(j + 1, m - 1)
+    s = np.concatenate([np.diff(u) / np.diff(tk), [0.0]])
+    u0, u1 = u[j], u[j1]
+    v = u0 + s[j] * np.maximum(t - tk[j], 0.0)
+    return np.minimum(np.maximum(v, np.minimum(u0, u1)), np.maximum(u0, u1))
+
+
 def design_layout(t_new, cond_new, n_cond):
     """The rules of a prediction design (include/smc_hip.h: smc_user_predict_at), in NumPy: t_new (n_ex_new, n_t_new) by the row
     rules of obs_layout - a strictly increasing run of finite times, possibly followed by NaN only; t_new[e][0] is the initial
