@@ -37,7 +37,9 @@ extern "C" {
 
 #define SMC_ABI_VERSION 3    /* 2: smc_meth_sweep_check writes FIVE words (round 3 added the cancelled count); smc_mh_sweeps_device_rng
                               * 3: smc_work_totals; smc_mh_sweeps_device_rng takes the methanation model too and returns the sweep counters;
-                              *    smc_meth_dae_host's stats have five words (round 5) */
+                              *    smc_meth_dae_host's stats have five words (round 5)
+                              * (still 3: smc_set_share_replicates / smc_mm_share_info and smc_set_start_reject / smc_mm_start_reject_info /
+                              *    smc_mm_reject_threshold only ADD entry points; the binding tolerates their absence in an older A/B build) */
 #define SMC_MAX_DIM 8        /* parameters per particle (3 for Michaelis-Menten, 5 for methanation) */
 #define SMC_MAX_ESS_CAND 16  /* tempering candidates evaluated by one smc_ess_partials call */
 #define SMC_MAX_RANKS 64
@@ -353,6 +355,26 @@ int smc_mm_group_replicates(const double *t, const double *S0, int n_ex, int n_t
  * RK45 attempts since the last smc_timing_reset that are in rk_attempts (smc_work_totals out[1], the sweeps' own counts) but were
  * not executed - the partners' copies.  Either pointer may be NULL.  Synchronises the stream. */
 int smc_mm_share_info(smc_ctx *ctx, int *n_solve, int64_t *shared_attempts);
+/* Rejection at start (Michaelis-Menten Metropolis sweeps, default: on; no effect unless smc_set_early_reject is on; the environment
+ * variable SMC_START_REJECT=0 turns it off whatever this switch says).  The proposal kernel computes, per particle, the sum of squared
+ * residuals from which the accept test is certain to fail (smc_mm_reject_threshold); an item of a later pass of the solve queue
+ * adds up the sums its siblings have already published and, if they reach that threshold, is cancelled before its first attempt.
+ * Every result is the same bit for bit (tests/test_gpu_start_reject.py compares on and off); only the attempt counters and the
+ * solved / cancelled split differ, and depend on timing.  Off, the proposal kernel computes no thresholds and the solve kernel -
+ * the same kernel, with a flag in its arguments clear - skips the look at one wave-uniform branch per started item.  On, the host
+ * still drops both for the sweeps that follow a sweep which left fewer than 1 item in 100 unstarted (a posterior-like population
+ * would pay the loads for nothing), until the next likelihood sweep of the context announces a new population. */
+int smc_set_start_reject(smc_ctx *ctx, int enable);
+/* not_started: (particle, experiment) items of this context's Michaelis-Menten Metropolis sweeps that were cancelled with no attempt
+ * at all, since smc_create - device-counted by the accept kernel, summed on the host when a sweep's counters are read. */
+int smc_mm_start_reject_info(smc_ctx *ctx, int64_t *not_started);
+/* The threshold itself, a pure host function (no device is touched; the propose kernel evaluates the same inline function): finished
+ * sums of squared residuals that add up to at least the returned value make the accept test
+ *   exp((sum_k (c0 - S_k / (2 sigma^2)) - lk1) * gamma) * pratio >= rr,   c0 = -n_t / 2 * log(2 pi sigma^2),  k < n_ex,
+ * fail in double precision whatever the other S_k >= 0 are.  pratio: 1.0 in SMC_PRIOR_MODE_MASK.  0 where the test fails with no
+ * residual at all; +inf ("never") for every doubtful input: in_support == 0, rr outside (0, 1], sigma <= 0, gamma <= 0, pratio not
+ * positive and finite, NaN or infinite arguments, and where the terms of a positive threshold cancel to three digits or more. */
+double smc_mm_reject_threshold(double lk1, double gamma, double rr, double sigma, int n_ex, int n_t, double pratio, int in_support);
 /* Michaelis-Menten Metropolis sweeps over a homogeneous population (the previous sweep of the context had fewer than one
  * (particle, experiment) solve in 20 000 with more than 64 RK45 attempts - counted on the device) run their waves IN PHASE
  * (default: on): a wave waits up to 12 attempts for all 64 lanes to finish before it starts its next 64 items, so that the

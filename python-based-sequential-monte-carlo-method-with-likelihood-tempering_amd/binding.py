@@ -95,6 +95,10 @@ SIGNATURES = {
     "smc_set_share_replicates": (cint, [c_ctx, cint]),
     "smc_mm_group_replicates": (cint, [c_dp, c_dp, cint, cint, c_ip, c_ip]),
     "smc_mm_share_info": (cint, [c_ctx, c_ip, c_i64p]),
+    "smc_set_start_reject": (cint, [c_ctx, cint]),
+    "smc_mm_start_reject_info": (cint, [c_ctx, c_i64p]),
+    "smc_mm_reject_threshold": (ctypes.c_double, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, cint, cint,
+                                                  ctypes.c_double, cint]),
     "smc_set_in_phase": (cint, [c_ctx, cint]),
     "smc_set_exact_pow": (cint, [c_ctx, cint]),
     "smc_exchange_plan": (cint, [cint, cint, i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),

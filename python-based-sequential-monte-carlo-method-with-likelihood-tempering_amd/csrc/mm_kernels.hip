@@ -305,18 +305,35 @@ __device__ __forceinline__ void mm_propose_one(const Prior &prior, const MHParam
     double pdf = prior_pdf(prior.kind[0], prior.a[0], prior.b[0], c0);
     pdf = pdf * prior_pdf(prior.kind[1], prior.a[1], prior.b[1], c1);
     pdf = pdf * prior_pdf(prior.kind[2], prior.a[2], prior.b[2], c2);
+    double pratio = 1.0;
     if (mh.prior_mode != SMC_PRIOR_MODE_MASK) {   // p0_2 / p0_1 (SMC_methanation_main.py:323-324, 343)
         double cur = prior_pdf(prior.kind[0], prior.a[0], prior.b[0], f0);
         cur = cur * prior_pdf(prior.kind[1], prior.a[1], prior.b[1], f1);
         cur = cur * prior_pdf(prior.kind[2], prior.a[2], prior.b[2], f2);
-        mh.pratio[p] = pdf / cur;
+        pratio = pdf / cur;
+        mh.pratio[p] = pratio;
     }
     const double p0 = (pdf > 0.0 || mh.prior_mode == SMC_PRIOR_MODE_RATIO) ? 1.0 : 0.0, q0 = 1.0 - p0;
     const double w0 = __dadd_rn(__dmul_rn(c0, p0), __dmul_rn(f0, q0)), w1 = __dadd_rn(__dmul_rn(c1, p0), __dmul_rn(f1, q0));
     prop[p] = w0;
     prop[pstride + p] = w1;
-    prop[2 * pstride + p] = __dadd_rn(__dmul_rn(c2, p0), __dmul_rn(f2, q0));
+    const double w2 = __dadd_rn(__dmul_rn(c2, p0), __dmul_rn(f2, q0));
+    prop[2 * pstride + p] = w2;
     p0_out[p] = (uint8_t)(p0 != 0.0);
+    // rejection at start (MMOps::start_values): everything the accept test of this proposal needs except its sums of squares is known
+    // here - lk1, gamma, the accept uniform (device RNG: a pure function of the Philox key), the prior ratio, sigma - so the sum of
+    // squares from which the proposal is certain to be rejected is computed once, here, and the solve kernel only compares
+    if (mh.reject_thr) {
+        double rr;
+        if (mh.device_rng) {
+            const u32x4 ru = philox_block(mh.seed, (uint64_t)(mh.global_offset + p), mh.stream, SMC_PHILOX_BLOCK_UNIFORM);
+            rr = u01_from(ru.x, ru.y);
+        } else {
+            rr = mh.rr[p];
+        }
+        mh.reject_thr[p] = mm_reject_threshold(mh.reject_lk1[p], mh.gamma, rr, mh.thr_est_sigma ? w2 : mh.thr_sigma_fixed, mh.pending_n_ex,
+                                               mh.thr_n_t, pratio, p0 != 0.0);
+    }
     if (mh.cost_bucket) {
         const unsigned cls = mm_cost_bucket(w0, w1, p0 != 0.0);
         mh.cost_bucket[p] = (uint8_t)cls;
@@ -390,6 +407,14 @@ constexpr int kSolveBlock = 256;   // 4 waves
 constexpr int kLongItemAttempts = 64;
 constexpr int kFinishSharedWord = 1;   // accept kernel: 8-byte words from its arrival counter to the running total of shared attempts
 constexpr int kPoolWords = 15;     // 8-byte words of a pooled item: 11 doubles, 2 packed int pairs, out_idx, prediction pointer
+// Rejection at start: the first solve group (experiment, without replicate sharing) whose items look at their siblings' sums.  The
+// groups of a chunk are started microseconds apart by one wave (solve_sched.h: kExPerChunk), so only a LATER chunk's groups can find
+// a finished sibling: the first kExPerChunk groups would pay the loads for nothing.
+#ifndef SMC_START_LOOK_FROM
+#define SMC_START_LOOK_FROM kExPerChunk
+#endif
+constexpr int kStartLookFrom = SMC_START_LOOK_FROM;
+static_assert(kStartLookFrom >= 1, "group 0 is handed out first: it has no finished sibling");
 
 struct SolveArgs {              // everything the attempt loops do not touch stays behind a pointer (RejectArgs, StiffList)
     const double *theta;        // SoA rows: Vmax at [p], Km at [stride + p], sigma at [2*stride + p]
@@ -405,6 +430,8 @@ struct SolveArgs {              // everything the attempt loops do not touch sta
     int64_t stiff_cap;
     unsigned solo_cap;
     int patience;               // solve_sched.h: attempts a wave waits for all its lanes before a hand-out (homogeneous sweeps)
+    int start_look;             // rejection at start (MMOps::start_values): row n_ex of sum_r2 holds mm_reject_threshold() of every proposal,
+                                // written by the propose kernel of this sweep (0: off - smc_set_start_reject, or no early rejection)
     const int32_t *order;       // cost order of the sweep: position of the index-ordered pass -> particle (nullptr: identity)
     const unsigned *n_ordered;  // ... and how many positions it has: the in-support proposals (the others were published by the
                                 // propose kernel and come last in `order`); nullptr: all n (a probe's uploaded order)
@@ -547,6 +574,7 @@ struct MMOps {
     // SHARE: the block's lane-private words of LDS for the partner's running sum (one per thread), and the group table
     double *s_sum2;
     const int *s_grp;           // LDS: [2 s] primary experiment of solve group s, [2 s + 1] its partner or -1
+    int look;                   // a.start_look
 
     __device__ __forceinline__ double *sum2_word() const { return SHARE ? s_sum2 + threadIdx.x : nullptr; }
     // distance in experiments to the partner of the item (0: none), and the partner's sum so far
@@ -561,6 +589,7 @@ struct MMOps {
     __device__ __forceinline__ int start_values(long long p, int e, bool from_list, bool masked, double Vmax, double Km, double sigma,
                                                 Item &nb) const {
         int d_e = 0;                                     // SHARE: e is a solve group
+        const int g_self = e;                            // the scheduler's index of the item: solve group or experiment
         if (SHARE) {
             const int g = e;
             e = s_grp[2 * g];
@@ -573,6 +602,27 @@ struct MMOps {
         nb.pred = nullptr;
         // index-ordered pass: a particle of the stiff list has been handed out already
         if (!from_list && list && !masked && mm_is_stiff(Vmax, Km)) return kStartSkipped;
+        // Rejection at start.  An index- or cost-ordered item of a later pass of the queue finds the sums of its siblings of the
+        // earlier passes published; if they alone reach the proposal's threshold (smc_internal.h: mm_reject_threshold) the accept kernel
+        // rejects the proposal whatever this solve returns, and the solve is not started: it is published as cancelled with no
+        // attempts, which every consumer of those words already understands.  Loads, adds and a comparison: exp, log and Philox
+        // happened in the propose kernel.  The groups of the FIRST pass would find nothing but NaN and do not look.
+        if (look != 0 && !from_list && !masked && g_self >= kStartLookFrom) {
+            double fin = 0.0;
+            bool dead = false;
+            const unsigned long long *sums = reinterpret_cast<const unsigned long long *>(pub_sums) + p;
+            for (int k = SHARE ? mm.n_ex : n_ex; k > 0; --k, sums += n) {
+                const double v = __longlong_as_double((long long)__hip_atomic_load(sums, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                dead = dead || v < 0.0;        // kSumCancelled: a sibling has already established the rejection
+                fin += v >= 0.0 ? v : 0.0;     // finished; NaN = not finished (or failed): counts as 0
+            }
+            const double T = *reinterpret_cast<const double *>(sums);   // the row behind the sums: written before this kernel began
+            if (dead || (fin >= T && fin <= 1.7976931348623157e308)) {
+                publish_item(a, nb.out_idx, kSumCancelled, 0 | kInfoCancelled);
+                if (SHARE && d_e != 0) publish_item(a, out_idx2, kSumCancelled, 0 | kInfoCancelled);
+                return kStartDone;
+            }
+        }
         if (masked || sigma <= 0.0) {                    // sigma <= 0: -inf without solving (:53-54)
             publish_item(a, nb.out_idx, 0.0, 0);
             if (SHARE && d_e != 0) publish_item(a, out_idx2, 0.0, 0);
@@ -751,7 +801,7 @@ __device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs
                                  a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, own_sgpr(mm.rtol), own_sgpr(mm.atol),
                                  own_sgpr(a.patience),
                                  a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : (long long)a.n,
-                                 own_sgpr(a.sum_r2), own_sgpr(a.info), SHARE ? s_sum2 : nullptr, SHARE ? s_grp : nullptr};
+                                 own_sgpr(a.sum_r2), own_sgpr(a.info), SHARE ? s_sum2 : nullptr, SHARE ? s_grp : nullptr, a.start_look};
     solve_persistent(ops, a.queue, s_pool);
 }
 // The kernel: the primary template serves the parity arithmetic (EXACT: 164 VGPRs, three waves per SIMD); the default-mode
@@ -888,6 +938,8 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
                 attempts += (unsigned)(fl & kInfoAttemptsMask);
                 shared_attempts += ((unsigned)mm.partner_mask >> k) & 1u ? (unsigned)(fl & kInfoAttemptsMask) : 0u;
                 long_items += (unsigned)(fl & kInfoAttemptsMask) > (unsigned)kLongItemAttempts;
+                // (items cancelled before their first attempt - MMOps::start_values - ride in the HIGH half through the block reduction)
+                long_items += (unsigned long long)((fl & (kInfoCancelled | kInfoAttemptsMask)) == kInfoCancelled) << 32;
                 pf |= (unsigned)(fl >> 30) & 1u;
                 cancelled = cancelled || (fl & kInfoCancelled) != 0;
 #ifndef SMC_NO_SOLVED_COUNT   // A/B builds
@@ -988,6 +1040,9 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
             row_store(row + 5, v >> 32);
         } else if (threadIdx.x == 5) {
             row_store(row + 6, v);
+        } else if (threadIdx.x == 4) {      // low half: long items; high half: items that were never started
+            row_store(row + 4, v & 0xffffffffULL);
+            row_store(row + 7, v >> 32);
         } else {
             row_store(row + threadIdx.x, v);
         }
@@ -998,8 +1053,9 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
     __syncthreads();
     if (!s_last) return;
     {
-        constexpr int kTot = 7;      // the six sweep counters, then the shared attempts
-        unsigned long long tot[kTot] = {0, 0, 0, 0, 0, 0, 0};
+        constexpr int kTot = 8;      // the six sweep counters, then the shared attempts and the items that were never started
+        static_assert(kTot <= kFinishCountWords, "a row has a word for each");
+        unsigned long long tot[kTot] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
 #pragma unroll
             for (int q = 0; q < kTot; ++q) tot[q] += ctl_load<true>(tail.count_rows + (size_t)b * kFinishCountWords + q);
@@ -1023,6 +1079,10 @@ mm_finish_kernel(MMModel mm, MHParams mh, const double *__restrict__ theta /* ev
         if (threadIdx.x == 6) {      // not a sweep counter: a running total beside the arrival counter (smc_mm_share_info)
             const unsigned long long v = s_tot[0][6] + s_tot[1][6] + s_tot[2][6] + s_tot[3][6];
             if (v) atomicAdd(reinterpret_cast<unsigned long long *>(tail.arrive) + kFinishSharedWord, v);
+        }
+        if (threadIdx.x == 7) {      // (with its result, as above: the control step below takes its snapshot of the counters)
+            const unsigned long long v = s_tot[0][7] + s_tot[1][7] + s_tot[2][7] + s_tot[3][7];
+            if (v) s_tot[0][7] = atomicAdd(&counters->cancelled_solves, v);
         }
         if (threadIdx.x == 0) __hip_atomic_store(tail.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1142,7 +1202,8 @@ static StiffList next_stiff_list(smc_ctx *ctx, int64_t n) {
 
 static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int64_t n, const uint8_t *p0, double *pred,
                          const StiffList &sl, bool queue_cleared = false, bool reject = false, int patience = 0,
-                         const int32_t *order = nullptr, bool cost_ordered = false, const MHControl *ctl = nullptr) {
+                         const int32_t *order = nullptr, bool cost_ordered = false, const MHControl *ctl = nullptr,
+                         bool start_look = false) {
     const bool share = share_on(ctx);
     MMModel mm = ctx->mm;
     mm.partner_mask = 0;        // (read by the accept kernel only)
@@ -1166,6 +1227,7 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
     a.n_ordered = cost_ordered ? cost_n_ordered(ctx) : nullptr;
     a.sorted = static_cast<const SortedProposal *>(ctx->d_sorted);
     a.ctl = ctl;
+    a.start_look = reject && start_look;
 #ifdef SMC_DEBUG_PATIENCE_ENV   // A/B builds only (tools/ab_build.sh): in-phase patience of every sweep from the environment
     if (const char *e = getenv("SMC_DEBUG_PATIENCE")) a.patience = atoi(e);
 #endif
@@ -1207,6 +1269,7 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
 
 void launch_mm_loglik(smc_ctx *ctx, const double *theta, int64_t stride, int64_t n, double *lk, double *pred) {
     if (n <= 0) return;
+    ctx->start_look_idle = false;      // a new population: its Metropolis sweeps look again (smc_internal.h)
     const StiffList sl = next_stiff_list(ctx, n);
     if (sl.particles)
         hipLaunchKernelGGL(mm_stiff_scan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, theta, stride, n, sl);
@@ -1231,6 +1294,12 @@ void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in, const MHContro
         mh.pending_n_ex = ctx->mm.n_ex;
         mh.reject_out = ctx->d_reject;
         mh.reject_lk1 = F.lk;
+        if (ctx->start_reject != 0 && !ctx->start_reject_env_off && !ctx->start_look_idle) {
+            mh.reject_thr = ctx->d_sum_r2 + (size_t)ctx->mm.n_ex * n;     // the row behind the n_ex rows of sums of this sweep
+            mh.thr_sigma_fixed = ctx->mm.sigma_fixed;
+            mh.thr_n_t = ctx->mm.n_t;
+            mh.thr_est_sigma = ctx->mm.est_sigma;
+        }
     }
     mh.stiff = next_stiff_list(ctx, n);
     // in phase (solve_sched.h) when the previous Metropolis sweep of this context had fewer than 1 long item in 20 000 ...
@@ -1251,8 +1320,9 @@ void launch_mm_mh(smc_ctx *ctx, int64_t n, const MHParams &mh_in, const MHContro
     }
     const int patience = (ctx->in_phase != 0 && (homogeneous || cost_order)) ? kInPhasePatience : (ctx->order_debug ? ctx->order_debug_patience : 0);
     launch_solve(ctx, P.theta, P.stride, n, ctx->d_p0, nullptr, mh.stiff, mh.zero_queue != nullptr, reject, patience,
-                 ctx->order_debug ? ctx->d_order : nullptr, cost_order, mh.ctl);
+                 ctx->order_debug ? ctx->d_order : nullptr, cost_order, mh.ctl, mh.reject_thr != nullptr);
     ctx->pending_sweep_items = n * ctx->mm.n_ex;
+    ctx->start_look_pending = mh.reject_thr != nullptr;
     ctx->moment_rows_n = mh.moment_rows ? (int)finish_grid(n) : 0;
     launch_finish<1>(ctx, mh, P.theta, P.stride, n, ctx->d_p0, F.lk, F.theta, F.stride, ctx->r_ac, dbg ? ctx->dbg_lk2 : nullptr,
                      dbg ? ctx->dbg_r : nullptr, ctl_after, w_cov);

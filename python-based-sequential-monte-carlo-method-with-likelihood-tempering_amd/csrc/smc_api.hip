@@ -188,6 +188,8 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
     {   // unset = on; 0 = off whatever smc_set_share_replicates says later (A/B runs of one build under an unchanged caller)
         const char *e = getenv("SMC_SHARE_REPLICATES");
         c->share_env_off = e ? atoi(e) == 0 : false;
+        e = getenv("SMC_START_REJECT");         // the same for smc_set_start_reject
+        c->start_reject_env_off = e ? atoi(e) == 0 : false;
     }
 #define CK(call)                                   \
     do {                                           \
@@ -561,6 +563,19 @@ int smc_set_share_replicates(smc_ctx *c, int enable) {
     c->share_replicates = enable != 0;
     return 0;
 }
+int smc_set_start_reject(smc_ctx *c, int enable) {
+    if (!c) return fail(nullptr, "NULL context");
+    c->start_reject = enable != 0;
+    return 0;
+}
+int smc_mm_start_reject_info(smc_ctx *c, int64_t *not_started) {
+    if (!c) return fail(nullptr, "NULL context");
+    if (not_started) *not_started = c->w_not_started;
+    return 0;
+}
+double smc_mm_reject_threshold(double lk1, double gamma, double rr, double sigma, int n_ex, int n_t, double pratio, int in_support) {
+    return mm_reject_threshold(lk1, gamma, rr, sigma, n_ex, n_t, pratio, in_support);
+}
 int smc_mm_group_replicates(const double *t, const double *S0, int n_ex, int n_t, int *primary, int *partner) {
     if (!t || !S0 || !primary || !partner || n_ex < 1 || n_t < 1) return -1;
     return group_replicates(t, S0, n_ex, n_t, primary, partner);
@@ -698,7 +713,7 @@ static int ensure_item_capacity(smc_ctx *c, int64_t n) {
     c->d_info = nullptr;
     c->d_stiff_list = nullptr;
     c->item_cap = 0;
-    HIPC(c, hipMalloc(&c->d_sum_r2, (size_t)n * c->mm.n_ex * sizeof(double)));
+    HIPC(c, hipMalloc(&c->d_sum_r2, (size_t)n * (c->mm.n_ex + 1) * sizeof(double)));    // + 1: the rejection thresholds (smc_internal.h)
     HIPC(c, hipMalloc(&c->d_info, (size_t)n * c->mm.n_ex * sizeof(int)));
     HIPC(c, hipMalloc(&c->d_stiff_list, (size_t)n * sizeof(int32_t)));   // every particle at most once per sweep
     HIPC(c, hipMemsetAsync(c->d_stiff_count, 0, 4 * sizeof(unsigned), c->stream));
@@ -715,11 +730,13 @@ static int counters_end(smc_ctx *c) {
     if (c->model_kind == 1) {   // smc_work_totals: every sweep that ends here launched the solve kernel once
         c->w_solved_items += (int64_t)c->h_counters->solved_items;
         c->w_rk_attempts += (int64_t)c->h_counters->rk_attempts;
+        c->w_not_started += (int64_t)c->h_counters->cancelled_solves;
         c->w_solve_launches += 1;
     }
     if (c->model_kind == 1 && c->pending_sweep_items > 0) {   // what the next Metropolis sweep's in-phase decision looks at
         c->last_sweep_items = c->pending_sweep_items;
         c->last_sweep_long_items = (int64_t)c->h_counters->long_items;
+        if (c->start_look_pending && (int64_t)c->h_counters->cancelled_solves * 100 < c->last_sweep_items) c->start_look_idle = true;
         c->pending_sweep_items = 0;
     }
     if (c->model_kind == 2) {   // every (particle, experiment) item the sweep asked for must have been solved exactly once
@@ -1670,6 +1687,7 @@ int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, cons
         c->pending_sweep_items = 0;
         c->last_sweep_items = c->n_local * c->mm.n_ex;
         c->last_sweep_long_items = (int64_t)c->h_mhlog[done - 1].long_items;
+        if (c->start_look_pending && (int64_t)c->h_mhlog[done - 1].snap.cancelled_solves * 100 < c->last_sweep_items) c->start_look_idle = true;
         c->w_solve_launches += done;
         c->w_noop_launches += n_iter - done;
     }
@@ -1682,6 +1700,7 @@ int smc_mh_sweeps_device_rng(smc_ctx *c, double gamma, double mhstep_ratio, cons
         if (mm) {
             c->w_solved_items += (int64_t)e.solved_items;
             c->w_rk_attempts += (int64_t)e.rk_attempts;
+            c->w_not_started += (int64_t)e.snap.cancelled_solves;
         } else {   // every (particle, experiment) item the sweep asked for must have been solved or cancelled exactly once
             const SweepCounters &k = e.snap;
             if (k.completed_solves + k.cancelled_solves != k.expected_solves || k.unsolved_items != 0 || k.wave_split != 0) {

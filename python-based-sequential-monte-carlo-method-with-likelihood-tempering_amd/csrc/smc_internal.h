@@ -73,7 +73,9 @@ struct SweepCounters {  // device-side integer counters (order-independent atomi
     // unsolved (status still poisoned), waves that were incomplete at a dequeue.  A sweep is valid only if
     // completed == expected and the other two are zero (checked on the host after every sweep).
     unsigned long long expected_solves, completed_solves, unsolved_items, wave_split;
-    unsigned long long cancelled_solves;   // solves not started because their proposal was already certain to be rejected
+    unsigned long long cancelled_solves;   // solves not started because their proposal was already certain to be rejected (methanation:
+                                           // counted by its solve kernels; Michaelis-Menten: items with no attempt and the cancelled
+                                           // mark, counted by mm_finish_kernel - rejection at start and tail looks before a first attempt)
     unsigned long long long_items;         // Michaelis-Menten: items that needed more than kLongItemAttempts attempts (mm_kernels.hip)
     unsigned long long solved_items;       // Michaelis-Menten: (particle, experiment) solves that reached t_bound and produced their dense outputs
 };
@@ -154,8 +156,70 @@ struct MHParams {    // passed by value to the fused MH kernel
     unsigned *cost_table;       // ... and the counting sort's table, whose histogram rows the propose kernel's blocks add to
     double *done_sums;          // ... whose out-of-support proposals the propose kernel publishes itself ([e * n + p])
     int *done_info;
+    // Michaelis-Menten path, rejection at start (smc_set_start_reject): the propose kernel writes mm_reject_threshold() of every
+    // proposal here (nullptr: off in this sweep), from the data set's n_t and sigma (thr_est_sigma: the proposal's third parameter)
+    double *reject_thr;
+    double thr_sigma_fixed;
+    int thr_n_t, thr_est_sigma;
 };
 
+
+// ---------------------------------------------------------------------------------------------
+// Rejection threshold of a Michaelis-Menten proposal (mm_kernels.hip: the look in MMOps::start_values)
+// ---------------------------------------------------------------------------------------------
+// T such that: if the FINISHED sibling sums of squared residuals of a proposal add up to at least T, the accept kernel rejects
+// the proposal whatever its unfinished solves return.  One definition for the propose kernel (which writes T[p] once per sweep)
+// and the host (smc_mm_reject_threshold, tests/test_reject_threshold.py); everything that needs exp, log or Philox happens here,
+// so that the solve kernel's look is loads, adds and one comparison.
+//
+// The accept kernel (mm_finish_kernel) computes, in double precision,
+//     lk2 = sum_k fl(c0 - fl(S_k / d)),  c0 = (-n_t/2) log(2 pi sigma^2),  d = 2 sigma^2,     k = 0 .. n_ex - 1, from 0.0
+//     pp  = exp(fl(fl(lk2 - lk1) * gamma)) [* pratio],          accept  <=>  pp >= rr.
+// Every operation of lk2 is monotone (non-increasing) in each S_k >= 0, so lk2 <= its value with 0 for every unfinished sum
+// (the argument above mm_certainly_rejected).  With A the real sum of the finished S_k that value differs from the real number
+// L = n_ex c0 - A / d by at most 3 n_ex <= 48 roundings of quantities no larger than M = n_ex |c0| + A / d: |error| < 6e-15 M.
+// fl(lk2 - lk1) and the product with gamma add two roundings of at most |L| + |lk1|; exp, the product with pratio and the log
+// of this function move the exponent by a few 1e-16 (1 + |E|), E = log rr - log pratio.  Hence pp < rr is CERTAIN when
+//     gamma (L - lk1) + eps_r gamma (M + |lk1|) < E - eps_e (1 + |E|)
+// for any eps_r >= 1e-14, eps_e >= 1e-15.  Chosen: eps_r = 2e-10, eps_e = 1e-12 (the margin mm_certainly_rejected gives its exp) -
+// four and three orders of magnitude more than the roundoff, which also covers the last-bit differences between the host's and the
+// device's log, and the rounding of the look's own sum (n_ex adds).  Solved for A:
+//     A >= T = d (B + eps_r scale) (1 + eps_r),    B = n_ex c0 - lk1 - (E - eps_e (1 + |E|)) / gamma,
+//                                                  scale = n_ex |c0| + |lk1| + (1 + |E|) / gamma   (>= M + |lk1| - A/d, whose A/d
+//                                                  term is what the factor 1 + eps_r pays for).
+// The margin gives away at most (2 eps_r + eps_e) scale: where B >= 1e-3 scale that is 4.1e-7 of the real-number threshold.
+// B + eps_r scale <= 0: the proposal is rejected with no residual at all - A = 0 satisfies the inequality - and T = 0: every look
+// cancels.  (Common in the first tempering steps: a proposal that raises sigma lowers n_ex c0 by n_ex n_t log(sigma' / sigma), more
+// than a current point that fits as badly as a prior draw can lose, and more than log(rr) / gamma allows once gamma is not tiny.)
+// WHEN IN DOUBT, NEVER: T = +inf (the look cancels nothing) for a proposal outside the support (never solved anyway), rr not in
+// (0, 1] (rr == 0 accepts everything), sigma <= 0, gamma <= 0, pratio not a positive finite number, n_ex or n_t < 1, any NaN or
+// infinity among the inputs, and 0 < B + eps_r scale with B < 1e-3 scale - the terms cancel to three digits or more, the bound on
+// the margin above does not hold there, and a thin band of proposals is all it costs.
+// pratio: p0_2 / p0_1 in the ratio prior modes, exactly 1.0 in SMC_PRIOR_MODE_MASK.
+__host__ __device__ inline double mm_reject_threshold(double lk1, double gamma, double rr, double sigma, int n_ex, int n_t,
+                                                      double pratio, int in_support) {
+    constexpr double kEpsR = 2e-10, kEpsE = 1e-12, kMinB = 1e-3, kMax = 1.7976931348623157e308;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+#else
+    const double inf = __builtin_inf();
+#endif
+    if (!in_support || n_ex < 1 || n_t < 1) return inf;
+    if (!(rr > 0.0 && rr <= 1.0) || !(sigma > 0.0 && sigma <= kMax) || !(gamma > 0.0 && gamma <= kMax)) return inf;
+    if (!(pratio > 0.0 && pratio <= kMax) || !(lk1 >= -kMax && lk1 <= kMax)) return inf;
+    const double s2 = sigma * sigma;
+    const double c0 = (-0.5 * n_t) * log(2.0 * 3.141592653589793 * s2);     // as mm_finish_kernel
+    const double d = 2.0 * s2;
+    const double E = pratio == 1.0 ? log(rr) : log(rr) - log(pratio);
+    const double aE = 1.0 + fabs(E);
+    const double B = (double)n_ex * c0 - lk1 - (E - kEpsE * aE) / gamma;
+    const double scale = (double)n_ex * fabs(c0) + fabs(lk1) + aE / gamma;
+    if (!(scale <= kMax) || B != B) return inf;
+    if (B + kEpsR * scale <= 0.0) return 0.0;
+    if (!(B >= kMinB * scale)) return inf;
+    const double T = d * (B + kEpsR * scale) * (1.0 + kEpsR);
+    return (T > 0.0 && T <= kMax) ? T : inf;
+}
 
 struct EventPair {
     hipEvent_t a, b;
@@ -220,7 +284,8 @@ struct smc_ctx {
     int64_t recvbuf_cap = 0;
     // sweep scratch: per (experiment, particle) sums of squared residuals and solver info, support
     // flags of the proposals, the global work counter of the persistent solve kernel
-    double *d_sum_r2 = nullptr;
+    double *d_sum_r2 = nullptr;            // n_ex rows of item_cap, and one more: the rejection thresholds of a Metropolis sweep's
+                                           // proposals (mm_reject_threshold) lie behind the n_ex rows of n sums of that sweep
     int *d_info = nullptr;
     int64_t item_cap = 0;            // particles the two arrays above can hold (x kMaxEx experiments)
     uint8_t *d_p0 = nullptr;
@@ -233,6 +298,13 @@ struct smc_ctx {
     unsigned long long *d_queue = nullptr;
     unsigned long long *d_finish_rows = nullptr;   // accept kernel: one row of counts per block + its arrival counter (mm_kernels.hip)
     smc::RejectArgs *d_reject = nullptr;   // early-rejection arguments of the running sweep (written by its propose kernel)
+    int start_reject = 1;                  // do not start a solve whose proposal its finished siblings already reject (smc_set_start_reject) ...
+    bool start_reject_env_off = false;     // ... unless the environment says SMC_START_REJECT=0
+    // The look is dropped by the host, the way the in-phase patience is decided: once a Metropolis sweep that looked left fewer than
+    // 1 item in 100 unstarted, the following sweeps neither compute thresholds nor look (a posterior-like sweep pays the loads for
+    // nothing: +2.4 % per sweep, profiles/r08_ab_start_reject.log), until a likelihood sweep announces a new population.
+    bool start_look_pending = false, start_look_idle = false;   // the sweep whose counters come next looked / the look is dropped
+    int64_t w_not_started = 0;             // Michaelis-Menten items cancelled before their first attempt, since smc_create (smc_mm_start_reject_info)
     int32_t *d_stiff_list = nullptr;       // stiff list (item_cap entries) and its two alternating counters
     unsigned *d_stiff_count = nullptr;
     int stiff_parity = 0;

@@ -62,6 +62,8 @@ class SMCSettings:
     early_reject: bool = True         # stop a solve once its proposal is certainly rejected (exact; HipEngine.set_early_reject)
     share_replicates: bool = True     # one integration per pair of replicate experiments (same results; HipEngine.set_share_replicates;
                                       # the environment variable SMC_SHARE_REPLICATES=0 turns it off whatever this says)
+    start_reject: bool = True         # do not start a solve whose proposal its finished siblings already reject (same results; needs
+                                      # early_reject; HipEngine.set_start_reject; SMC_START_REJECT=0 turns it off whatever this says)
     stiff_first: bool = True          # hand the predictably long solves out first (same results; HipEngine.set_stiff_first)
     in_phase: bool = True             # homogeneous Metropolis sweeps run their waves in phase (same results; HipEngine.set_in_phase)
     cost_order: bool = True           # heterogeneous ones hand their solves out by cost class, in phase (same results; set_cost_order)
@@ -360,6 +362,10 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     if getattr(engine, "model", ("",))[0] == "mm" and hasattr(engine, "set_share_replicates"):
         engine.set_share_replicates(s.share_replicates)
         mm_shared0 = engine.share_info()["rk_attempts_shared"]
+    mm_not_started0 = None            # ... and of items cancelled before their first attempt (HipEngine.set_start_reject)
+    if getattr(engine, "model", ("",))[0] == "mm" and hasattr(engine, "set_start_reject"):
+        engine.set_start_reject(s.start_reject)
+        mm_not_started0 = engine.start_reject_info()["solves_not_started"]
     if hasattr(engine, "set_in_phase"):
         engine.set_in_phase(s.in_phase)
     if hasattr(engine, "set_cost_order"):
@@ -558,6 +564,8 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     engine.synchronize()
     if mm_shared0 is not None:        # rk_attempts counts per experiment, as the reference does: this many of them were not executed
         stats["rk_attempts_shared"] = engine.share_info()["rk_attempts_shared"] - mm_shared0
+    if mm_not_started0 is not None:   # items whose finished siblings had already decided the rejection when their turn came
+        stats["solves_not_started"] = engine.start_reject_info()["solves_not_started"] - mm_not_started0
     if dump_dir:                                                              # SavePosteriorcsv, :434-436
         final = engine.download_particles(SMC_SET_PRED)
         _dump(dump_dir, "pred/last_p_pred", final, rank, world)

@@ -380,6 +380,22 @@ class HipEngine:
         self._ck(self.L.smc_mm_share_info(self.ctx, ctypes.byref(ns), ctypes.byref(sh)), "smc_mm_share_info")
         return {"n_solve": ns.value, "rk_attempts_shared": sh.value}
 
+    def set_start_reject(self, enable=True):
+        """Do not start a Michaelis-Menten solve whose proposal its finished siblings already reject (include/smc_hip.h:
+        smc_set_start_reject; no effect unless early rejection is on)."""
+        if "smc_set_start_reject" in B.MISSING:        # A/B build of an earlier revision (SMC_HIP_LIB)
+            return
+        self._ck(self.L.smc_set_start_reject(self.ctx, int(bool(enable))), "smc_set_start_reject")
+
+    def start_reject_info(self):
+        """{"solves_not_started": (particle, experiment) items of this engine's Metropolis sweeps cancelled before their first
+        attempt, since the engine was created} (smc_mm_start_reject_info)."""
+        if "smc_mm_start_reject_info" in B.MISSING:    # A/B build of an earlier revision (SMC_HIP_LIB)
+            return {"solves_not_started": 0}
+        v = ctypes.c_int64(0)
+        self._ck(self.L.smc_mm_start_reject_info(self.ctx, ctypes.byref(v)), "smc_mm_start_reject_info")
+        return {"solves_not_started": v.value}
+
     def set_stiff_first(self, enable=True):
         """Hand the predictably long Michaelis-Menten solves out first (include/smc_hip.h: smc_set_stiff_first)."""
         if "smc_set_stiff_first" in B.MISSING:     # A/B build of a revision before the stiff list (SMC_HIP_LIB)

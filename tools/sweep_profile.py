@@ -1,5 +1,6 @@
 """Where one complete 10^6-particle run spends its time, sweep by sweep: wall time and device-counted RK45 attempts of the
 initial likelihood sweep and of every fused Metropolis iteration, and the time between them (ESS search, resampling).
+The sweeps are timed one call at a time (mh_batch=0: one synchronisation per iteration), so the run is a few ms slower than bench.py's.
 python tools/sweep_profile.py [n=1000000] [seed=1000] [stiff_first=1]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,7 +11,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 stiff = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 z = np.load(os.path.join(g.ROOT, "tests", "golden", "mm_data.npz"))
-s = pkg.SMCSettings(n_particle=n, stiff_first=bool(stiff))
+s = pkg.SMCSettings(n_particle=n, stiff_first=bool(stiff), mh_batch=0)
 with pkg.HipEngine(n, 3) as eng:
     eng.set_model_mm(z["t"], z["P_obs"], z["S0"])
     eng.set_prior(s.priors)
@@ -46,3 +47,4 @@ for name, ms, att, acc, gap, gam in log:
 sw = sum(l[1] for l in log[1:])
 print(f"sum: loglik {log[0][1]:.2f} ms, Metropolis sweeps {sw:.2f} ms, everything between them {sum(l[4] for l in log[1:]):.2f} ms")
 print("kernel time by class (HIP events):", {k: round(v["ms"], 2) for k, v in tm.items()})
+print("solves never started (rejection at start):", out["stats"].get("solves_not_started"))
