@@ -16,6 +16,7 @@
 #include "philox.h"
 #include "prior.h"
 #include "smc_internal.h"
+#include "reject_bound.h"
 
 namespace smc {
 
@@ -144,16 +145,7 @@ __device__ __attribute__((noinline)) bool meth_certainly_rejected(const RejectAr
         for (int e = 0; e < n_data; ++e) acc = meth_acc_step(acc, lane_bcast(dv[i], e));   // 0 for an unfinished experiment
         total = meth_loglike_step(total, c, acc, l);
     }
-    double rr;
-    if (r.device_rng) {
-        const u32x4 ru = philox_block(r.seed, (uint64_t)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
-        rr = u01_from(ru.x, ru.y);
-    } else {
-        rr = r.rr[p];
-    }
-    double pp = exp((total - r.lk1[p]) * r.gamma);
-    if (r.prior_mode != SMC_PRIOR_MODE_MASK) pp = pp * r.pratio[p];
-    return pp < rr * (1.0 - 1e-12);   // the margin covers a last-bit non-monotonicity of exp; any NaN: false
+    return reject_bound_fails(r, p, total);
 }
 
 // K8 over (particle, experiment) pairs of the resident set; one wave per solve (meth_dae_elem.h), persistent waves

@@ -36,6 +36,7 @@
 #include "philox.h"
 #include "prior.h"
 #include "smc_internal.h"
+#include "reject_bound.h"
 
 namespace smc {
 
@@ -521,24 +522,13 @@ __device__ __forceinline__ bool mm_certainly_rejected(const MMModel &mm, const S
         } else if (k == e_partner) {
             S = partial_partner;
         } else {
-            const double v = __longlong_as_double((long long)__hip_atomic_load(
-                reinterpret_cast<unsigned long long *>(a.sum_r2) + (int64_t)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            const double v = sibling_sum(a.sum_r2, (int64_t)k * a.n + p);
             if (v < 0.0) return true;      // kSumCancelled: a sibling has already established the rejection
             if (v == v) S = v;             // finished; NaN = still running (or failed): counts as 0
         }
         lk2_bound += mm_loglik_term(c0, S, s2);
     }
-    const RejectArgs &r = *a.rej;     // device memory, written by the propose kernel of this sweep
-    double rr;
-    if (r.device_rng) {
-        const u32x4 ru = philox_block(r.seed, (uint64_t)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
-        rr = u01_from(ru.x, ru.y);
-    } else {
-        rr = r.rr[p];
-    }
-    double pp = exp((lk2_bound - r.lk1[p]) * r.gamma);
-    if (r.prior_mode != SMC_PRIOR_MODE_MASK) pp = pp * r.pratio[p];
-    return pp < rr * (1.0 - 1e-12);   // the margin covers a last-bit non-monotonicity of exp
+    return reject_bound_fails(*a.rej, p, lk2_bound);     // *a.rej: device memory, written by the propose kernel of this sweep
 }
 
 // What solve_sched.h needs to know about a Michaelis-Menten item (see the list at the top of that file).

@@ -1,5 +1,5 @@
 // solve_sched.h -- the persistent, lane-level work scheduler of the likelihood sweeps, shared by the built-in
-// Michaelis-Menten kernel (mm_kernels.hip: MMOps) and the run-time compiled user-model kernel (user_model.hip: UserOps; this
+// Michaelis-Menten kernel (mm_kernels.hip: MMOps) and the run-time compiled user-model kernel (user_item_ops.h: Ops; this
 // file is handed to hiprtc as an in-memory header).  gfx950 (MI355X) only.
 //
 // What it schedules: the (particle, experiment) solves of one sweep (sim_particle, Micmem_likelihood.py:79-92) - n particles

@@ -5,7 +5,7 @@
 namespace smc {
 
 // What the exact early-rejection bound of a solve kernel needs (mm_kernels.hip: mm_certainly_rejected; meth_smc.hip:
-// meth_certainly_rejected; user_model.hip: UserOps::certainly_rejected).  Lives in DEVICE memory (ctx->d_reject) and is
+// meth_certainly_rejected; user_item_ops.h: Ops::certainly_rejected; their common tail is reject_bound.h).  Lives in DEVICE memory (ctx->d_reject) and is
 // written by the propose kernel of the sweep, so that the solve kernel carries one pointer instead of nine kernel arguments
 // in scalar registers through its attempt loops (144 SGPR spills).
 struct RejectArgs {

@@ -2,33 +2,24 @@
 // library appends this text to the user's source and hands the whole to hiprtc (user_model.hip: build_source).  It restates
 // solve_ivp(method="BDF", t_eval = t, rtol, atol) per lane as SciPy 1.15 has it (scipy/integrate/_ivp/bdf.py: the NDF
 // coefficients, the difference array D with change_D / compute_R, solve_bdf_system, the current_jac logic, the error-norm step
-// control with the order change over k-1, k, k+1, BdfDenseOutput; common.py: select_initial_step with order 1, num_jac) and
-// defines the same smc_user_solve_kernel entry point over a UserOps-style item, so that the scheduler (solve_sched.h), early
-// rejection, user_finish_kernel and the cost-hint scan are the RK45 path's.
+// control with the order change over k-1, k, k+1, BdfDenseOutput; common.py: select_initial_step with order 1, num_jac).
+//
+// Only the integrator is here.  The data an item reads, the adapter for the scheduler (solve_sched.h), early rejection, the
+// prediction stores, user_finish_kernel, the cost-hint scan and the kernel's body are what the RK45 kernel has:
+// user_item_ops.h, which also says how one text gives three kernels (appended twice for a multi-output source, the second
+// time with SMC_USER_PRED 1 and under other names).  No #pragma once; the names and SMC_USER_PRED are undefined again at the end.
 //
 // NumPy rounds every product and sum on its own: the integrator is compiled without contraction.  The small matrix products
 // (change_D, psi, the LU and its solves, the dense output) are plain sequential sums where SciPy calls BLAS / LAPACK, so
 // agreement with SciPy is at rounding level per step, not bitwise.  The user's functions are compiled once, with
 // smc_div(a, b) = a / b.
-//
-// One text, three kernels, as user_rk45_kernel.h: the one-output kernel (SMC_USER_NOBS not defined), and with SMC_USER_NOBS
-// defined the sweep kernel and, appended a second time with SMC_USER_PRED 1 under the names below, the prediction kernel.
-// What differs is in the blocks marked "data side" and "prediction".  No #pragma once; SMC_USER_PRED and the names are
-// undefined again at the end.
-#ifndef SMC_USER_PRED
-#define SMC_USER_PRED 0
-#endif
+#pragma clang fp contract(off)
+#include "user_item_ops.h"  // in-memory header handed to hiprtc by the library: all of a kernel that is not an integrator
 #if SMC_USER_PRED
 #define smc_user_bdf smc_user_bdf_pred
-#define UserBdfOps UserBdfOpsPred
-#define smc_user_solve_kernel smc_user_predict_kernel
 #endif
-#include "sweep_args.h"     // in-memory headers handed to hiprtc by the library: the argument blocks,
-#include "philox.h"         // the counter-based generator (the early-rejection bound re-derives the acceptance uniform),
-#include "solve_sched.h"    // the scheduler of the RK45 kernel
-#define NS SMC_USER_NS
 namespace smc_user_bdf {
-#pragma clang fp contract(off)
+using namespace smc_user_item;   // DataRec, t_bound_of, emit, item_cache_times, py_min, py_max
 constexpr double kEps = 0x1.0p-52;
 constexpr int kMaxOrder = 5, kNewtonMaxIter = 4;
 constexpr int kRows = kMaxOrder + 3;        // D[0 .. order + 2]
@@ -43,8 +34,6 @@ constexpr double kU[6][6] = {{1, 1, 1, 1, 1, 1}, {0, -1, -2, -3, -4, -5}, {0, 0,
 constexpr double kNumJacDiffReject = 0x1.6a09e667f3bcdp-46, kNumJacDiffSmall = 0x1.0p-39, kNumJacDiffBig = 0x1.0p-13;
 constexpr double kNumJacMinFactor = 0x1.f4p-43;
 
-__device__ __forceinline__ double py_min(double a, double b) { return (b < a) ? b : a; }   // Python's min / max
-__device__ __forceinline__ double py_max(double a, double b) { return (b > a) ? b : a; }
 __device__ __forceinline__ double np_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }   // np.maximum
 // tab[k] for a per-lane k < 6, by selects (an indexed read of a register array would go through scratch)
 __device__ __forceinline__ double pick(const double (&tab)[6], int k) {
@@ -66,6 +55,7 @@ __device__ __forceinline__ double norm(const double *x) {
 // bdf.py's `while not step_accepted` body (its Newton iterations, Jacobian refresh and LU factorisation included) and,
 // when the step is accepted, the order change and the t_eval outputs it covers.  sr2 accumulates (obs - smc_user_obs)^2.
 struct Item {
+    static constexpr bool kFuseOutputs = false;   // NumPy rounds an output's residuals one by one (user_item_ops.h: emit)
     double t, h_abs, sr2;
     double t_bound, t_next;        // t_eval[n_t - 1]; t_eval[i_out] (+inf when every data time has been served)
     double D[kRows][NS];           // differences; before the first attempt D[1] holds f(t0, y0) (fresh)
@@ -73,7 +63,7 @@ struct Item {
     double jac_factor[NS];         // num_jac's per-column factor (no smc_user_jac)
     int piv[NS];
 #ifdef SMC_USER_NOBS
-    double *pred;   // prediction kernel: where the outputs of t_eval[i_out] go (UserBdfOps::set_pred); else nullptr
+    double *pred;   // prediction kernel: where the outputs of t_eval[i_out] go (user_item_ops.h: Ops::set_pred); else nullptr
 #endif
 #if defined(SMC_USER_NOISE) && SMC_USER_NOISE
     smc_obs::Noise nz;   // noise model (user_obs_args.h): the particle's weights; sr2 then holds the excess sum X_e
@@ -82,33 +72,6 @@ struct Item {
     bool fresh, in_step, current_jac, lu_valid;
     unsigned n_steps, n_newton, n_lu, n_jac;   // accepted steps, Newton iterations, LU factorisations, Jacobian evaluations
 };
-
-// ---- data side: one data time of an experiment, the end time of its row, and what an output adds to the item ----
-#ifdef SMC_USER_NOBS
-// several outputs: the records of user_obs_args.h; the row's own end time is kept in its last record
-using DataRec = smc_obs::Rec;
-__device__ __forceinline__ double t_bound_of(const DataRec *tp, int n_t) { return tp[n_t].y[0]; }
-__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, const double *obs) {
-#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
-    smc_obs::emit_noise<SMC_USER_PRED, false>(it.sr2, it.pred, it.nz, yy, theta, cond, t_out, obs);
-#else
-    smc_obs::emit<SMC_USER_PRED, false>(it.sr2, it.pred, yy, theta, cond, t_out, obs);
-#endif
-}
-#else
-// one output: n_t + 1 (time, observation) pairs, the last one the sentinel (+inf, 0), as in the RK45 kernel
-using DataRec = double2;
-__device__ __forceinline__ double t_bound_of(const DataRec *tp, int n_t) { return tp[n_t - 1].x; }
-__device__ __forceinline__ void emit(Item &it, const double *yy, const double *theta, const double *cond, double t_out, double obs) {
-    const double r = obs - smc_user_ieee::smc_user_obs(t_out, yy, theta, cond);
-    it.sr2 += r * r;
-}
-#endif
-// ---- end of the data side ----
-__device__ __forceinline__ void item_cache_times(Item &it, const DataRec *tp, int n_t) {
-    it.t_bound = t_bound_of(tp, n_t);
-    it.t_next = tp[it.i_out].x;
-}
 // what a lane sets up for an item that has not had an attempt yet (item_begin and the pool's unpack)
 __device__ __forceinline__ void item_reset_lane(Item &it) {
 #pragma unroll
@@ -131,7 +94,6 @@ __device__ __forceinline__ void item_reset_lane(Item &it) {
     it.lu_valid = false;
     it.n_steps = it.n_newton = it.n_lu = it.n_jac = 0u;
 }
-
 
 __device__ __forceinline__ void rhs(double t, const double *y, const double *theta, const double *cond, double *f) {
     smc_user_ieee::smc_user_rhs(t, y, theta, cond, f);
@@ -620,310 +582,83 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
     }
     it.status = (accepted && t_new - t_bound >= 0) ? 1 : 0;    // base.py
 }
-}  // namespace smc_user_bdf
-
-// solve_sched.h's view of a BDF item: as UserOps of the RK45 kernel, plus the per-item work counters
-struct UserBdfOps {
-    struct Item {
-        smc_user_bdf::Item s;
-        double th[SMC_USER_DIM];
-        long long out_idx;      // e * n + p
-        int e;
-        unsigned attempts;
-    };
-    static constexpr int kPoolWords = 2 * NS + 6;
-    const smc::UserSolveArgs &a;
-    long long n;
-    int n_ex;
-    const int *list;
-    unsigned n_list;
-    const int *solo;
-    unsigned n_solo;
-    int patience;
-    long long n_pos;
-    const smc_user_bdf::DataRec *s_tp;
-    unsigned *counts;           // [k * n_ex * n + e * n + p], k: accepted steps, Newton iterations, LU factorisations, Jacobians
-
-    __device__ __forceinline__ const double *cond(int e) const { return a.cond + (long long)e * a.n_cond; }
-    __device__ __forceinline__ const smc_user_bdf::DataRec *row(int e) const { return s_tp + e * (a.n_t + 1); }
-    __device__ __forceinline__ void publish(long long idx, double sum, int info) const {
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(a.sum_r2) + idx, (unsigned long long)__double_as_longlong(sum),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.info[idx] = info;
+// What user_item_ops.h needs to know about the integrator (see the list at the top of that file).  Pool words 6 ..: y = D[0],
+// f = D[1] - only an item that has not had an attempt yet goes through the pool - and no flag in word 3.  The four work
+// counters of an item are published wherever it ends.
+struct Bdf {
+    using Item = smc_user_bdf::Item;
+    static __device__ __forceinline__ void begin(Item &s, const double *theta, const double *cond, const DataRec *tp, int n_t, double rtol,
+                                                 double atol) { item_begin(s, theta, cond, tp, n_t, rtol, atol); }
+    static __device__ __forceinline__ void attempt(Item &s, const double *theta, const double *cond, const DataRec *tp, double rtol,
+                                                   double atol) { item_attempt(s, theta, cond, tp, rtol, atol); }
+    static __device__ __forceinline__ int pool_flag(const Item &) { return 0; }
+    static __device__ __forceinline__ void set_pool_flag(Item &, int) {}
+    static __device__ __forceinline__ void pack(const Item &s, double *w) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            w[i * 64] = s.D[0][i];            // y0
+            w[(NS + i) * 64] = s.D[1][i];     // f(t0, y0)
+        }
     }
-    __device__ __forceinline__ void publish_counts(long long idx, const smc_user_bdf::Item &s) const {
-        const long long m = (long long)a.n_ex * a.n;
+    static __device__ __forceinline__ void unpack(Item &s, const double *w) {
+        item_reset_lane(s);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            s.D[0][i] = w[i * 64];
+            s.D[1][i] = w[(NS + i) * 64];
+        }
+    }
+    static __device__ __forceinline__ void broadcast(Item &u, const Item &s, int src) {
+        lane_progress(u, s, src);
+#pragma unroll
+        for (int r = 0; r < kRows; ++r)
+#pragma unroll
+            for (int i = 0; i < NS; ++i) u.D[r][i] = smc::lane_value(s.D[r][i], src);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            u.jac_factor[i] = smc::lane_value(s.jac_factor[i], src);
+            u.piv[i] = __builtin_amdgcn_readlane(s.piv[i], src);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                u.J[i][j] = smc::lane_value(s.J[i][j], src);
+                u.LU[i][j] = smc::lane_value(s.LU[i][j], src);
+            }
+        }
+        u.order = __builtin_amdgcn_readlane(s.order, src);
+        u.n_equal_steps = __builtin_amdgcn_readlane(s.n_equal_steps, src);
+        lane_outputs(u, s, src);
+        const int flags = (int)s.fresh | ((int)s.in_step << 1) | ((int)s.current_jac << 2) | ((int)s.lu_valid << 3);
+        const int uf = __builtin_amdgcn_readlane(flags, src);
+        u.fresh = (uf & 1) != 0;
+        u.in_step = (uf & 2) != 0;
+        u.current_jac = (uf & 4) != 0;
+        u.lu_valid = (uf & 8) != 0;
+        u.n_steps = (unsigned)__builtin_amdgcn_readlane((int)s.n_steps, src);
+        u.n_newton = (unsigned)__builtin_amdgcn_readlane((int)s.n_newton, src);
+        u.n_lu = (unsigned)__builtin_amdgcn_readlane((int)s.n_lu, src);
+        u.n_jac = (unsigned)__builtin_amdgcn_readlane((int)s.n_jac, src);
+    }
+    static __device__ __forceinline__ void no_work(Item &s) { s.n_steps = s.n_newton = s.n_lu = s.n_jac = 0u; }
+    // counts[k * m + idx], k: accepted steps, Newton iterations, LU factorisations, Jacobians
+    static __device__ __forceinline__ void publish_work(unsigned *counts, long long m, long long idx, const Item &s) {
         counts[idx] = s.n_steps;
         counts[m + idx] = s.n_newton;
         counts[2 * m + idx] = s.n_lu;
         counts[3 * m + idx] = s.n_jac;
     }
-    // ---- prediction: smc_user_predict_kernel (SMC_USER_PRED 1) writes the model's outputs to `pred`; an item's pointer to its
-    // next output follows from out_idx and i_out (no pool word).  A one-output item has no such pointer.
-    double *pred;               // UserObsArgs::pred; nullptr in every other kernel
-#ifdef SMC_USER_NOBS
-    __device__ __forceinline__ void set_pred(Item &it, int i) const {
-        it.s.pred = SMC_USER_PRED ? pred + (((it.out_idx - (long long)it.e * a.n) * a.n_ex + it.e) * a.n_t + i) * smc_obs::kObs : nullptr;
-    }
-    __device__ __forceinline__ void pred_from_lane(Item &u, const Item &it, int src) const {
-        u.s.pred = SMC_USER_PRED ? (double *)smc::lane_value_ll((long long)it.s.pred, src) : nullptr;
-    }
-    // NaN from the first output time not served on (past the row's end; from a failed solve's stop)
-    __device__ __forceinline__ void pred_tail(const Item &it) const {
-        if (SMC_USER_PRED) {
-            for (int i = it.s.i_out; i < a.n_t; ++i)
-                for (int k = 0; k < smc_obs::kObs; ++k) it.s.pred[(i - it.s.i_out) * smc_obs::kObs + k] = __longlong_as_double(0x7ff8000000000000LL);
-        }
-    }
-#else
-    __device__ __forceinline__ void set_pred(Item &, int) const {}
-    __device__ __forceinline__ void pred_from_lane(Item &, const Item &, int) const {}
-    __device__ __forceinline__ void pred_tail(const Item &) const {}
-#endif
-    // ---- end of prediction ----
-    __device__ __forceinline__ void load_theta(Item &it, long long p) const {
-#pragma unroll
-        for (int c = 0; c < SMC_USER_DIM; ++c) it.th[c] = a.theta[c * a.stride + p];
-#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
-        smc_obs::noise_weights(it.s.nz, it.th, a.n_ex, a.n_t);
-#endif
-    }
-    __device__ __forceinline__ int start(long long p, int e, bool from_list, Item &nb) const {
-        nb.out_idx = (long long)e * a.n + p;
-        nb.e = e;
-        nb.attempts = 0;
-        if (!from_list && list && a.listed[p] != 0) return smc::kStartSkipped;
-        if (a.p0 && a.p0[p] == 0) {
-            nb.s.n_steps = nb.s.n_newton = nb.s.n_lu = nb.s.n_jac = 0u;
-            publish_counts(nb.out_idx, nb.s);
-            publish(nb.out_idx, 0.0, 0);
-            return smc::kStartDone;
-        }
-        load_theta(nb, p);
-        set_pred(nb, 0);
-        smc_user_bdf::item_begin(nb.s, nb.th, cond(e), row(e), a.n_t, a.rtol, a.atol);
-        if (nb.s.status == 0) return smc::kStartStarted;
-        publish_counts(nb.out_idx, nb.s);
-        pred_tail(nb);
-        publish(nb.out_idx, nb.s.sr2, nb.s.status < 0 ? (1 << 30) : 0);
-        return smc::kStartDone;
-    }
-    __device__ __forceinline__ void pack(const Item &nb, double *slot) const {
-        slot[0 * 64] = nb.s.t;
-        slot[1 * 64] = nb.s.h_abs;
-        slot[2 * 64] = nb.s.sr2;
-        slot[3 * 64] = __hiloint2double(nb.s.i_out, 0);
-        slot[4 * 64] = __hiloint2double((int)nb.attempts, nb.e);
-        slot[5 * 64] = __longlong_as_double(nb.out_idx);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            slot[(6 + i) * 64] = nb.s.D[0][i];          // y0
-            slot[(6 + NS + i) * 64] = nb.s.D[1][i];     // f(t0, y0)
-        }
-    }
-    __device__ __forceinline__ void unpack(Item &it, const double *slot) const {
-        smc_user_bdf::item_reset_lane(it.s);
-        it.s.t = slot[0 * 64];
-        it.s.h_abs = slot[1 * 64];
-        it.s.sr2 = slot[2 * 64];
-        const double w4 = slot[4 * 64];
-        it.s.i_out = __double2hiint(slot[3 * 64]);
-        it.e = __double2loint(w4);
-        it.attempts = (unsigned)__double2hiint(w4);
-        it.out_idx = __double_as_longlong(slot[5 * 64]);
-        set_pred(it, it.s.i_out);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            it.s.D[0][i] = slot[(6 + i) * 64];
-            it.s.D[1][i] = slot[(6 + NS + i) * 64];
-        }
-        smc_user_bdf::item_cache_times(it.s, row(it.e), a.n_t);
-        load_theta(it, it.out_idx - (long long)it.e * a.n);
-    }
-    __device__ __forceinline__ int attempt(Item &it) const {
-        smc_user_bdf::item_attempt(it.s, it.th, cond(it.e), row(it.e), a.rtol, a.atol);
-        ++it.attempts;
-        if (it.attempts >= 0x1fffffffu) it.s.status = -1;        // hard bound so that every wave drains
-        return it.s.status;
-    }
-    __device__ __forceinline__ int uniform_attempts(Item &it, int budget) const { return smc::uniform_attempts_plain(*this, it, budget); }
-    __device__ __forceinline__ bool long_running(const Item &it) const { return it.attempts > 64u; }
-    __device__ __forceinline__ long long positions() const { return n_pos; }
-    __device__ __forceinline__ int start_at(long long pos, int e, Item &nb) const {
-        return start(a.order ? (long long)a.order[pos] : pos, e, false, nb);
-    }
-    __device__ __forceinline__ void finish(Item &it, int st) const {
-        pred_tail(it);
-        publish_counts(it.out_idx, it.s);
-        publish(it.out_idx, it.s.sr2, (int)(it.attempts & 0x1fffffffu) | ((st < 0) ? (1 << 30) : 0));
-    }
-    __device__ __forceinline__ Item broadcast(const Item &it, int src) const {
-        Item u;
-        u.s.t = smc::lane_value(it.s.t, src);
-        u.s.h_abs = smc::lane_value(it.s.h_abs, src);
-        u.s.sr2 = smc::lane_value(it.s.sr2, src);
-        u.s.t_bound = smc::lane_value(it.s.t_bound, src);
-        u.s.t_next = smc::lane_value(it.s.t_next, src);
-#pragma unroll
-        for (int r = 0; r < smc_user_bdf::kRows; ++r)
-#pragma unroll
-            for (int i = 0; i < NS; ++i) u.s.D[r][i] = smc::lane_value(it.s.D[r][i], src);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            u.s.jac_factor[i] = smc::lane_value(it.s.jac_factor[i], src);
-            u.s.piv[i] = __builtin_amdgcn_readlane(it.s.piv[i], src);
-#pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                u.s.J[i][j] = smc::lane_value(it.s.J[i][j], src);
-                u.s.LU[i][j] = smc::lane_value(it.s.LU[i][j], src);
-            }
-        }
-        u.s.order = __builtin_amdgcn_readlane(it.s.order, src);
-        u.s.n_equal_steps = __builtin_amdgcn_readlane(it.s.n_equal_steps, src);
-        pred_from_lane(u, it, src);
-        u.s.i_out = __builtin_amdgcn_readlane(it.s.i_out, src);
-        u.s.status = __builtin_amdgcn_readlane(it.s.status, src);
-        const int flags = (int)it.s.fresh | ((int)it.s.in_step << 1) | ((int)it.s.current_jac << 2) | ((int)it.s.lu_valid << 3);
-        const int uf = __builtin_amdgcn_readlane(flags, src);
-        u.s.fresh = (uf & 1) != 0;
-        u.s.in_step = (uf & 2) != 0;
-        u.s.current_jac = (uf & 4) != 0;
-        u.s.lu_valid = (uf & 8) != 0;
-        u.s.n_steps = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_steps, src);
-        u.s.n_newton = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_newton, src);
-        u.s.n_lu = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_lu, src);
-        u.s.n_jac = (unsigned)__builtin_amdgcn_readlane((int)it.s.n_jac, src);
-#pragma unroll
-        for (int c = 0; c < SMC_USER_DIM; ++c) u.th[c] = smc::lane_value(it.th[c], src);
-#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
-#pragma unroll
-        for (int k = 0; k < smc_obs::kObs; ++k) {
-            u.s.nz.w[k] = smc::lane_value(it.s.nz.w[k], src);
-#if SMC_USER_NOISE_PROP
-            u.s.nz.q[k] = smc::lane_value(it.s.nz.q[k], src);
-#endif
-        }
-#endif
-        u.out_idx = smc::lane_value_ll(it.out_idx, src);
-        u.e = __builtin_amdgcn_readlane(it.e, src);
-        u.attempts = (unsigned)__builtin_amdgcn_readlane((int)it.attempts, src);
-        return u;
-    }
-    __device__ __forceinline__ bool reject_enabled() const { return a.rej != nullptr; }
-    // exact early rejection: the bound of UserOps (RK45 kernel) - the sum of squared residuals only grows as outputs are emitted
-#if defined(SMC_USER_NOISE) && SMC_USER_NOISE
-    // EXACT early rejection under a noise model (user_obs_args.h): every observation not yet served sits at its floor
-    // log(a_k s_k), known from theta, and the published sums are excesses over it, which only grow - so the likelihood formed
-    // from the sums SO FAR (0 for a sibling still running) is an upper bound.  user_finish_noise_kernel's expression, in its order.
-    __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
-        const long long p = it.out_idx - (long long)it.e * a.n;
-        if (!smc_obs::noise_valid(it.th, a.n_ex, a.n_t)) return false;
-        double la[smc_obs::kObs];
-#pragma unroll
-        for (int k = 0; k < smc_obs::kObs; ++k) la[k] = log(smc_obs::noise_add(it.th, k, a.n_ex, a.n_t) * smc_obs::noise_scale(k, a.n_ex, a.n_t));
-        double lk2_bound = 0.0;
-        for (int k = 0; k < a.n_ex; ++k) {
-            double S = 0.0;
-            if (k == it.e) {
-                S = it.s.sr2;
-            } else {
-                const double v = __longlong_as_double((long long)__hip_atomic_load(
-                    reinterpret_cast<unsigned long long *>(a.sum_r2) + (long long)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (v < 0.0) return true;      // a sibling has already established the rejection
-                if (v == v) S = v;             // finished; NaN = still running: counts as 0
-            }
-            lk2_bound += smc_obs::noise_floor_of(k, la, a.n_ex, a.n_t) - S;
-        }
-        const smc::RejectArgs &r = *a.rej;
-        double rr;
-        if (r.device_rng) {
-            const smc::u32x4 ru = smc::philox_block(r.seed, (unsigned long long)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
-            rr = smc::u01_from(ru.x, ru.y);
-        } else {
-            rr = r.rr[p];
-        }
-        double pp = exp((lk2_bound - r.lk1[p]) * r.gamma);
-        if (r.prior_mode != 0) pp = pp * r.pratio[p];
-        return pp < rr * (1.0 - 1e-12);
-    }
-#else
-    __device__ __forceinline__ bool certainly_rejected(const Item &it) const {
-        const long long p = it.out_idx - (long long)it.e * a.n;
-        const double sigma = a.est_sigma ? it.th[SMC_USER_DIM - 1] : a.sigma_fixed;
-        if (!(sigma > 0.0)) return false;
-        const double s2 = sigma * sigma;
-        const double lg = log(2.0 * 3.141592653589793 * s2);
-#ifndef SMC_USER_NOBS   // data side: every experiment has n_t observations of scale 1
-        const double c0 = (-0.5 * a.n_t) * lg;
-#endif
-        double lk2_bound = 0.0;
-        for (int k = 0; k < a.n_ex; ++k) {
-            double S = 0.0;
-            if (k == it.e) {
-                S = it.s.sr2;
-            } else {
-                const double v = __longlong_as_double((long long)__hip_atomic_load(
-                    reinterpret_cast<unsigned long long *>(a.sum_r2) + (long long)k * a.n + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (v < 0.0) return true;
-                if (v == v) S = v;
-            }
-#ifdef SMC_USER_NOBS    // data side: the experiment's own count and scales
-            const double c0 = (-0.5 * smc_obs::me(k)) * lg - smc_obs::sum_log_scale(k, a.n_ex);
-#endif
-            lk2_bound += c0 - S / (2.0 * s2);
-        }
-        const smc::RejectArgs &r = *a.rej;
-        double rr;
-        if (r.device_rng) {
-            const smc::u32x4 ru = smc::philox_block(r.seed, (unsigned long long)(r.global_offset + p), r.stream, SMC_PHILOX_BLOCK_UNIFORM);
-            rr = smc::u01_from(ru.x, ru.y);
-        } else {
-            rr = r.rr[p];
-        }
-        double pp = exp((lk2_bound - r.lk1[p]) * r.gamma);
-        if (r.prior_mode != 0) pp = pp * r.pratio[p];
-        return pp < rr * (1.0 - 1e-12);
-    }
-#endif
-    __device__ __forceinline__ void cancel(Item &it) const {
-        publish_counts(it.out_idx, it.s);
-        publish(it.out_idx, -1.0, (int)(it.attempts & 0x1fffffffu) | (1 << 29));
-    }
 };
+}  // namespace smc_user_bdf
 
-// Outputs per item: the sum of squared residuals, attempts | cancelled << 29 | failed << 30, and the four work counters.
-// LDS per wave: a ring of 64 started items of UserBdfOps::kPoolWords words; then the data, read by every output
-#ifdef SMC_USER_NOBS   // data side: the image the host has built (user_obs_args.h)
+#ifdef SMC_USER_NOBS
 extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts, smc::UserObsArgs o) {
-    extern __shared__ double s_pool_all[];
-    double *s_pool = s_pool_all + (threadIdx.x >> 6) * (UserBdfOps::kPoolWords * 64);
-    static_assert(4 * UserBdfOps::kPoolWords * 64 == smc_obs::kHdrAt, "user_obs_args.h: the image follows the pools");
-    const smc_obs::Rec *s_tp = smc_obs::table(a.n_ex);
-    for (int i = threadIdx.x; i < o.img_len; i += blockDim.x) smc_obs::lds()[i] = o.img[i];
-    double *const pred = o.pred;
-#else                  // data side: the table of (time, observation) pairs, built here
-extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts) {
-    extern __shared__ double s_pool_all[];
-    double *s_pool = s_pool_all + (threadIdx.x >> 6) * (UserBdfOps::kPoolWords * 64);
-    double2 *s_tp = reinterpret_cast<double2 *>(s_pool_all + 4 * (UserBdfOps::kPoolWords * 64));
-    for (int i = threadIdx.x; i < a.n_ex * (a.n_t + 1); i += blockDim.x) {
-        const int e = i / (a.n_t + 1), k = i - e * (a.n_t + 1);
-        s_tp[i] = (k < a.n_t) ? make_double2(a.t[e * a.n_t + k], a.obs[e * a.n_t + k])
-                              : make_double2(__longlong_as_double(0x7ff0000000000000LL), 0.0);
-    }
-    double *const pred = nullptr;
-#endif
-    __syncthreads();
-    const unsigned n_list = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[0]) : 0u;
-    unsigned n_solo = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[1]) : 0u;
-    if (n_solo > a.solo_cap) n_solo = a.solo_cap;
-    UserBdfOps ops{a, a.n, a.n_ex, a.stiff_list, n_list, a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, a.patience,
-                   a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : a.n, s_tp, counts, pred};
-    smc::solve_persistent(ops, a.queue, s_pool);
+    SMC_USER_KERNEL_BODY(smc_user_bdf::Bdf, counts)
 }
-#if SMC_USER_PRED
-#undef smc_user_bdf
-#undef UserBdfOps
-#undef smc_user_solve_kernel
+#else
+extern "C" __global__ void __launch_bounds__(256) smc_user_solve_kernel(smc::UserSolveArgs a, unsigned *counts) {
+    SMC_USER_KERNEL_BODY(smc_user_bdf::Bdf, counts)
+}
 #endif
+#undef smc_user_bdf
+#undef smc_user_item
+#undef smc_user_solve_kernel
 #undef SMC_USER_PRED

@@ -31,10 +31,11 @@
 
 namespace smc {
 
-// solve_sched.h, sweep_args.h and philox.h as strings (csrc/Makefile generates the file from the headers themselves): hiprtc
-// gets them as in-memory headers, so the run-time compiled kernel is scheduled by the very code the built-in kernel uses.
-// The kernels themselves come the same way: user_rk45_kernel.h, user_bdf_kernel.h (one per SMC_USER_METHOD_*) and
-// user_cost_scan.h are device code only, appended to the user's text by build_source
+// solve_sched.h, sweep_args.h, philox.h and reject_bound.h as strings (csrc/Makefile generates the file from the headers
+// themselves): hiprtc gets them as in-memory headers, so the run-time compiled kernel is scheduled, and ends its rejection bound,
+// by the very code the built-in kernel uses.  The kernels themselves come the same way: user_rk45_kernel.h, user_bdf_kernel.h
+// (one integrator per SMC_USER_METHOD_*) and user_cost_scan.h are device code only, appended to the user's text by
+// build_source; user_item_ops.h, everything of a kernel that is not an integrator, is the header both of them include
 #include "embedded_headers.inc"
 
 // what the user's functions may call (include/smc_hip.h)
@@ -267,8 +268,10 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
 
 // the in-memory headers of a compilation, and with the source itself the files of a dump (smc_user_model_dump_source*)
 static const struct { const char *name, *text; } kUserHeaders[] = {
-    {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"solve_sched.h", k_solve_sched_h},
-    {"rk45_math.h", k_rk45_math_h}, {"user_obs_args.h", k_user_obs_args_h}, {"user_input.h", k_user_input_h}};
+    {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"reject_bound.h", k_reject_bound_h}, {"solve_sched.h", k_solve_sched_h},
+    {"rk45_math.h", k_rk45_math_h}, {"user_item_ops.h", k_user_item_ops_h}, {"user_obs_args.h", k_user_obs_args_h},
+    {"user_input.h", k_user_input_h}};
+constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
 // user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs
 static int user_headers(int n_obs, const UserInputGeom &geom, const char **texts, const char **names) {
     int n = 0;
@@ -285,7 +288,7 @@ static bool compile_user(const char *user_source, int n_states, int dim, int met
                          std::string &log, int noise = 0, const UserInputGeom &geom = UserInputGeom()) {
     const std::string src = build_source(user_source, n_states, dim, method, n_obs, noise, geom);
     hiprtcProgram prog;
-    const char *headers[8], *names[8];
+    const char *headers[kUserHeaderCount], *names[kUserHeaderCount];
     const int n_headers = user_headers(n_obs, geom, headers, names);
     if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", n_headers, headers, names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
@@ -462,7 +465,7 @@ void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
     if (n <= 0) return;
     ParticleSet &P = c->set[SMC_SET_PRED];
     UserModel *u = (UserModel *)c->user;
-    // exact early rejection (UserOps::certainly_rejected): off while the proposals' likelihoods are captured for inspection
+    // exact early rejection (user_item_ops.h: Ops::certainly_rejected): off while the proposals' likelihoods are captured for inspection
     const bool reject = c->early_reject != 0 && c->debug_capture == 0 && mh_in.gamma > 0.0 && c->d_reject;
     MHParams mh = mh_in;
     if (reject) {
@@ -753,7 +756,7 @@ static int user_model_dump_impl(const char *source, int n_states, int dim, int m
                                 const UserInputGeom &geom = UserInputGeom()) {
     if (!dir || !user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
     const std::string src = build_source(source, n_states, dim, method, n_obs, noise, geom);
-    const char *texts[8], *names[8];
+    const char *texts[kUserHeaderCount], *names[kUserHeaderCount];
     const int n_headers = user_headers(n_obs, geom, texts, names);
     for (int i = -1; i < n_headers; ++i) {
         FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : names[i])).c_str(), "w");

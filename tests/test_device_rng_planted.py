@@ -482,7 +482,7 @@ ER_LARGE = 400_000
 @pytest.mark.gpu
 @pytest.mark.parametrize("method", ["RK45", "BDF"])
 def test_early_rejection_of_the_user_kernels_changes_no_decision(pkg, method):
-    """user_rk45_kernel.h / user_bdf_kernel.h re-derive rr for their rejection bound: with the bound on and off the accepted
+    """The user kernels (user_item_ops.h, through reject_bound.h) re-derive rr for their rejection bound: with the bound on and off the accepted
     sets are the same, and they are the restated one.  This does NOT pin the uniform of these two bounds: measured on an
     MI355X, the bound of this three-attempt solve stopped nothing at n = 257 (6168 attempts on and off) nor at 200 000
     particles x 8 experiments (RK45: 4 800 000 on and off; BDF: 44 attempts of 19 199 937 fewer), and block 254 in both bounds

@@ -186,7 +186,8 @@ def test_user_model_kernel_is_under_the_same_control_flow_checks(pkg, tmp_path, 
     d = str(tmp_path)
     src = getattr(pkg.user_models, model)
     assert pkg.lib().smc_user_model_dump_source(src.encode(), n_states, 3, d.encode()) == 0
-    assert sorted(os.listdir(d)) == ["philox.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h"]
+    assert sorted(os.listdir(d)) == ["philox.h", "reject_bound.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h",
+                                     "user_item_ops.h"]
     U = _load_tool("uniformity_report")
     ll, uni = U.compile_ir(os.path.join(d, "smc_user_model.hip"), d, extra=("-I", d))
     name, cycles, n_div = U.kernel_cycles(ll, uni, "smc_user_solve_kernel")

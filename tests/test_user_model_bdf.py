@@ -78,7 +78,8 @@ def test_rk45_dump_is_unchanged_by_the_method_argument(pkg, tmp_path):
 def _bdf_dump(pkg, tmp_path, src, ns):
     d = str(tmp_path)
     assert pkg.lib().smc_user_model_dump_source2(src.encode(), ns, 3, BDF, d.encode()) == 0
-    assert sorted(os.listdir(d)) == ["philox.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h"]
+    assert sorted(os.listdir(d)) == ["philox.h", "reject_bound.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h",
+                                     "user_item_ops.h"]
     return d
 
 

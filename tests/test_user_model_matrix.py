@@ -1,4 +1,4 @@
-"""The user-model kernel family (csrc/user_rk45_kernel.h, user_bdf_kernel.h, user_obs_args.h, user_model.hip) over a covering set
+"""The user-model kernel family (csrc/user_rk45_kernel.h, user_bdf_kernel.h, user_item_ops.h, user_obs_args.h, user_model.hip) over a covering set
 of its instantiations - 1 .. 8 states, 1 .. 8 outputs, 3 .. 8 parameters with a noise parameter at index 7, three condition
 numbers, analytic and numerical Jacobians, every likelihood - on a linear chain whose solution is known exactly
 (tests/linear_chain_model.py, where the 14 cases, their data, the exact solutions, the bounds K and the swap counts live).

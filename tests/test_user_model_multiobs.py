@@ -87,8 +87,8 @@ def test_two_output_rk45_kernel_registers_and_scratch(pkg, tmp_path):
     (<= 128 VGPRs) and has no scratch traffic in its bulk attempt loop and no scratch store in any attempt loop."""
     d = str(tmp_path)
     assert pkg.lib().smc_user_model_dump_source3(pkg.user_models.CONSECUTIVE_REACTIONS_AB.encode(), 2, 3, RK45, 2, d.encode()) == 0
-    assert sorted(os.listdir(d)) == ["philox.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h",
-                                     "user_obs_args.h"]
+    assert sorted(os.listdir(d)) == ["philox.h", "reject_bound.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h",
+                                     "user_item_ops.h", "user_obs_args.h"]
     asm = os.path.join(d, "u.s")
     subprocess.run([HIPCC, *FLAGS, "-I", d, "-DSMC_ISA_MARKS", "-S", "--cuda-device-only", "-o", asm, os.path.join(d, "smc_user_model.hip")],
                    check=True, stderr=subprocess.DEVNULL, timeout=900)

@@ -167,13 +167,14 @@ def test_every_excess_term_is_non_negative_and_completes_the_density():
     np.testing.assert_allclose(np.log(a * s) + x, ref, rtol=1e-10, atol=1e-10)
 
 
-def test_dump_source4_writes_the_six_files_and_the_switches(pkg, tmp_path):
+def test_dump_source4_writes_the_eight_files_and_the_switches(pkg, tmp_path):
     src = pkg.user_models.CONSECUTIVE_REACTIONS_AB.encode()
     for prop in (0, 1):
         d = tmp_path / f"p{prop}"
         d.mkdir()
         assert pkg.lib().smc_user_model_dump_source4(src, 2, 5, RK45, 2, prop, str(d).encode()) == 0
-        assert sorted(os.listdir(d)) == ["philox.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h", "user_obs_args.h"]
+        assert sorted(os.listdir(d)) == ["philox.h", "reject_bound.h", "rk45_math.h", "smc_user_model.hip", "solve_sched.h", "sweep_args.h",
+                                         "user_item_ops.h", "user_obs_args.h"]
         head = (d / "smc_user_model.hip").read_text()[:400]
         assert "#define SMC_USER_NOISE 1\n" in head and f"#define SMC_USER_NOISE_PROP {prop}\n" in head
     d = tmp_path / "three"
