@@ -191,7 +191,8 @@ int smc_user_model_dump_source4(const char *source, int n_states, int dim, int m
  * m = 1 is a constant.  It EQUALS u[j] at t == tk[j] and NEVER LEAVES [min(u[j], u[j+1]), max(u[j], u[j+1])] (clamped), and it
  * is the same number in both namespaces of an RK45 source.  user_models.input_value is the definition in NumPy.  The
  * integrators do NOT stop at knots: as solve_ivp with np.interp inside f, they step over the kinks under their own step
- * control (a switch is a steep ramp between two close knots) - this is not SciPy-with-tstops, and there are no state resets.
+ * control (a switch is a steep ramp between two close knots).  What does stop the integrator, and changes the state by a jump,
+ * is a scheduled event: smc_set_model_user6 below.
  * Data: in_t n_ex x n_knot, a row by the row rules of t (a strictly increasing finite run of at least one knot, then only NaN);
  * in_u n_ex x n_knot x n_in, finite at the row's finite knots (and every slope finite) and ignored past them; n_knot <=
  * SMC_USER_MAX_KNOTS.  Anything else fails with the row, the knot and the rule.  smc_user_input_check applies these rules alone
@@ -224,6 +225,50 @@ int smc_user_model_check5(const char *source, int n_states, int dim, int method,
 int smc_user_model_dump_source5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, const char *dir);
 int smc_user_set_design_inputs(smc_ctx *ctx, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new);
+/* Scheduled events (doses, feed additions, washouts, resets): at known times the state changes by a jump and the integrator
+ * stops there.  Each experiment e has a row of event times ev_t[e][0 .. n_ev) and per event n_val numbers
+ * ev_v[e][j][0 .. n_val) (a dose amount, a target compartment, ...).  The source of a model with events defines one more
+ * ingredient (a source that contains the name must define it) and may call smc_event_value from it:
+ *     __device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond);   // y changed in place
+ *     double smc_event_value(const double *cond, int j, int k);     // value k of event j of this experiment
+ * cond is the handle to the experiment, as for smc_input, which smc_user_event may read too; smc_user_event always runs with
+ * IEEE division, like smc_user_y0.
+ * A solve of experiment e is the chain of solve_ivp calls a SciPy user would write.  With t0 = t[e][0] and t_end the row's last
+ * finite time the events that fire are those with t0 < tau_j < t_end, in order; segment s is solve_ivp(f, (a, b), y, method,
+ * t_eval = the row's data times in (a, b] (the first: [t0, b]), rtol, atol) with b the next firing event time or t_end; at an
+ * event smc_user_event(j, tau_j, y, ...) is applied to the segment's end state and the next segment starts afresh from
+ * (tau_j, y): RK45 with a new first derivative, select_initial_step over the new interval and no memory of a rejected step, BDF
+ * at order 1 with a new Jacobian and the initial step rule.  A data time equal to tau_j sees the state before the event, the
+ * next representable time after it the state after.  An event with tau_j >= t_end never fires; a segment may hold no data
+ * time; rk_attempts counts step attempts only; a failed segment fails the solve as before (info bit 30, NaN from the stop on).
+ * Event TIMES are data: they cannot depend on theta (amounts can, through smc_user_event), and there are no state-triggered
+ * events.
+ * Row rules: a row of ev_t is a strictly increasing finite run and then only NaN - it may have no event at all; every finite
+ * event time is > t[e][0]; the values are finite at a row's finite events and ignored past them.  Anything else fails with the
+ * row, the event and the rule.  smc_user_event_check applies these rules alone (no GPU, no context; the reason in
+ * smc_last_error(NULL)).
+ * smc_set_model_user6: the arguments of smc_set_model_user5, then ev_t (n_ex x n_ev), ev_v (n_ex x n_ev x n_val; NULL with
+ * n_val == 0), n_ev <= SMC_USER_MAX_EVENTS, 0 <= n_val <= SMC_USER_MAX_EVENT_VALUES.  n_ev == 0 with both pointers NULL is
+ * smc_set_model_user5, its path and its bits.  smc_user_model_check6 / smc_user_model_dump_source6: as the 5 functions plus the
+ * geometry n_ev, n_val the source is compiled for; a source that defines or calls the event names compiles only for a model
+ * with events ("smc_user_event: this model has no events"), and a model with events needs a source with smc_user_event.
+ * smc_user_set_design_events: the events of an explicit design of smc_user_predict_at / smc_user_predict_summary (the what-if
+ * dosing regimen; nothing is compiled again): n_ex_new rows of n_ev_new <= the model's n_ev events, held until replaced, both
+ * pointers NULL clears them.  An explicit design on a model with events without design events of the same n_ex_new fails with
+ * the reason; t_new == NULL uses the data's events. */
+#define SMC_USER_MAX_EVENTS 256
+#define SMC_USER_MAX_EVENT_VALUES 8
+int smc_set_model_user6(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                        const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
+                        const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
+                        int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot,
+                        const double *ev_t, const double *ev_v, int n_ev, int n_val);
+int smc_user_event_check(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val);
+int smc_user_model_check6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, char *log, int log_cap);
+int smc_user_model_dump_source6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, int n_ev, int n_val, const char *dir);
+int smc_user_set_design_events(smc_ctx *ctx, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new);
 /* Model PREDICTIONS of a user model (any of the three set functions; RK45 or BDF), for n host particles (n x dim, AoS; any n -
  * run in chunks of n_local): lk[n] as smc_loglik computes it and, unless pred is NULL, pred[((p * n_ex + e) * n_t + i) * n_obs + k]
  * = output k at t[e][i], written for every finite time whether or not obs is measured there; NaN past a row's end and from

@@ -18,6 +18,7 @@ SMC_SET_PRED, SMC_SET_FILT = 0, 1
 SMC_USER_METHOD_RK45, SMC_USER_METHOD_BDF = 0, 1
 SMC_USER_MAX_OBS = 8
 SMC_USER_MAX_INPUTS, SMC_USER_MAX_KNOTS = 8, 4096
+SMC_USER_MAX_EVENTS, SMC_USER_MAX_EVENT_VALUES = 256, 8
 USER_METHODS = {"RK45": SMC_USER_METHOD_RK45, "BDF": SMC_USER_METHOD_BDF}
 SMC_PRIOR_UNIFORM, SMC_PRIOR_NORMAL, SMC_PRIOR_FLAT = 0, 1, 2
 SMC_PRIOR_MODE_MASK, SMC_PRIOR_MODE_RATIO_MASK, SMC_PRIOR_MODE_RATIO = 0, 1, 2
@@ -77,6 +78,12 @@ SIGNATURES = {
     "smc_user_model_check5": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source5": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p]),
     "smc_user_set_design_inputs": (cint, [c_ctx, c_dp, c_dp, cint, cint]),
+    "smc_set_model_user6": (cint, [c_ctx, ctypes.c_char_p, cint, cint, c_dp, c_dp, c_dp, c_dp, cint, cint, cint, c_ip, c_dp, c_ip, c_dp,
+                                    f64, f64, cint, cint, f64, c_dp, c_dp, cint, cint, c_dp, c_dp, cint, cint]),
+    "smc_user_event_check": (cint, [c_dp, c_dp, c_dp, cint, cint, cint, cint]),
+    "smc_user_model_check6": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p, cint]),
+    "smc_user_model_dump_source6": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p]),
+    "smc_user_set_design_events": (cint, [c_ctx, c_dp, c_dp, cint, cint]),
     "smc_user_predict": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_at": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, cint, cint, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_summary": (cint, [c_ctx, cint, c_dp, c_dp, cint, cint, c_dp, cint, cint, u64, i64, ctypes.c_size_t, c_dp, c_dp,

@@ -71,6 +71,10 @@ struct Item {
     int order, n_equal_steps, i_out, status;   // status: 0 running, 1 finished, -1 TOO_SMALL_STEP
     bool fresh, in_step, current_jac, lu_valid;
     unsigned n_steps, n_newton, n_lu, n_jac;   // accepted steps, Newton iterations, LU factorisations, Jacobian evaluations
+#ifdef SMC_USER_EVENTS
+    double t_end;   // scheduled events (user_item_ops.h: item_cache_times): the row's end; t_bound is the SEGMENT's bound
+    int i_ev;       // the next event of the row: the first with tau > t
+#endif  // SMC_USER_EVENTS
 };
 // what a lane sets up for an item that has not had an attempt yet (item_begin and the pool's unpack)
 __device__ __forceinline__ void item_reset_lane(Item &it) {
@@ -333,7 +337,11 @@ __device__ __forceinline__ void solve_bdf_system(Item &it, const double *theta, 
 __device__ void item_begin(Item &it, const double *theta, const double *cond, const DataRec *tp, int n_t, double rtol_in,
                            double atol) {
     const double rtol = (rtol_in < 100 * kEps) ? 100 * kEps : rtol_in;      // common.py validate_tol
+#ifdef SMC_USER_EVENTS
+    const double t0 = tp[0].x, t_bound = smc_ev::segment_bound(cond, 0, t_bound_of(tp, n_t));   // the first step is sized by the segment
+#else  // SMC_USER_EVENTS
     const double t0 = tp[0].x, t_bound = t_bound_of(tp, n_t);
+#endif  // SMC_USER_EVENTS
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     item_reset_lane(it);
     it.t = t0;
@@ -372,8 +380,56 @@ __device__ void item_begin(Item &it, const double *theta, const double *cond, co
         while (tp[it.i_out].x <= it.t) { emit(it, y, theta, cond, tp[it.i_out].x, tp[it.i_out].y); ++it.i_out; }
         it.status = 1;
     }
+#ifdef SMC_USER_EVENTS
+    item_cache_times(it, cond, tp, n_t);
+#else  // SMC_USER_EVENTS
     item_cache_times(it, tp, n_t);
+#endif  // SMC_USER_EVENTS
 }
+#ifdef SMC_USER_EVENTS
+// The start of a segment at (it.t, y) that runs to it.t_bound - what a new solve_ivp(BDF) call sets up, which is what
+// item_begin sets up for the first: item_reset_lane (order 1, no Jacobian, no LU, num_jac's factors as new), D[0] = y,
+// D[1] = f(t, y) - the first attempt then scales it and evaluates J there - and common.py select_initial_step (order 1) over
+// the SEGMENT's length.  The work counters go on counting; the right-hand-side evaluations here are not step attempts.
+__device__ __forceinline__ void segment_start(Item &it, const double *y_in, const double *theta, const double *cond, double rtol, double atol) {
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const unsigned n_steps = it.n_steps, n_newton = it.n_newton, n_lu = it.n_lu, n_jac = it.n_jac;
+    double y0[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) y0[i] = y_in[i];
+    item_reset_lane(it);
+    it.n_steps = n_steps;
+    it.n_newton = n_newton;
+    it.n_lu = n_lu;
+    it.n_jac = n_jac;
+    const double t0 = it.t;
+    double *y = it.D[0], *f = it.D[1];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) y[i] = y0[i];
+    rhs(t0, y, theta, cond, f);
+    const double interval_length = fabs(it.t_bound - t0);
+    double scale[NS], tmp[NS], y1[NS], f1[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        scale[i] = atol + fabs(y[i]) * rtol;
+        tmp[i] = y[i] / scale[i];
+    }
+    const double d0 = norm(tmp);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) tmp[i] = f[i] / scale[i];
+    const double d1 = norm(tmp);
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = py_min(h0, interval_length);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) y1[i] = y[i] + h0 * 1.0 * f[i];
+    rhs(t0 + h0 * 1.0, y1, theta, cond, f1);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) tmp[i] = (f1[i] - f[i]) / scale[i];
+    const double d2 = norm(tmp) / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : sqrt(0.01 / py_max(d1, d2));   // ** (1 / 2)
+    it.h_abs = py_min(py_min(py_min(100 * h0, h1), interval_length), inf);
+}
+#endif  // SMC_USER_EVENTS
 
 // One pass of bdf.py _step_impl's `while not step_accepted` body; on acceptance also the rest of _step_impl (D update,
 // order change) and the t_eval outputs of the step through BdfDenseOutput (built after the step, as solve_ivp does).
@@ -580,6 +636,26 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         it.i_out = i_out;
         it.t_next = nx.x;
     }
+#ifdef SMC_USER_EVENTS
+    // The accepted step ends a segment in front of event i_ev (t_new == t_bound == tau < t_end).  The outputs up to and including
+    // tau are out, from the state BEFORE the event; now the event changes the end state D[0] and the next segment starts afresh
+    // from (tau, y), as a new solve_ivp call would: segment_start.  The item goes on (status 0).
+    // Termination: every event application advances i_ev, and i_ev <= SMC_USER_NEV because an event fires only with a finite
+    // tau < t_end and the table ends in +inf, so an item has at most SMC_USER_NEV + 1 segments.  Event times increase strictly
+    // and lie above t0, so every segment has positive length, and inside it the item is the solve it always was: t reaches
+    // t_bound, or TOO_SMALL_STEP above stops it (Ops::attempt bounds the attempts besides).  No loop is added.
+    if (accepted && t_new - t_bound >= 0 && t_bound < it.t_end) {
+        double y[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) y[s] = it.D[0][s];
+        smc_user_ieee::smc_user_event(it.i_ev, t_new, y, theta, cond);
+        ++it.i_ev;
+        it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+        segment_start(it, y, theta, cond, rtol, atol);
+        it.status = 0;
+        return;
+    }
+#endif  // SMC_USER_EVENTS
     it.status = (accepted && t_new - t_bound >= 0) ? 1 : 0;    // base.py
 }
 // What user_item_ops.h needs to know about the integrator (see the list at the top of that file).  Pool words 6 ..: y = D[0],

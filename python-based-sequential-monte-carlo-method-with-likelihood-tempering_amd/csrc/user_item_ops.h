@@ -72,11 +72,24 @@ __device__ __forceinline__ void emit(It &it, const double *yy, const double *the
 }
 #endif
 // ---- end of the data side ----
+#ifdef SMC_USER_EVENTS
+// Scheduled events: an item also holds t_end, the end time of its row, and i_ev, the index of its next event = the first
+// event with tau > t; t_bound is the bound of the SEGMENT it is in (user_event.h: segment_bound).  This is for an item that has
+// had no attempt (item_begin, the pool's unpack): it stands at t0, and every event time of a row is > t0, so i_ev = 0.
+template <class It>
+__device__ __forceinline__ void item_cache_times(It &it, const double *cond, const DataRec *tp, int n_t) {
+    it.t_end = t_bound_of(tp, n_t);
+    it.i_ev = 0;
+    it.t_bound = smc_ev::segment_bound(cond, 0, it.t_end);
+    it.t_next = tp[it.i_out].x;
+}
+#else  // SMC_USER_EVENTS
 template <class It>
 __device__ __forceinline__ void item_cache_times(It &it, const DataRec *tp, int n_t) {
     it.t_bound = t_bound_of(tp, n_t);
     it.t_next = tp[it.i_out].x;
 }
+#endif  // SMC_USER_EVENTS
 // An item's registers read from lane src (the uniform tail of solve_sched.h), in two groups that an integrator's broadcast
 // places among its own: where the solve stands, and which output comes next
 template <class It>
@@ -86,6 +99,10 @@ __device__ __forceinline__ void lane_progress(It &u, const It &s, int src) {
     u.sr2 = smc::lane_value(s.sr2, src);
     u.t_bound = smc::lane_value(s.t_bound, src);
     u.t_next = smc::lane_value(s.t_next, src);
+#ifdef SMC_USER_EVENTS
+    u.t_end = smc::lane_value(s.t_end, src);
+    u.i_ev = __builtin_amdgcn_readlane(s.i_ev, src);
+#endif  // SMC_USER_EVENTS
 }
 template <class It>
 __device__ __forceinline__ void lane_outputs(It &u, const It &s, int src) {
@@ -203,7 +220,11 @@ struct Ops {
         set_pred(it, it.s.i_out);
         it.s.status = 0;
         Integ::unpack(it.s, slot + 6 * 64);
+#ifdef SMC_USER_EVENTS
+        item_cache_times(it.s, cond(it.e), row(it.e), a.n_t);
+#else  // SMC_USER_EVENTS
         item_cache_times(it.s, row(it.e), a.n_t);
+#endif  // SMC_USER_EVENTS
         load_theta(it, particle(it));      // the parameters come from HBM / L2 again, not through the pool
     }
     __device__ __forceinline__ int attempt(Item &it) const {

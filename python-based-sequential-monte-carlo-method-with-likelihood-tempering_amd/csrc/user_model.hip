@@ -171,14 +171,25 @@ user_bdf_count_kernel(const uint8_t *__restrict__ p0mask, const unsigned *__rest
 
 // The compile-time geometry of a model with inputs (user_input.h): the model's n_cond, n_in inputs, kcap = the power of two >=
 // n_knot.  n_in = 0: a model without inputs - its source and its cond rows are what they always were.
+// ... and of a model with scheduled events (user_event.h): n_ev, the event capacity, and n_val values per event; the event
+// table follows the input table (or the cond numbers).  n_ev = 0: a model without events.
 struct UserInputGeom {
     int n_cond = 0, n_in = 0, kcap = 0;
-    int row_words() const { return n_cond + kcap + n_in * (2 * kcap + 1); }
+    int n_ev = 0, n_val = 0;
+    int in_words() const { return n_in > 0 ? n_cond + kcap + n_in * (2 * kcap + 1) : n_cond; }      // = the offset of the event table
+    int ev_words() const { return n_ev > 0 ? n_ev + 1 + n_ev * n_val : 0; }
+    int row_words() const { return in_words() + ev_words(); }
+    bool tabled() const { return n_in > 0 || n_ev > 0; }      // a cond row holds more than the model's cond numbers
 };
 // the inputs as a set function receives them (nullptr: none)
 struct UserInputs {
     const double *in_t, *in_u;      // n_ex x n_knot, n_ex x n_knot x n_in
     int n_in, n_knot;
+};
+// ... and the events (nullptr: none)
+struct UserEvents {
+    const double *ev_t, *ev_v;      // n_ex x n_ev, n_ex x n_ev x n_val (nullptr with n_val = 0)
+    int n_ev, n_val;
 };
 static int knot_capacity(int n_knot) {
     int k = 1;
@@ -224,10 +235,12 @@ struct UserModel {
     UserNoise nz{};
     // smc_set_model_user5: time-varying inputs (user_input.h).  The table lies behind each experiment's cond row, so d_cond holds
     // rows of geom.row_words() doubles; h_rows keeps the data's rows and design_* the inputs of an explicit design
+    // smc_set_model_user6: scheduled events (user_event.h).  Their table follows in the same rows; design_ev_* are the events of
+    // an explicit design (smc_user_set_design_events)
     UserInputGeom geom{};
-    std::vector<double> h_rows, design_t, design_u;
-    int design_n_ex = 0, design_n_knot = 0;
-    int cond_stride() const { return geom.n_in > 0 ? geom.row_words() : n_cond; }
+    std::vector<double> h_rows, design_t, design_u, design_ev_t, design_ev_v;
+    int design_n_ex = 0, design_n_knot = 0, design_ev_n_ex = 0, design_ev_n_ev = 0;
+    int cond_stride() const { return geom.tabled() ? geom.row_words() : n_cond; }
 };
 
 // an optional ingredient (smc_user_cost, smc_user_jac, smc_user_obs_vec; smc_div): a source that mentions it must define it
@@ -239,6 +252,9 @@ static bool mentions(const char *user_source, const char *name) { return strstr(
 // appended twice: the sweep kernel, then with SMC_USER_PRED 1 the prediction kernel smc_user_predict_kernel.
 // geom.n_in > 0 (smc_set_model_user5): SMC_USER_NCOND / NIN / KCAP and user_input.h in front, and smc_input made visible in the
 // namespace(s) of the user's text.  A source that calls smc_input without inputs is stopped by an #error that says so.
+// geom.n_ev > 0 (smc_set_model_user6): SMC_USER_EVENTS, SMC_USER_EVAT / NEV / NVAL and user_event.h in front, smc_event_value made
+// visible to the user's text, and the kernel file with its SMC_USER_EVENTS blocks (k_..._ev).  The event names and a model
+// without events, or events and a source without smc_user_event, stop with an #error that says so.
 static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs, int noise = 0,
                                 const UserInputGeom &geom = UserInputGeom()) {
     const bool bdf = method == SMC_USER_METHOD_BDF;
@@ -248,6 +264,15 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
             "\n#define SMC_USER_KCAP " + std::to_string(geom.kcap) + "\n#include \"user_input.h\"\n";
     else if (mentions(user_source, "smc_input"))
         s = "#error \"smc_input: this model has no inputs (n_in = 0) - set it with in_t / in_u through smc_set_model_user5\"\n";
+    const bool events = geom.n_ev > 0;
+    if (events) {
+        s += "#define SMC_USER_EVENTS 1\n#define SMC_USER_EVAT " + std::to_string(geom.in_words()) + "\n#define SMC_USER_NEV " +
+             std::to_string(geom.n_ev) + "\n#define SMC_USER_NVAL " + std::to_string(geom.n_val) + "\n#include \"user_event.h\"\n";
+        if (!mentions(user_source, "smc_user_event"))
+            s += "#error \"smc_user_event: this model has events and its source does not define smc_user_event\"\n";
+    } else if (mentions(user_source, "smc_user_event") || mentions(user_source, "smc_event_value")) {
+        s += "#error \"smc_user_event: this model has no events (n_ev = 0) - set it with ev_t / ev_v through smc_set_model_user6\"\n";
+    }
     s += "#define SMC_USER_NS " + std::to_string(n_states) + "\n#define SMC_USER_DIM " + std::to_string(dim) + "\n";
     if (n_obs > 0)
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
@@ -258,10 +283,11 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
     if (!bdf) s += mentions(user_source, "smc_div") ? "#define SMC_USER_USES_DIV 1\n" : "#define SMC_USER_USES_DIV 0\n";
     // #line: hiprtc's diagnostics point into the user's text
-    const std::string text = std::string(geom.n_in > 0 ? "using smc_in::smc_input;\n" : "") + "#line 1 \"user_model\"\n" + user_source + "\n";
+    const std::string text = std::string(geom.n_in > 0 ? "using smc_in::smc_input;\n" : "") + (events ? "using smc_ev::smc_event_value;\n" : "") +
+                             "#line 1 \"user_model\"\n" + user_source + "\n";
     s += bdf ? kUserBdfPrelude + text : kUserPreludeLean + text + kUserPreludeIeee + text;
     s += "}  // namespace smc_user_ieee\n";
-    const char *kernel = bdf ? k_user_bdf_kernel_h : k_user_rk45_kernel_h;
+    const char *kernel = bdf ? (events ? k_user_bdf_kernel_h_ev : k_user_bdf_kernel_h) : (events ? k_user_rk45_kernel_h_ev : k_user_rk45_kernel_h);
     if (n_obs > 0) s = s + "#include \"user_obs_args.h\"\n" + kernel + "#define SMC_USER_PRED 1\n";
     return s + kernel + k_user_cost_scan_h;
 }
@@ -270,14 +296,17 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
 static const struct { const char *name, *text; } kUserHeaders[] = {
     {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"reject_bound.h", k_reject_bound_h}, {"solve_sched.h", k_solve_sched_h},
     {"rk45_math.h", k_rk45_math_h}, {"user_item_ops.h", k_user_item_ops_h}, {"user_obs_args.h", k_user_obs_args_h},
-    {"user_input.h", k_user_input_h}};
+    {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}};
 constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
-// user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs
+// user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs, user_event.h with one that
+// has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks
 static int user_headers(int n_obs, const UserInputGeom &geom, const char **texts, const char **names) {
     int n = 0;
     for (const auto &h : kUserHeaders) {
-        if ((h.text == k_user_obs_args_h && n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0)) continue;
-        texts[n] = h.text;
+        if ((h.text == k_user_obs_args_h && n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
+            (h.text == k_user_event_h && geom.n_ev <= 0))
+            continue;
+        texts[n] = (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev : h.text;
         names[n++] = h.name;
     }
     return n;
@@ -619,7 +648,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
     const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls,
                                                     u->noise ? &u->nz : nullptr);
-    const int cs = u->cond_stride();      // a model with inputs: cond holds whole rows, the table included
+    const int cs = u->cond_stride();      // a model with inputs or events: cond holds whole rows, the tables included
     const size_t nc = (size_t)g * (cs > 0 ? cs : 1) * sizeof(double);
     dg.e0 = e0;
     dg.n_ex = g;
@@ -750,6 +779,22 @@ int smc_user_model_check5(const char *source, int n_states, int dim, int method,
     if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
     return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
 }
+// ... and of check6 / dump_source6: n_ev = 0 is a model without events, whose geometry is check5's
+static bool user_geom_of6(int noise, int n_cond, int n_in, int n_knot, int n_ev, int n_val, UserInputGeom &geom) {
+    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return false;
+    if (n_ev < 0 || n_ev > SMC_USER_MAX_EVENTS || n_val < 0 || n_val > SMC_USER_MAX_EVENT_VALUES) return false;
+    if (n_ev == 0) return true;
+    geom.n_cond = n_cond;
+    geom.n_ev = n_ev;
+    geom.n_val = n_val;
+    return true;
+}
+int smc_user_model_check6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, char *log, int log_cap) {
+    UserInputGeom geom;
+    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
+    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
+}
 
 // everything hiprtc would read, as files: `hipcc -I <dir>` compiles <dir>/smc_user_model.hip off line
 static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0,
@@ -783,6 +828,12 @@ int smc_user_model_dump_source5(const char *source, int n_states, int dim, int m
                                 int n_knot, const char *dir) {
     UserInputGeom geom;
     if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
+    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+}
+int smc_user_model_dump_source6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, int n_ev, int n_val, const char *dir) {
+    UserInputGeom geom;
+    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
     return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
 }
 
@@ -832,7 +883,7 @@ int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n
 // division, here and nowhere else; 0 from the last knot on).
 static std::vector<double> build_input_rows(const double *cond, const UserInputGeom &g, const double *in_t, const double *in_u, int n_ex,
                                             int n_knot, const std::vector<int> &m) {
-    const int K = g.kcap, W = g.row_words();
+    const int K = g.kcap, W = g.in_words();
     std::vector<double> rows((size_t)n_ex * W, 0.0);
     for (int e = 0; e < n_ex; ++e) {
         double *r = rows.data() + (size_t)e * W;
@@ -845,6 +896,65 @@ static std::vector<double> build_input_rows(const double *cond, const UserInputG
             for (int j = 0; j <= K; ++j) u[j] = in_u[((size_t)e * n_knot + (j < m[e] ? j : m[e] - 1)) * g.n_in + k];
             for (int j = 0; j < K; ++j) sl[j] = j < m[e] - 1 ? (u[j + 1] - u[j]) / (tk[j + 1] - tk[j]) : 0.0;
         }
+    }
+    return rows;
+}
+
+// the data rules of a model's scheduled events (include/smc_hip.h: smc_set_model_user6; user_models.event_layout is the same in
+// NumPy): ev_t n_ex x n_ev, every row a strictly increasing finite run (it may be empty) and then only NaN, every finite event
+// time > t[e][0]; ev_v n_ex x n_ev x n_val, finite at the row's finite events (nullptr with n_val = 0).  t == nullptr (the events
+// of a design whose times are not known yet) leaves the rule about t[e][0] out.  On success m[e] holds the events of row e;
+// "" = valid, else what is wrong.
+static std::string event_layout_error(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val,
+                                      std::vector<int> &m) {
+    if (n_ev < 1) return "n_ev = " + std::to_string(n_ev) + ": a model with events needs room for at least one";
+    if (n_ev > SMC_USER_MAX_EVENTS)
+        return "n_ev = " + std::to_string(n_ev) + " above the event capacity " + std::to_string(SMC_USER_MAX_EVENTS) + " (SMC_USER_MAX_EVENTS)";
+    if (n_val < 0 || n_val > SMC_USER_MAX_EVENT_VALUES) return "n_val = " + std::to_string(n_val) + " outside 0 .. 8 (SMC_USER_MAX_EVENT_VALUES)";
+    if (n_ex < 1) return "n_ex = " + std::to_string(n_ex) + ": no experiment";
+    if (t && n_t < 1) return "n_t = " + std::to_string(n_t) + ": no time";
+    if (!ev_t) return "NULL ev_t";
+    if ((n_val > 0) != (ev_v != nullptr)) return n_val > 0 ? "NULL ev_v with n_val > 0" : "ev_v given with n_val = 0 (it must be NULL)";
+    m.assign(n_ex, 0);
+    for (int e = 0; e < n_ex; ++e) {
+        const double *te = ev_t + (size_t)e * n_ev;
+        int len = 0;
+        while (len < n_ev && !std::isnan(te[len])) ++len;
+        const std::string row = "row " + std::to_string(e) + " of ev_t ";
+        for (int i = len; i < n_ev; ++i)
+            if (!std::isnan(te[i]))
+                return row + "has a NaN event time before a number at event " + std::to_string(i) + " (only a trailing run of NaN may shorten a row)";
+        for (int i = 0; i < len; ++i) {
+            if (!std::isfinite(te[i])) return row + "holds an infinite event time at event " + std::to_string(i);
+            if (i > 0 && !(te[i] > te[i - 1])) return row + "is not strictly increasing at event " + std::to_string(i);
+            if (t && !(te[i] > t[(size_t)e * n_t])) return row + "is not later than the row's first time t[e][0] at event " + std::to_string(i);
+        }
+        for (int i = 0; i < len; ++i)
+            for (int k = 0; k < n_val; ++k)
+                if (!std::isfinite(ev_v[((size_t)e * n_ev + i) * n_val + k]))
+                    return "row " + std::to_string(e) + " of ev_v is not finite at event " + std::to_string(i) + ", value " + std::to_string(k);
+        m[e] = len;
+    }
+    return "";
+}
+int smc_user_event_check(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val) {
+    std::vector<int> m;
+    const std::string bad = t ? event_layout_error(t, ev_t, ev_v, n_ex, n_t, n_ev, n_val, m) : std::string("NULL t");
+    return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_event_check: " + bad).c_str());
+}
+// The cond rows of a model with events (user_event.h) for events event_layout_error has accepted: `base` holds per experiment
+// the g.in_words() words in front (the cond numbers, with inputs their table); behind them the row's m[e] event times, +inf up
+// to and including index g.n_ev, and the values.  n_ev: the width of ev_t / ev_v as given, m[e] <= g.n_ev.
+static std::vector<double> build_event_rows(const double *base, const UserInputGeom &g, const double *ev_t, const double *ev_v, int n_ex,
+                                            int n_ev, const std::vector<int> &m) {
+    const int B = g.in_words(), W = g.row_words();
+    std::vector<double> rows((size_t)n_ex * W, 0.0);
+    for (int e = 0; e < n_ex; ++e) {
+        double *r = rows.data() + (size_t)e * W;
+        for (int j = 0; j < B; ++j) r[j] = base[(size_t)e * B + j];
+        for (int j = 0; j <= g.n_ev; ++j) r[B + j] = j < m[e] ? ev_t[(size_t)e * n_ev + j] : HUGE_VAL;
+        for (int j = 0; j < m[e]; ++j)
+            for (int k = 0; k < g.n_val; ++k) r[B + g.n_ev + 1 + j * g.n_val + k] = ev_v[((size_t)e * n_ev + j) * g.n_val + k];
     }
     return rows;
 }
@@ -878,7 +988,7 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
 static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
                                double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr,
-                               const UserInputs *in = nullptr) {
+                               const UserInputs *in = nullptr, const UserEvents *ev = nullptr) {
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
@@ -908,6 +1018,16 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         geom.kcap = knot_capacity(in->n_knot);
         rows = build_input_rows(cond, geom, in->in_t, in->in_u, n_ex, in->n_knot, knots);
     }
+    if (ev) {
+        std::vector<int> events;
+        const std::string bad_ev = t ? event_layout_error(t, ev->ev_t, ev->ev_v, n_ex, n_t, ev->n_ev, ev->n_val, events) : std::string("NULL t");
+        if (!bad_ev.empty()) return smc_fail(c, ("smc_set_model_user6: " + bad_ev).c_str());
+        if (n_cond > 0 && !cond) return smc_fail(c, "smc_set_model_user6: n_cond > 0 and cond is NULL");
+        geom.n_cond = n_cond;
+        geom.n_ev = ev->n_ev;
+        geom.n_val = ev->n_val;
+        rows = build_event_rows(in ? rows.data() : cond, geom, ev->ev_t, ev->ev_v, n_ex, ev->n_ev, events);
+    }
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
     std::string lg;
@@ -931,13 +1051,14 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         return smc_fail(c, "smc_set_model_user: the source mentions smc_user_cost but the scan kernel is missing from the module");
     }
     const size_t nt = (size_t)n_ex * n_t * sizeof(double);
-    const size_t nc = in ? rows.size() * sizeof(double) : (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
+    const bool tabled = in || ev;      // the cond rows carry a table
+    const size_t nc = tabled ? rows.size() * sizeof(double) : (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
     bool ok = hipMalloc(&u->d_cond, nc) == hipSuccess;
     if (ok && !multi)      // the one-output kernel reads the data itself
         ok = hipMalloc(&u->d_t, nt) == hipSuccess && hipMalloc(&u->d_obs, nt) == hipSuccess &&
              hipMemcpy(u->d_t, t, nt, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(u->d_obs, obs, nt, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && in) ok = hipMemcpy(u->d_cond, rows.data(), nc, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !in && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && tabled) ok = hipMemcpy(u->d_cond, rows.data(), nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !tabled && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
     {   // likelihood constants; and the image (one-output model: only if its data is what smc_set_model_user3 would accept)
         std::vector<double> k(2 * (size_t)n_ex, 0.0);
         for (int e = 0; e < n_ex; ++e) {
@@ -1042,11 +1163,11 @@ int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs,
                                atol, method, true);
 }
 
-// a model with a noise specification: smc_set_model_user4, and smc_set_model_user5 (`in`: its inputs)
+// a model with a noise specification: smc_set_model_user4, and smc_set_model_user5 / 6 (`in`: its inputs, `ev`: its events)
 static int set_model_user_noise(smc_ctx *c, const char *who, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                 const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                                 const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol,
-                                int method, const UserInputs *in) {
+                                int method, const UserInputs *in, const UserEvents *ev = nullptr) {
     if (!c) return smc_fail(nullptr, "NULL context");
     const std::string bad = noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed);
     if (!bad.empty()) return smc_fail(c, (std::string(who) + ": " + bad).c_str());
@@ -1058,7 +1179,7 @@ static int set_model_user_noise(smc_ctx *c, const char *who, const char *source,
         }
         if (last || fixed)
             return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, last ? 1 : 0,
-                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true, nullptr, in);
+                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true, nullptr, in, ev);
     }
     UserNoise nz{};
     for (int k = 0; k < kUserMaxObs; ++k) {
@@ -1069,7 +1190,7 @@ static int set_model_user_noise(smc_ctx *c, const char *who, const char *source,
         nz.scale[k] = (k < n_obs && obs_scale) ? obs_scale[k] : 1.0;
     }
     nz.prop = prop_index ? 1 : 0;
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in);
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in, ev);
 }
 
 int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
@@ -1097,6 +1218,58 @@ int smc_set_model_user5(smc_ctx *c, const char *source, int n_states, int n_obs,
         return smc_fail(c, "smc_set_model_user5: add_index is NULL (the sigma rule) and another part of a noise model is given");
     return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
                                method, true, nullptr, in);
+}
+
+int smc_set_model_user6(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
+                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
+                        double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot, const double *ev_t,
+                        const double *ev_v, int n_ev, int n_val) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    if (n_ev == 0) {      // no events: smc_set_model_user5's path and its bits
+        if (ev_t || ev_v) return smc_fail(c, "smc_set_model_user6: n_ev = 0 with ev_t or ev_v given (both must be NULL)");
+        return smc_set_model_user5(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index, add_fixed, prop_index,
+                                   prop_fixed, rtol, atol, method, est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot);
+    }
+    const UserInputs inputs{in_t, in_u, n_in, n_knot};
+    const UserInputs *in = &inputs;
+    if (n_in == 0) {
+        if (in_t || in_u) return smc_fail(c, "smc_set_model_user6: n_in = 0 with in_t or in_u given (both must be NULL)");
+        in = nullptr;
+    }
+    const UserEvents events{ev_t, ev_v, n_ev, n_val};
+    if (add_index)
+        return set_model_user_noise(c, "smc_set_model_user6", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
+                                    add_fixed, prop_index, prop_fixed, rtol, atol, method, in, &events);
+    if (add_fixed || prop_index || prop_fixed)
+        return smc_fail(c, "smc_set_model_user6: add_index is NULL (the sigma rule) and another part of a noise model is given");
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
+                               method, true, nullptr, in, &events);
+}
+
+int smc_user_set_design_events(smc_ctx *c, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_set_design_events: no user model has been set");
+    if (!ev_t_new && !ev_v_new) {
+        u->design_ev_t.clear();
+        u->design_ev_v.clear();
+        u->design_ev_n_ex = u->design_ev_n_ev = 0;
+        return 0;
+    }
+    if (u->geom.n_ev == 0) return smc_fail(c, "smc_user_set_design_events: the model has no events (set it through smc_set_model_user6)");
+    if (n_ev_new > u->geom.n_ev)
+        return smc_fail(c, ("smc_user_set_design_events: n_ev_new = " + std::to_string(n_ev_new) + " above the event capacity " +
+                            std::to_string(u->geom.n_ev) + " the model was compiled for (its n_ev)").c_str());
+    std::vector<int> events;      // the rule about t[e][0] waits for the design's times (resolve_design)
+    const std::string bad = event_layout_error(nullptr, ev_t_new, ev_v_new, n_ex_new, 0, n_ev_new, u->geom.n_val, events);
+    if (!bad.empty()) return smc_fail(c, ("smc_user_set_design_events: " + bad + " (of the design)").c_str());
+    u->design_ev_t.assign(ev_t_new, ev_t_new + (size_t)n_ex_new * n_ev_new);
+    u->design_ev_v.clear();
+    if (ev_v_new) u->design_ev_v.assign(ev_v_new, ev_v_new + (size_t)n_ex_new * n_ev_new * u->geom.n_val);
+    u->design_ev_n_ex = n_ex_new;
+    u->design_ev_n_ev = n_ev_new;
+    return 0;
 }
 
 int smc_user_set_design_inputs(smc_ctx *c, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new) {
@@ -1195,14 +1368,15 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
 }
 // the design of a call: (t_new, cond_new) checked by the rules of smc_set_model_user3, or the data's own
 // A model with inputs: cond becomes whole rows (cond_stride words, the table behind the numbers) - the data's own, or in `rows`
-// those of cond_new and the design inputs of smc_user_set_design_inputs, which an explicit design must have.
+// those of cond_new and the design inputs of smc_user_set_design_inputs, which an explicit design must have.  A model with
+// events: the same with the design events of smc_user_set_design_events.
 static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const double *&t, const double *&cond, int &n_ex, int &n_t,
                           std::vector<double> &rows) {
     const std::string w = std::string(who) + ": ";
     if (!t) {
         if (!u->d_img) return smc_fail(c, u->img_error.c_str());
         t = u->h_t.data();
-        cond = u->geom.n_in > 0 ? u->h_rows.data() : u->h_cond.data();
+        cond = u->geom.tabled() ? u->h_rows.data() : u->h_cond.data();
         n_ex = u->n_ex;
         n_t = u->n_t;
         return 0;
@@ -1224,6 +1398,19 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
             return smc_fail(c, (w + "the design inputs are no longer valid").c_str());
         // a row whose finite knots fit the capacity may still be stored wider (trailing NaN): only its knots are copied
         rows = build_input_rows(cond, u->geom, u->design_t.data(), u->design_u.data(), n_ex, u->design_n_knot, knots);
+        cond = rows.data();
+    }
+    if (u->geom.n_ev > 0) {      // the what-if regimen: the design's own events, behind what the rows hold so far
+        if (u->design_ev_n_ex != n_ex)
+            return smc_fail(c, (w + "the model has events and the design has no matching design events: " +
+                                (u->design_ev_n_ex ? "smc_user_set_design_events holds " + std::to_string(u->design_ev_n_ex) + " rows"
+                                                   : std::string("none are set")) +
+                                ", the design has " + std::to_string(n_ex) + " experiments (smc_user_set_design_events)").c_str());
+        std::vector<int> events;
+        const std::string bad_ev = event_layout_error(t, u->design_ev_t.data(), u->geom.n_val > 0 ? u->design_ev_v.data() : nullptr, n_ex, n_t,
+                                                      u->design_ev_n_ev, u->geom.n_val, events);
+        if (!bad_ev.empty()) return smc_fail(c, (w + bad_ev + " (of the design events)").c_str());
+        rows = build_event_rows(cond, u->geom, u->design_ev_t.data(), u->design_ev_v.data(), n_ex, u->design_ev_n_ev, events);
         cond = rows.data();
     }
     return 0;

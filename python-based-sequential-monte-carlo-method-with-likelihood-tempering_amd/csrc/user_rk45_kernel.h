@@ -66,11 +66,50 @@ struct Item {
 #endif
     int i_out, status;   // status: 0 running, 1 finished, -1 step size underflow (the reference's solver raises)
     bool rejected;
+#ifdef SMC_USER_EVENTS
+    double t_end;   // scheduled events (user_item_ops.h: item_cache_times): the row's end; t_bound is the SEGMENT's bound
+    int i_ev;       // the next event of the row: the first with tau > t
+#endif  // SMC_USER_EVENTS
 };
+#ifdef SMC_USER_EVENTS
+// The start of a segment at (it.t, it.y) that runs to it.t_bound - what a new solve_ivp call does first: the derivative
+// there, common.py select_initial_step (direction +1, order 4, max_step inf) over the SEGMENT's length, and no rejected step to
+// remember.  item_begin's own arithmetic for the first segment, statement by statement; the right-hand-side evaluations are not
+// step attempts.
+__device__ __forceinline__ void segment_start(Item &it, const double *theta, const double *cond, double rtol, double atol) {
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const double t0 = it.t;
+    double tmp[NS];
+    it.rejected = false;
+    Ieee::rhs(t0, it.y, theta, cond, it.f);
+    const double interval_length = fabs(it.t_bound - t0);
+    double scale[NS], y1[NS], f1[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) { scale[i] = atol + fabs(it.y[i]) * rtol; tmp[i] = it.y[i] / scale[i]; }
+    const double d0 = rms(tmp);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) tmp[i] = it.f[i] / scale[i];
+    const double d1 = rms(tmp);
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = py_min(h0, interval_length);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) y1[i] = it.y[i] + h0 * 1.0 * it.f[i];
+    Ieee::rhs(t0 + h0 * 1.0, y1, theta, cond, f1);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) tmp[i] = (f1[i] - it.f[i]) / scale[i];
+    const double d2 = rms(tmp) / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? py_max(1e-6, h0 * 1e-3) : 1.0 / smc::pow_minus_fifth<false>(0.01 / py_max(d1, d2));
+    it.h_abs = py_min(py_min(py_min(100 * h0, h1), interval_length), inf);
+}
+#endif  // SMC_USER_EVENTS
 
 __device__ void item_begin(Item &it, const double *theta, const double *cond, const DataRec *tp, int n_t,
                            double rtol, double atol) {
+#ifdef SMC_USER_EVENTS
+    const double t0 = tp[0].x, t_bound = smc_ev::segment_bound(cond, 0, t_bound_of(tp, n_t));   // the first step is sized by the segment
+#else  // SMC_USER_EVENTS
     const double t0 = tp[0].x, t_bound = t_bound_of(tp, n_t);
+#endif  // SMC_USER_EVENTS
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     double tmp[NS];
     it.t = t0;
@@ -108,7 +147,11 @@ __device__ void item_begin(Item &it, const double *theta, const double *cond, co
         while (tp[it.i_out].x <= it.t) { emit(it, it.y, theta, cond, tp[it.i_out].x, tp[it.i_out].y); ++it.i_out; }   // stops at the sentinel
         it.status = 1;
     }
+#ifdef SMC_USER_EVENTS
+    item_cache_times(it, cond, tp, n_t);
+#else  // SMC_USER_EVENTS
     item_cache_times(it, tp, n_t);
+#endif  // SMC_USER_EVENTS
 }
 
 // rk_step (rk.py:64-71) and the error norm (rk.py:106-110,146-147) of one attempt: a pure function of the item's state.
@@ -179,7 +222,12 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
     double pw = 0.9 * smc::pow_minus_fifth<false>(st.error_norm);
     bool accept = st.error_norm < 1.0;                   // false for a NaN norm: Python's max(0.2, nan) is 0.2
     const bool redo = SMC_USER_USES_DIV && !__builtin_isfinite(st.error_norm);
+#ifdef SMC_USER_EVENTS
+    // ... and an accepted step that ends a segment in front of an event (t_bound < t_end: the row goes on behind it)
+    if (fail || redo || (accept && (it.t_next <= t_new || (t_new - t_bound >= 0 && t_bound < it.t_end)))) {
+#else  // SMC_USER_EVENTS
     if (fail || redo || (accept && it.t_next <= t_new)) {
+#endif  // SMC_USER_EVENTS
         if (fail) {
             it.status = -1;
             return;
@@ -225,6 +273,27 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
             it.i_out = i_out;
             it.t_next = nx.x;
         }
+#ifdef SMC_USER_EVENTS
+        // The segment ends at event i_ev (t_new == t_bound == tau < t_end).  The outputs up to and including tau are out, from the
+        // state BEFORE the event; now the event changes the end state and the next segment starts afresh from (tau, y), as a new
+        // solve_ivp call would: segment_start.  The item goes on (status 0) and this return keeps the bookkeeping below from
+        // overwriting the restarted h_abs, f and rejected.
+        // Termination: every event application advances i_ev, and i_ev <= SMC_USER_NEV because an event fires only with a finite
+        // tau < t_end and the table ends in +inf, so an item has at most SMC_USER_NEV + 1 segments.  Event times increase strictly
+        // and lie above t0, so every segment has positive length, and inside it the item is the solve it always was: t reaches
+        // t_bound, or the step-size failure above stops it (Ops::attempt bounds the attempts besides).  No loop is added.
+        if (accept && t_new - t_bound >= 0 && t_bound < it.t_end) {
+            it.t = t_new;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) it.y[i] = st.y_new[i];
+            smc_user_ieee::smc_user_event(it.i_ev, t_new, it.y, theta, cond);
+            ++it.i_ev;
+            it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+            segment_start(it, theta, cond, rtol, atol);
+            it.status = 0;
+            return;
+        }
+#endif  // SMC_USER_EVENTS
     }
     double fac_acc = py_min(10.0, pw);
     fac_acc = it.rejected ? py_min(1.0, fac_acc) : fac_acc;

@@ -332,7 +332,8 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     is bit-identical to the uninterrupted run (tests/test_gpu_parity.py).
 
     predictive: keyword arguments of HipEngine.predictive_summary (user models only; `which` defaults to the final posterior,
-    SMC_SET_PRED): the summary is formed on the device before returning and stored as out["predictive"].
+    SMC_SET_PRED): the summary is formed on the device before returning and stored as out["predictive"].  A design's "inputs"
+    and "events" (a feed profile or a dosing regimen that was never run) go through with the rest.
 
     Returns a dict: final particles (this rank's block), lk, schedule records, logZ, counters.
     """

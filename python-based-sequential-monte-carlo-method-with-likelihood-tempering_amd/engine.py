@@ -126,6 +126,8 @@ class HipEngine:
         self.user_n_obs = 1     # outputs per data time of a user model (set_model_user)
         self.user_n_cond = 0    # ... and its numbers per experiment
         self.user_n_in = 0      # ... and its time-varying inputs (set_model_user(inputs=))
+        self.user_n_ev = 0      # ... its event capacity and the values per event (set_model_user(events=))
+        self.user_n_val = 0
         if "smc_ess_search_global" in B.MISSING:   # A/B build of an older revision (SMC_HIP_LIB): the driver falls back
             self.ess_search_global = None
         self._peer_barrier = None
@@ -172,7 +174,7 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None):
+                       atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None, events=None):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
@@ -189,12 +191,17 @@ class HipEngine:
         row may end in NaN) and the values of n_in inputs at them (2-D for one input); the source reads them as
         smc_input(cond, k, t), linear between knots (user_models.input_value is the definition, input_layout the rules: ValueError
         for inputs that break them).  With obs, obs_scale, noise / est_sigma as above.  inputs=None goes through the calls above
-        exactly as before."""
+        exactly as before.
+        Scheduled events (smc_set_model_user6): events={"t": (n_ex, n_ev), "values": (n_ex, n_ev, n_val) or None} - event times (a
+        row may end in NaN, or hold none) and the numbers of every event; the source defines smc_user_event(j, t, y, theta, cond),
+        which changes y in place at event j and reads its numbers as smc_event_value(cond, j, k).  The solve is the chain of
+        solve_ivp calls between the events (include/smc_hip.h); user_models.event_layout states the rules (ValueError for events
+        that break them).  events=None goes through the calls above exactly as before."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
         obs = np.asarray(obs)
-        multi = obs.ndim == 3 or obs_scale is not None or noise is not None or inputs is not None
+        multi = obs.ndim == 3 or obs_scale is not None or noise is not None or inputs is not None or events is not None
         if multi:
             # several outputs, NaN = not measured, ragged rows (smc_set_model_user3); the same checks as the library's
             obs = _f64(obs if obs.ndim == 3 else obs.reshape(obs.shape + (1,)))
@@ -216,9 +223,20 @@ class HipEngine:
             ai, af = np.ascontiguousarray(ai, dtype=np.int32), np.ascontiguousarray(af)
             pi = None if pi is None else np.ascontiguousarray(pi, dtype=np.int32)
             pf = None if pf is None else np.ascontiguousarray(pf)
-        n_in = 0
+        n_in = n_ev = n_val = 0
+        in_t = in_u = None
         if inputs is not None:
             in_t, in_u, n_in = self._inputs("set_model_user", inputs, t.shape[0])
+        if events is not None:
+            ev_t, ev_v, n_val = self._events("set_model_user", events, t)
+            n_ev = ev_t.shape[1]
+            self._ck(self.L.smc_set_model_user6(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
+                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
+                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
+                                                int(bool(est_sigma)), float(sigma_fixed), fp(in_t), fp(in_u), n_in,
+                                                0 if in_t is None else in_t.shape[1], _dp(ev_t), fp(ev_v), n_ev, n_val),
+                     "smc_set_model_user6")
+        elif inputs is not None:
             self._ck(self.L.smc_set_model_user5(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
                                                 None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
                                                 ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
@@ -242,6 +260,23 @@ class HipEngine:
         self.user_n_obs = n_obs
         self.user_n_cond = cond.shape[1]
         self.user_n_in = n_in
+        self.user_n_ev, self.user_n_val = n_ev, n_val
+
+    @staticmethod
+    def _events(what, events, t):
+        """events = {"t", "values"} checked by user_models.event_layout against the times t: contiguous ev_t (n_ex, n_ev), ev_v
+        (n_ex, n_ev, n_val) or None for n_val = 0, n_val."""
+        if not isinstance(events, dict) or set(events) != {"t", "values"}:
+            raise ValueError(f'{what}: events must be {{"t": (n_ex, n_ev), "values": (n_ex, n_ev, n_val) or None}}')
+        from .user_models import event_layout
+        ev_t = _f64(events["t"])
+        ev_v = None if events["values"] is None else _f64(events["values"])
+        if ev_v is not None and ev_v.ndim == 2 and ev_t.ndim == 2:
+            ev_v = np.ascontiguousarray(ev_v.reshape(ev_v.shape + (1,)))
+        event_layout(t, ev_t, ev_v)
+        if ev_v is not None and ev_v.shape[2] == 0:
+            ev_v = None
+        return ev_t, ev_v, 0 if ev_v is None else ev_v.shape[2]
 
     @staticmethod
     def _inputs(what, inputs, n_ex):
@@ -498,13 +533,14 @@ class HipEngine:
                  "smc_user_predict")
         return lk, pred, {"n_failed": nf.value, "rk_attempts": att.value}
 
-    def _design(self, what, t, cond, inputs=None):
+    def _design(self, what, t, cond, inputs=None, events=None):
         """(t, cond) of a prediction design as contiguous arrays and their C arguments; (None, None): the data's own design.
         inputs: the design's inputs ({"t", "u"} as set_model_user's), handed to the library (smc_user_set_design_inputs) before
-        the call; None with an explicit design clears them, and a model with inputs then refuses the design with the reason."""
+        the call; None with an explicit design clears them, and a model with inputs then refuses the design with the reason.
+        events: the design's events ({"t", "values"} as set_model_user's; smc_user_set_design_events), in the same way."""
         if t is None:
-            if cond is not None or inputs is not None:
-                raise ValueError(f"{what}: cond or inputs without t (a design is all of them, or none for the data's own)")
+            if cond is not None or inputs is not None or events is not None:
+                raise ValueError(f"{what}: cond, inputs or events without t (a design is all of them, or none for the data's own)")
             return None, None, (None, None, 0, 0), (self.model[1], self.model[2])
         from .user_models import design_layout
         t = _f64(t)
@@ -519,24 +555,38 @@ class HipEngine:
                      "smc_user_set_design_inputs")
         elif self.user_n_in:
             self._ck(self.L.smc_user_set_design_inputs(self.ctx, None, None, 0, 0), "smc_user_set_design_inputs")
+        if events is not None:
+            if self.user_n_ev == 0:
+                raise ValueError(f"{what}: events for a model that has none")
+            ev_t, ev_v, n_val = self._events(what, events, t)
+            if n_val != self.user_n_val:
+                raise ValueError(f"{what}: the model's events hold {self.user_n_val} values, the design's hold {n_val}")
+            if ev_t.shape[1] > self.user_n_ev:
+                raise ValueError(f"{what}: the model was compiled for {self.user_n_ev} events per row, the design's rows hold {ev_t.shape[1]}")
+            self._ck(self.L.smc_user_set_design_events(self.ctx, _dp(ev_t), None if ev_v is None else _dp(ev_v), t.shape[0], ev_t.shape[1]),
+                     "smc_user_set_design_events")
+        elif self.user_n_ev:
+            self._ck(self.L.smc_user_set_design_events(self.ctx, None, None, 0, 0), "smc_user_set_design_events")
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond, dtype=np.float64).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
         return t, cbuf, (_dp(t), _dp(cbuf), t.shape[0], t.shape[1]), t.shape
 
-    def predict_user_at(self, particles, t=None, cond=None, inputs=None):
+    def predict_user_at(self, particles, t=None, cond=None, inputs=None, events=None):
         """A user model's predictions for host particles (n, dim) on a design of its own (include/smc_hip.h: smc_user_predict_at):
         t (n_ex_new, n_t_new) rows of output times (the first is the initial time; a row may end in NaN), cond
         (n_ex_new, n_cond) - other times, a longer horizon, an experiment that was never run.  Without a design: the data's,
         with predict_user's bits.  Returns pred (n, n_ex_new, n_t_new, n_obs), NaN past a row's end and from where a solve
         failed, and {"n_failed", "rk_attempts"}.  ValueError for a design that breaks the rules (user_models.design_layout).
         A model with inputs (set_model_user(inputs=)): an explicit design brings its own, inputs={"t": (n_ex_new, n_knot_new),
-        "u": (n_ex_new, n_knot_new, n_in)} - "what if I feed like this instead"; without them it is refused (SmcError)."""
+        "u": (n_ex_new, n_knot_new, n_in)} - "what if I feed like this instead"; without them it is refused (SmcError).
+        A model with events (set_model_user(events=)): likewise events={"t": (n_ex_new, n_ev_new), "values": ...} with n_ev_new
+        up to the model's n_ev - the dosing regimen that was never run; nothing is compiled again."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("predict_user_at: no user model has been set")
         particles = _f64(particles)
         if particles.ndim != 2 or particles.shape[1] != self.dim:
             raise ValueError(f"predict_user_at: particles must be (n, {self.dim}), got {particles.shape}")
-        t, cbuf, cargs, shape = self._design("predict_user_at", t, cond, inputs)
+        t, cbuf, cargs, shape = self._design("predict_user_at", t, cond, inputs, events)
         n = particles.shape[0]
         pred = np.empty((n, shape[0], shape[1], self.user_n_obs))
         nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -545,7 +595,7 @@ class HipEngine:
         return pred, {"n_failed": nf.value, "rk_attempts": att.value}
 
     def predictive_summary(self, which=SMC_SET_FILT, probs=(0.025, 0.5, 0.975), t=None, cond=None, noise=False, seed=0,
-                           global_offset=0, max_staging_bytes=0, inputs=None):
+                           global_offset=0, max_staging_bytes=0, inputs=None, events=None):
         """Posterior predictive summaries of a resident particle set, formed on the device (include/smc_hip.h:
         smc_user_predict_summary): per cell (experiment, time, output) of the design (t, cond; None: the data's) over the set's
         equally weighted particles.  Returns {"mean", "sd", "n_finite": (n_ex, n_t, n_obs); "lower", "upper", "quantile":
@@ -553,13 +603,13 @@ class HipEngine:
         value between them (user_models.quantile_ranks, linear_quantile); "n_failed", "rk_attempts"; "kernel_ms":
         {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
         global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
-        With several ranks the summary describes this rank's block only.  inputs: as predict_user_at's."""
+        With several ranks the summary describes this rank's block only.  inputs, events: as predict_user_at's."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("predictive_summary: no user model has been set")
         q = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))
         if not 1 <= q.size <= B.SMC_PRED_MAX_PROBS or not np.all((q >= 0) & (q <= 1)):
             raise ValueError(f"predictive_summary: 1 .. {B.SMC_PRED_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
-        t, cbuf, cargs, shape = self._design("predictive_summary", t, cond, inputs)
+        t, cbuf, cargs, shape = self._design("predictive_summary", t, cond, inputs, events)
         cells = (shape[0], shape[1], self.user_n_obs)
         mean, sd = np.empty(cells), np.empty(cells)
         lower, upper = np.empty((q.size,) + cells), np.empty((q.size,) + cells)

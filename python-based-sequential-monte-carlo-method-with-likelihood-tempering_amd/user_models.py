@@ -71,6 +71,35 @@ ROBERTSON_AC = ROBERTSON.replace(
     "__device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out) {\n"
     "    out[0] = y[0];\n    out[1] = y[2];\n}\n")
 
+# Scheduled events (include/smc_hip.h: smc_set_model_user6).  A one-compartment model under repeated bolus doses:
+# theta = (k, sigma), cond = (y0,), dC/dt = -k C and event j adds its value 0 (the dose over the volume) to C
+ONE_COMPARTMENT_DOSED = r"""
+__device__ void smc_user_y0(const double *theta, const double *cond, double *y) { y[0] = cond[0]; }
+__device__ void smc_user_rhs(double t, const double *y, const double *theta, const double *cond, double *dydt) { dydt[0] = -theta[0] * y[0]; }
+__device__ double smc_user_obs(double t, const double *y, const double *theta, const double *cond) { return y[0]; }
+__device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond) { y[0] += smc_event_value(cond, j, 0); }
+"""
+# Oral dosing, gut -> central -> out: theta = (ka, ke, F, sigma), cond = (gut0,), both compartments observed.  An event holds
+# (amount, kind): kind 0 is a dose into the gut of which the fraction F = theta[2] arrives (the jump depends on theta), kind 1
+# empties the central compartment (a washout)
+ORAL_DOSING = r"""
+__device__ void smc_user_y0(const double *theta, const double *cond, double *y) { y[0] = cond[0]; y[1] = 0.0; }
+__device__ void smc_user_rhs(double t, const double *y, const double *theta, const double *cond, double *dydt) {
+    dydt[0] = -theta[0] * y[0];
+    dydt[1] = theta[0] * y[0] - theta[1] * y[1];
+}
+__device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out) {
+    out[0] = y[0];
+    out[1] = y[1];
+}
+__device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond) {
+    if (smc_event_value(cond, j, 1) == 0.0)
+        y[0] += theta[2] * smc_event_value(cond, j, 0);
+    else
+        y[1] = 0.0;
+}
+"""
+
 
 def obs_layout(t, obs, obs_scale=None):
     """The data rules of smc_set_model_user3 (include/smc_hip.h), in NumPy: t (n_ex, n_t); obs (n_ex, n_t, n_obs) with NaN for a
@@ -222,6 +251,56 @@ def input_layout(in_t, in_u, n_ex):
                     raise ValueError(f"input_layout: row {e} of in_u is not finite at knot {i} of input {j}")
                 if steep[i, j]:
                     raise ValueError(f"input_layout: row {e} of in_u has a slope that overflows at knot {i} of input {j}")
+        m[e] = k
+    return m
+
+
+def event_layout(t, ev_t, ev_v=None):
+    """The data rules of a model's scheduled events (include/smc_hip.h: smc_set_model_user6), in NumPy: t (n_ex, n_t) the data
+    times; ev_t (n_ex, n_ev) event times, every row a strictly increasing finite run - it may be empty - possibly followed by NaN
+    only, every finite event time later than the row's first time t[e][0]; ev_v (n_ex, n_ev, n_val) the n_val = 0 .. 8 numbers of
+    every event (None for n_val = 0), finite at a row's finite events and ignored past them; n_ev = 1 .. 256.  Which events fire
+    is the solve's matter: those with t[e][0] < tau < the row's last finite time.  Returns the events per row, (n_ex,) int; raises
+    ValueError, in the library's words (smc_user_event_check), for events the library refuses."""
+    import numpy as np
+    t = np.asarray(t, dtype=np.float64)
+    et = np.asarray(ev_t, dtype=np.float64)
+    if t.ndim != 2 or et.ndim != 2 or et.shape[0] != t.shape[0]:
+        raise ValueError(f"event_layout: t must be (n_ex, n_t) and ev_t (n_ex, n_ev), got {t.shape} and {et.shape}")
+    n_ex, n_ev = et.shape
+    ev = np.zeros((n_ex, n_ev, 0)) if ev_v is None else np.asarray(ev_v, dtype=np.float64)
+    if ev.ndim != 3 or ev.shape[:2] != et.shape:
+        raise ValueError(f"event_layout: ev_v must be ({n_ex}, {n_ev}, n_val) or None, got {ev.shape}")
+    n_val = ev.shape[2]
+    if n_ev < 1:
+        raise ValueError(f"event_layout: n_ev = {n_ev}: a model with events needs room for at least one")
+    if n_ev > 256:
+        raise ValueError(f"event_layout: n_ev = {n_ev} above the event capacity 256 (SMC_USER_MAX_EVENTS)")
+    if n_val > 8:
+        raise ValueError(f"event_layout: n_val = {n_val} outside 0 .. 8 (SMC_USER_MAX_EVENT_VALUES)")
+    if n_ex < 1:
+        raise ValueError(f"event_layout: n_ex = {n_ex}: no experiment")
+    if t.shape[1] < 1:
+        raise ValueError(f"event_layout: n_t = {t.shape[1]}: no time")
+    m = np.zeros(n_ex, dtype=np.int64)
+    for e in range(n_ex):
+        nan = np.isnan(et[e])
+        k = int(nan.argmax()) if nan.any() else n_ev
+        late = np.flatnonzero(~nan[k:])
+        if late.size:
+            raise ValueError(f"event_layout: row {e} of ev_t has a NaN event time before a number at event {k + late[0]} "
+                             "(only a trailing run of NaN may shorten a row)")
+        for i in range(k):
+            if not np.isfinite(et[e, i]):
+                raise ValueError(f"event_layout: row {e} of ev_t holds an infinite event time at event {i}")
+            if i > 0 and not et[e, i] > et[e, i - 1]:
+                raise ValueError(f"event_layout: row {e} of ev_t is not strictly increasing at event {i}")
+            if not et[e, i] > t[e, 0]:
+                raise ValueError(f"event_layout: row {e} of ev_t is not later than the row's first time t[e][0] at event {i}")
+        for i in range(k):
+            for j in range(n_val):
+                if not np.isfinite(ev[e, i, j]):
+                    raise ValueError(f"event_layout: row {e} of ev_v is not finite at event {i}, value {j}")
         m[e] = k
     return m
 
