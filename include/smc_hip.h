@@ -39,7 +39,9 @@ extern "C" {
                               * 3: smc_work_totals; smc_mh_sweeps_device_rng takes the methanation model too and returns the sweep counters;
                               *    smc_meth_dae_host's stats have five words (round 5)
                               * (still 3: smc_set_share_replicates / smc_mm_share_info and smc_set_start_reject / smc_mm_start_reject_info /
-                              *    smc_mm_reject_threshold only ADD entry points; the binding tolerates their absence in an older A/B build) */
+                              *    smc_mm_reject_threshold only ADD entry points; the binding tolerates their absence in an older A/B build;
+                              *    likewise the user-model functions ...4 to ...7: noise models, inputs, events and, with
+                              *    smc_set_model_user7 / smc_user_censor_check / check7 / dump_source7, censored observations) */
 #define SMC_MAX_DIM 8        /* parameters per particle (3 for Michaelis-Menten, 5 for methanation) */
 #define SMC_MAX_ESS_CAND 16  /* tempering candidates evaluated by one smc_ess_partials call */
 #define SMC_MAX_RANKS 64
@@ -269,6 +271,40 @@ int smc_user_model_check6(const char *source, int n_states, int dim, int method,
 int smc_user_model_dump_source6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, int n_ev, int n_val, const char *dir);
 int smc_user_set_design_events(smc_ctx *ctx, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new);
+/* CENSORED OBSERVATIONS (additive; the functions above keep their behaviour): a value the assay could not quantify - below the
+ * limit of quantification in a washout tail, above the upper limit at a peak - is neither dropped (NaN) nor taken for a
+ * measurement of the limit, but contributes the probability of lying beyond it (Beal's M3).  censor: n_ex x n_t x n_obs flags
+ * beside obs, 0: obs is the measured value (the term of the functions above); -1: left-censored, the true value is <= obs, which
+ * holds the lower limit; +1: right-censored, the true value is >= obs, the upper limit.  With sd_ik as in smc_set_model_user4:
+ *   logL = sum over quantified (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ] + sum over censored log Phi(z_ik),
+ *   z_ik = (obs_ik - f_ik) / sd_ik  (left),   (f_ik - obs_ik) / sd_ik  (right);      any a_k <= 0 or b_k < 0: -inf.
+ * user_models.censored_loglik is the definition in NumPy.  The kernels add x = -log Phi(z) >= 0 as
+ *   z > 0:  -log1p(-erfc(z / sqrt 2) / 2),      z <= 0:  z^2 / 2 - log(erfcx(-z / sqrt 2) / 2)
+ * - accurate in both tails, never negative - to the sums of smc_set_model_user4; a censored value's floor is 0 and m_e, m_ek count
+ * quantified values only, so exact early rejection applies unchanged.
+ * Rules: every flag is -1, 0 or +1; a nonzero flag stands on a finite value at a finite time of its row.  Anything else fails
+ * with the row, the time, the output and the rule.  smc_user_censor_check applies these rules alone to t and obs that
+ * smc_set_model_user3 accepts (no GPU, no context; the reason in smc_last_error(NULL)); c_n_ex, c_n_t, c_n_obs: the shape of
+ * censor itself, which must be that of obs.
+ * smc_set_model_user7: the arguments of smc_set_model_user6, then censor.  NULL or all zeros is smc_set_model_user6, its path
+ * and its bits.  With a flag set the model is a noise model: add_index == NULL forms the equivalent specification - every
+ * output at parameter dim - 1 under est_sigma, else fixed at sigma_fixed, obs_scale as given.  Limits, times and events
+ * combine freely; a record of the LDS table holds the flags in its pad word (n_obs even) or grows by 16 bytes (n_obs odd), and a
+ * table that no longer fits fails with the bytes needed and available.  smc_user_predict returns lk under this likelihood;
+ * designs (smc_user_predict_at, smc_user_predict_summary) carry no observations and run as before.
+ * check7 / dump_source7: as the 6 functions plus censor != 0: the source compiled with SMC_USER_CENSOR (it needs noise = 1 or 2);
+ * dump_source7 then also writes user_censor.h.  With censor == 0 they are check6 / dump_source6. */
+int smc_set_model_user7(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
+                        const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
+                        const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
+                        int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot,
+                        const double *ev_t, const double *ev_v, int n_ev, int n_val, const signed char *censor);
+int smc_user_censor_check(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs, int c_n_ex,
+                          int c_n_t, int c_n_obs);
+int smc_user_model_check7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, int censor, char *log, int log_cap);
+int smc_user_model_dump_source7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, int n_ev, int n_val, int censor, const char *dir);
 /* Model PREDICTIONS of a user model (any of the three set functions; RK45 or BDF), for n host particles (n x dim, AoS; any n -
  * run in chunks of n_local): lk[n] as smc_loglik computes it and, unless pred is NULL, pred[((p * n_ex + e) * n_t + i) * n_obs + k]
  * = output k at t[e][i], written for every finite time whether or not obs is measured there; NaN past a row's end and from

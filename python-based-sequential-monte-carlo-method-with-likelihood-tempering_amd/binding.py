@@ -43,6 +43,7 @@ class SmcError(RuntimeError):
 c_dp = ctypes.POINTER(ctypes.c_double)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
+c_i8p = ctypes.POINTER(ctypes.c_int8)
 c_ip = ctypes.POINTER(ctypes.c_int)
 c_ctx = ctypes.c_void_p
 i64, f64, cint, u64 = ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_uint64
@@ -84,6 +85,13 @@ SIGNATURES = {
     "smc_user_model_check6": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source6": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p]),
     "smc_user_set_design_events": (cint, [c_ctx, c_dp, c_dp, cint, cint]),
+    "smc_set_model_user7": (cint, [c_ctx, ctypes.c_char_p, cint, cint, c_dp, c_dp, c_dp, c_dp, cint, cint, cint, c_ip, c_dp, c_ip, c_dp,
+                                    f64, f64, cint, cint, f64, c_dp, c_dp, cint, cint, c_dp, c_dp, cint, cint, c_i8p]),
+    "smc_user_censor_check": (cint, [c_dp, c_dp, c_i8p, cint, cint, cint, cint, cint, cint]),
+    "smc_user_model_check7": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p,
+                                      cint]),
+    "smc_user_model_dump_source7": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint,
+                                            ctypes.c_char_p]),
     "smc_user_predict": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_at": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, cint, cint, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_summary": (cint, [c_ctx, cint, c_dp, c_dp, cint, cint, c_dp, cint, cint, u64, i64, ctypes.c_size_t, c_dp, c_dp,

@@ -26,6 +26,7 @@
 #include "smc_internal.h"
 #include "solve_sched.h"   // kChunk: the grid is sized in chunks of the shared scheduler
 #include "stage_kernels.h" // launch_aos_to_soa (smc_user_predict)
+#include "user_censor.h"   // censored observations (smc_set_model_user7)
 #include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
 #include "predictive_kernels.h"   // smc_user_predict_summary's kernels
 
@@ -176,6 +177,7 @@ user_bdf_count_kernel(const uint8_t *__restrict__ p0mask, const unsigned *__rest
 struct UserInputGeom {
     int n_cond = 0, n_in = 0, kcap = 0;
     int n_ev = 0, n_val = 0;
+    int censor = 0;      // 1: censored observations (user_censor.h) - SMC_USER_CENSOR, records with a flag word; no part of a cond row
     int in_words() const { return n_in > 0 ? n_cond + kcap + n_in * (2 * kcap + 1) : n_cond; }      // = the offset of the event table
     int ev_words() const { return n_ev > 0 ? n_ev + 1 + n_ev * n_val : 0; }
     int row_words() const { return in_words() + ev_words(); }
@@ -278,6 +280,8 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
              ((n_obs > 1 || mentions(user_source, "smc_user_obs_vec")) ? "1\n" : "0\n");
     // smc_set_model_user4: the SMC_USER_NOISE blocks of the kernel files and of user_obs_args.h (noise = 2: with log1p and the division)
+    // smc_set_model_user7: SMC_USER_CENSOR, user_censor.h in front and user_obs_args.h with its SMC_USER_CENSOR blocks (a noise model always)
+    if (n_obs > 0 && noise > 0 && geom.censor) s += "#define SMC_USER_CENSOR 1\n#include \"user_censor.h\"\n";
     if (n_obs > 0 && noise > 0) s += std::string("#define SMC_USER_NOISE 1\n#define SMC_USER_NOISE_PROP ") + (noise > 1 ? "1\n" : "0\n");
     if (mentions(user_source, "smc_user_cost")) s += "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n";
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
@@ -296,17 +300,19 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
 static const struct { const char *name, *text; } kUserHeaders[] = {
     {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"reject_bound.h", k_reject_bound_h}, {"solve_sched.h", k_solve_sched_h},
     {"rk45_math.h", k_rk45_math_h}, {"user_item_ops.h", k_user_item_ops_h}, {"user_obs_args.h", k_user_obs_args_h},
-    {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}};
+    {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}, {"user_censor.h", k_user_censor_h}};
 constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
 // user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs, user_event.h with one that
-// has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks
+// has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks -, user_censor.h with one that has censored observations
+// - and user_obs_args.h then with its SMC_USER_CENSOR blocks
 static int user_headers(int n_obs, const UserInputGeom &geom, const char **texts, const char **names) {
     int n = 0;
     for (const auto &h : kUserHeaders) {
         if ((h.text == k_user_obs_args_h && n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
-            (h.text == k_user_event_h && geom.n_ev <= 0))
+            (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !geom.censor))
             continue;
-        texts[n] = (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev : h.text;
+        texts[n] = (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev
+                   : (h.text == k_user_obs_args_h && geom.censor) ? k_user_obs_args_h_cn : h.text;
         names[n++] = h.name;
     }
     return n;
@@ -372,9 +378,10 @@ static size_t user_lds_bytes(int n_states, int n_ex, int n_t) {
     return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)2 * n_ex * (n_t + 1)) * sizeof(double);
 }
 // ... of the multi-output kernels: the pools, then the image of user_obs_args.h
-// (noise: plus the noise block of a model of smc_set_model_user4)
-static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs, bool noise = false) {
-    return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)obs_table_at(n_ex) + (size_t)n_ex * (n_t + 1) * obs_rec_words(n_obs) +
+// (noise: plus the noise block of a model of smc_set_model_user4; censor: records with the flag word of user_censor.h)
+static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs, bool noise = false, bool censor = false) {
+    return ((size_t)4 * (2 * n_states + 6) * 64 + (size_t)obs_table_at(n_ex) +
+            (size_t)n_ex * (n_t + 1) * (censor ? obs_rec_words_censor(n_obs) : obs_rec_words(n_obs)) +
             (noise ? (size_t)obs_noise_words(n_ex) : 0)) * sizeof(double);
 }
 static const size_t kUserLdsCap = 150 * 1024;
@@ -412,7 +419,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const bool multi = u->multi || pred;
-    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
+    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->geom.censor != 0) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
     if (lists) {
         u->parity ^= 1;
         UserScanArgs sa{};
@@ -512,8 +519,10 @@ void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
 // strictly increasing run of n_t_e >= 1 finite times followed by NaN only; NaN in obs is a value not measured (what lies at a
 // NaN time is ignored), an infinite one is refused; obs_scale (nullptr: ones) is finite and > 0.  On success me / ls hold
 // m_e and the sum of log s_k over the observed values of each experiment; "" = valid, else what is wrong.
+// censor (flags censor_layout_error has accepted, or nullptr): m_e and the sum count QUANTIFIED values only - a censored value
+// has no density term and its floor is 0.
 static std::string obs_layout(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
-                              std::vector<double> &me, std::vector<double> &ls) {
+                              std::vector<double> &me, std::vector<double> &ls, const signed char *censor = nullptr) {
     for (int k = 0; k < n_obs; ++k)
         if (scale && !(std::isfinite(scale[k]) && scale[k] > 0.0)) return "obs_scale must be finite and > 0";
     me.assign(n_ex, 0.0);
@@ -535,6 +544,7 @@ static std::string obs_layout(const double *t, const double *obs, const double *
                 const double v = obs[((size_t)e * n_t + i) * n_obs + k];
                 if (std::isnan(v)) continue;
                 if (!std::isfinite(v)) return "obs holds an infinite value (NaN marks a value that was not measured)";
+                if (censor && censor[((size_t)e * n_t + i) * n_obs + k] != 0) continue;
                 me[e] += 1.0;
                 ls[e] += scale ? std::log(scale[k]) : 0.0;
             }
@@ -543,22 +553,27 @@ static std::string obs_layout(const double *t, const double *obs, const double *
 }
 
 // the LDS image of user_obs_args.h for data obs_layout has accepted
-// m_ek [8 e + k]: the finite observations of output k at the finite times of experiment e
-static std::vector<double> count_mek(const double *t, const double *obs, int n_ex, int n_t, int n_obs) {
+// m_ek [8 e + k]: the finite observations of output k at the finite times of experiment e (censor: the quantified ones)
+static std::vector<double> count_mek(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const signed char *censor = nullptr) {
     std::vector<double> mek(8 * (size_t)n_ex, 0.0);
     for (int e = 0; e < n_ex; ++e)
         for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
-            for (int k = 0; k < n_obs; ++k)
-                if (!std::isnan(obs[((size_t)e * n_t + i) * n_obs + k])) mek[8 * (size_t)e + k] += 1.0;
+            for (int k = 0; k < n_obs; ++k) {
+                const size_t at = ((size_t)e * n_t + i) * n_obs + k;
+                if (!std::isnan(obs[at]) && !(censor && censor[at] != 0)) mek[8 * (size_t)e + k] += 1.0;
+            }
     return mek;
 }
 
+// flagged: the image of a model compiled with SMC_USER_CENSOR - records of obs_rec_words_censor(n_obs) words, the last one the
+// flags of the record's outputs (user_censor.h); censor: the flags (nullptr: none set, a design's image)
 static std::vector<double> build_obs_image(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
-                                           const std::vector<double> &me, const std::vector<double> &ls, const UserNoise *nz = nullptr) {
-    const int R = obs_rec_words(n_obs), at = obs_table_at(n_ex);
+                                           const std::vector<double> &me, const std::vector<double> &ls, const UserNoise *nz = nullptr,
+                                           bool flagged = false, const signed char *censor = nullptr) {
+    const int R = flagged ? obs_rec_words_censor(n_obs) : obs_rec_words(n_obs), at = obs_table_at(n_ex);
     std::vector<double> img((size_t)at + (size_t)n_ex * (n_t + 1) * R + (nz ? (size_t)obs_noise_words(n_ex) : 0), 0.0);
     if (nz) {      // the noise block (user_obs_args.h)
-        double *b = img.data() + obs_noise_at(n_ex, n_t, n_obs);
+        double *b = img.data() + at + (size_t)n_ex * (n_t + 1) * R;
         for (int k = 0; k < kUserMaxObs; ++k) {
             b[k] = k < n_obs ? (double)nz->add_index[k] : -1.0;
             b[8 + k] = k < n_obs ? nz->add_fixed[k] : 1.0;
@@ -566,7 +581,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
             b[24 + k] = (k < n_obs && nz->prop) ? nz->prop_fixed[k] : 0.0;
             b[32 + k] = k < n_obs ? nz->scale[k] : 1.0;
         }
-        const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs);
+        const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor);
         std::copy(mek.begin(), mek.end(), b + kNoiseHdr);
     }
     for (int k = 0; k < kObsHdrMe; ++k) img[k] = (scale && k < n_obs) ? 1.0 / scale[k] : 1.0;
@@ -582,6 +597,14 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
             if (i < len) {
                 r[0] = te[i];
                 for (int k = 0; k < n_obs; ++k) r[1 + k] = obs[((size_t)e * n_t + i) * n_obs + k];
+                if (flagged && censor) {
+                    int bits = 0;
+                    for (int k = 0; k < n_obs; ++k) {
+                        const signed char f = censor[((size_t)e * n_t + i) * n_obs + k];
+                        bits |= (f < 0 ? kCensorLeft : f > 0 ? kCensorRight : kCensorNone) << (2 * k);
+                    }
+                    r[R - 1] = (double)bits;
+                }
             } else {
                 r[0] = HUGE_VAL;          // the sentinel: no output time is ever >= it
                 r[1] = te[len - 1];       // t_bound
@@ -593,7 +616,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
 
 // occupancy and LDS limit of the prediction kernel (u->fn_pred)
 static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
-    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise);
+    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->geom.censor != 0);
     int nb = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu_pred = nb;
     if (lds > 48 * 1024 &&
@@ -647,7 +670,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
     std::vector<double> me, ls;
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
     const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls,
-                                                    u->noise ? &u->nz : nullptr);
+                                                    u->noise ? &u->nz : nullptr, u->geom.censor != 0);      // no flag set
     const int cs = u->cond_stride();      // a model with inputs or events: cond holds whole rows, the tables included
     const size_t nc = (size_t)g * (cs > 0 ? cs : 1) * sizeof(double);
     dg.e0 = e0;
@@ -660,7 +683,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
               hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && cs > 0)
         ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * cs, nc, hipMemcpyHostToDevice) == hipSuccess;
-    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs, u->noise);
+    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs, u->noise, u->geom.censor != 0);
     int nb = 0;
     if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
     (void)c;
@@ -692,7 +715,7 @@ struct DesignScope {
 // the largest run of experiments whose image fits the LDS cap (0: not even one row)
 static int design_lds_group(const UserModel *u, int n_ex, int n_t) {
     int g = 0;
-    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs, u->noise) <= kUserLdsCap) ++g;
+    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs, u->noise, u->geom.censor != 0) <= kUserLdsCap) ++g;
     return g;
 }
 
@@ -795,6 +818,20 @@ int smc_user_model_check6(const char *source, int n_states, int dim, int method,
     if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
     return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
 }
+// ... and of check7 / dump_source7: censor = 0 is a model without censored observations, whose geometry is check6's; with it
+// the source is a noise model's (noise = 1 or 2)
+static bool user_geom_of7(int noise, int n_cond, int n_in, int n_knot, int n_ev, int n_val, int censor, UserInputGeom &geom) {
+    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return false;
+    if (censor != 0 && noise == 0) return false;
+    geom.censor = censor != 0 ? 1 : 0;
+    return true;
+}
+int smc_user_model_check7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, int censor, char *log, int log_cap) {
+    UserInputGeom geom;
+    if (!user_geom_of7(noise, n_cond, n_in, n_knot, n_ev, n_val, censor, geom)) return 2;
+    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
+}
 
 // everything hiprtc would read, as files: `hipcc -I <dir>` compiles <dir>/smc_user_model.hip off line
 static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0,
@@ -835,6 +872,44 @@ int smc_user_model_dump_source6(const char *source, int n_states, int dim, int m
     UserInputGeom geom;
     if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
     return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+}
+int smc_user_model_dump_source7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
+                                int n_knot, int n_ev, int n_val, int censor, const char *dir) {
+    UserInputGeom geom;
+    if (!user_geom_of7(noise, n_cond, n_in, n_knot, n_ev, n_val, censor, geom)) return 2;
+    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+}
+
+// the rules of the flags of censored observations (include/smc_hip.h: smc_set_model_user7; user_models.censor_layout is the same
+// in NumPy), for t and obs that obs_layout accepts: censor has obs's shape (c_*: its own), every flag is -1, 0 or +1, and a
+// nonzero flag stands on a finite value at a finite time of its row.  The first offence in row-major order; "" = valid.
+static std::string censor_layout_error(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs,
+                                       int c_n_ex, int c_n_t, int c_n_obs) {
+    if (!t || !obs || !censor) return "NULL t, obs or censor";
+    if (n_ex < 1 || n_t < 1 || !user_obs_ok(n_obs)) return "bad data shape";
+    if (c_n_ex != n_ex || c_n_t != n_t || c_n_obs != n_obs)
+        return "censor must have the shape of obs (" + std::to_string(n_ex) + ", " + std::to_string(n_t) + ", " + std::to_string(n_obs) +
+               "), got (" + std::to_string(c_n_ex) + ", " + std::to_string(c_n_t) + ", " + std::to_string(c_n_obs) + ")";
+    for (int e = 0; e < n_ex; ++e) {
+        int len = 0;
+        while (len < n_t && !std::isnan(t[(size_t)e * n_t + len])) ++len;
+        for (int i = 0; i < n_t; ++i)
+            for (int k = 0; k < n_obs; ++k) {
+                const int f = censor[((size_t)e * n_t + i) * n_obs + k];
+                if (f == 0) continue;
+                const std::string where = "row " + std::to_string(e) + ", time " + std::to_string(i) + ", output " + std::to_string(k);
+                if (f != -1 && f != 1)
+                    return "censor holds the flag " + std::to_string(f) + " at " + where + " (0: measured, -1: at or below obs, +1: at or above obs)";
+                if (i >= len) return "censor flags a value past the end of its row at " + where;
+                if (std::isnan(obs[((size_t)e * n_t + i) * n_obs + k])) return "censor flags a value that was not measured (obs is NaN) at " + where;
+            }
+    }
+    return "";
+}
+int smc_user_censor_check(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs, int c_n_ex,
+                          int c_n_t, int c_n_obs) {
+    const std::string bad = censor_layout_error(t, obs, censor, n_ex, n_t, n_obs, c_n_ex, c_n_t, c_n_obs);
+    return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_censor_check: " + bad).c_str());
 }
 
 // the data rules of a model's inputs (include/smc_hip.h: smc_set_model_user5; user_models.input_layout is the same in NumPy):
@@ -988,25 +1063,33 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
 static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
                                double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr,
-                               const UserInputs *in = nullptr, const UserEvents *ev = nullptr) {
+                               const UserInputs *in = nullptr, const UserEvents *ev = nullptr, const signed char *censor = nullptr) {
+    // censor: flags with at least one set (smc_set_model_user7 has checked them against t and obs); only with a noise model
     if (!c) return smc_fail(nullptr, "NULL context");
     if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
+    if (censor && !(nz && multi)) return smc_fail(c, "smc_set_model_user7: censored observations need a noise model");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
     if (n_states < 1 || n_states > SMC_USER_MAX_STATES) return smc_fail(c, "smc_set_model_user: n_states out of range");
     if (multi && !user_obs_ok(n_obs)) return smc_fail(c, "smc_set_model_user3: n_obs out of range (1 .. SMC_USER_MAX_OBS)");
     if (n_ex < 1 || n_t < 1 || n_cond < 0) return smc_fail(c, "smc_set_model_user: bad data shape");
     std::vector<double> me, ls;
-    std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls) : std::string("NULL t or obs");
+    std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, censor) : std::string("NULL t or obs");
     if (multi && !bad.empty()) return smc_fail(c, ("smc_set_model_user3: " + bad).c_str());
     if (multi && !nz && user_lds_bytes3(n_states, n_ex, n_t, n_obs) > kUserLdsCap)
         return smc_fail(c, "smc_set_model_user3: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) "
                            "(n_obs + 2 rounded down to even)) x 8 B + pools > 150 KB)");
+    if (nz && censor && user_lds_bytes3(n_states, n_ex, n_t, n_obs, true, true) > kUserLdsCap)
+        return smc_fail(c, ("smc_set_model_user7: data set too large for the kernel's LDS table with the flags of censored observations "
+                            "((8 + 2 n_ex + n_ex (n_t + 1) (n_obs + 3 rounded down to even) + 40 + 8 n_ex) x 8 B + pools): " +
+                            std::to_string(user_lds_bytes3(n_states, n_ex, n_t, n_obs, true, true)) + " B needed, " + std::to_string(kUserLdsCap) +
+                            " B available").c_str());
     if (nz && user_lds_bytes3(n_states, n_ex, n_t, n_obs, true) > kUserLdsCap)
         return smc_fail(c, ("smc_set_model_user4: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) (n_obs + 2 "
                             "rounded down to even) + 40 + 8 n_ex) x 8 B + pools): " +
                             std::to_string(user_lds_bytes3(n_states, n_ex, n_t, n_obs, true)) + " B needed, " + std::to_string(kUserLdsCap) +
                             " B available").c_str());
     UserInputGeom geom;
+    geom.censor = censor ? 1 : 0;
     std::vector<double> rows;      // the cond rows of a model with inputs, the table behind each
     if (in) {
         std::vector<int> knots;
@@ -1066,7 +1149,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
             k[n_ex + e] = multi ? ls[e] : 0.0;
         }
         if (nz) {      // user_finish_noise_kernel: m_ek follows
-            const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs);
+            const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor);
             k.insert(k.end(), mek.begin(), mek.end());
         }
         ok = ok && hipMalloc(&u->d_const, k.size() * sizeof(double)) == hipSuccess &&
@@ -1076,7 +1159,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
                 if (me[e] != (double)n_t) bad = "a missing observation (NaN)";
         }
         if (bad.empty()) {
-            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz);
+            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz, censor != nullptr, censor);
             u->img_len = (int)img.size();
             ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
                  hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
@@ -1108,7 +1191,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     }
     {   // occupancy of the compiled kernel with its pool in LDS
         int nb = 0;
-        const size_t lds = multi ? user_lds_bytes3(n_states, n_ex, n_t, n_obs, nz != nullptr) : user_lds_bytes(n_states, n_ex, n_t);
+        const size_t lds = multi ? user_lds_bytes3(n_states, n_ex, n_t, n_obs, nz != nullptr, censor != nullptr) : user_lds_bytes(n_states, n_ex, n_t);
         if (lds > kUserLdsCap) {
             user_model_release(c);
             return smc_fail(c, "smc_set_model_user: data set too large for the kernel's LDS table (n_ex * n_t * 16 B + pools > 150 KB)");
@@ -1167,11 +1250,11 @@ int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs,
 static int set_model_user_noise(smc_ctx *c, const char *who, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                                 const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                                 const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol,
-                                int method, const UserInputs *in, const UserEvents *ev = nullptr) {
+                                int method, const UserInputs *in, const UserEvents *ev = nullptr, const signed char *censor = nullptr) {
     if (!c) return smc_fail(nullptr, "NULL context");
     const std::string bad = noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed);
     if (!bad.empty()) return smc_fail(c, (std::string(who) + ": " + bad).c_str());
-    if (!prop_index) {      // today's model: one sigma for every output - the smc_set_model_user3 path and its bits
+    if (!prop_index && !censor) {      // today's model: one sigma for every output - the smc_set_model_user3 path and its bits
         bool last = true, fixed = true;
         for (int k = 0; k < n_obs; ++k) {
             last = last && add_index[k] == c->dim - 1;
@@ -1190,7 +1273,7 @@ static int set_model_user_noise(smc_ctx *c, const char *who, const char *source,
         nz.scale[k] = (k < n_obs && obs_scale) ? obs_scale[k] : 1.0;
     }
     nz.prop = prop_index ? 1 : 0;
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in, ev);
+    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in, ev, censor);
 }
 
 int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
@@ -1245,6 +1328,58 @@ int smc_set_model_user6(smc_ctx *c, const char *source, int n_states, int n_obs,
         return smc_fail(c, "smc_set_model_user6: add_index is NULL (the sigma rule) and another part of a noise model is given");
     return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
                                method, true, nullptr, in, &events);
+}
+
+// censored observations: smc_set_model_user6's arguments, then the flags.  NULL or all zeros: smc_set_model_user6, its path and
+// its bits.  Else the model takes the noise path; without a noise specification (add_index NULL) the equivalent one is formed
+// here - every output at the last parameter under est_sigma, else fixed at sigma_fixed.
+int smc_set_model_user7(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
+                        const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
+                        const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
+                        double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot, const double *ev_t,
+                        const double *ev_v, int n_ev, int n_val, const signed char *censor) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    bool any = false;
+    if (censor && n_ex >= 1 && n_t >= 1 && user_obs_ok(n_obs))
+        for (size_t i = 0; i < (size_t)n_ex * n_t * n_obs && !any; ++i) any = censor[i] != 0;
+    if (!any)
+        return smc_set_model_user6(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index, add_fixed, prop_index,
+                                   prop_fixed, rtol, atol, method, est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot, ev_t, ev_v, n_ev, n_val);
+    {   // the data's own rules first (the flags' rules assume them), then the flags'
+        std::vector<double> me, ls;
+        const std::string bad_obs = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls) : std::string("NULL t or obs");
+        if (!bad_obs.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad_obs).c_str());
+        const std::string bad = censor_layout_error(t, obs, censor, n_ex, n_t, n_obs, n_ex, n_t, n_obs);
+        if (!bad.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad).c_str());
+    }
+    const UserInputs inputs{in_t, in_u, n_in, n_knot};
+    const UserInputs *in = &inputs;
+    if (n_in == 0) {
+        if (in_t || in_u) return smc_fail(c, "smc_set_model_user7: n_in = 0 with in_t or in_u given (both must be NULL)");
+        in = nullptr;
+    }
+    const UserEvents events{ev_t, ev_v, n_ev, n_val};
+    const UserEvents *ev = &events;
+    if (n_ev == 0) {
+        if (ev_t || ev_v) return smc_fail(c, "smc_set_model_user7: n_ev = 0 with ev_t or ev_v given (both must be NULL)");
+        ev = nullptr;
+    }
+    int sigma_index[kUserMaxObs];
+    double sigma_value[kUserMaxObs];
+    if (!add_index) {
+        if (add_fixed || prop_index || prop_fixed)
+            return smc_fail(c, "smc_set_model_user7: add_index is NULL (the sigma rule) and another part of a noise model is given");
+        if (!est_sigma && !(std::isfinite(sigma_fixed) && sigma_fixed > 0.0))
+            return smc_fail(c, "smc_set_model_user7: sigma_fixed must be finite and > 0");
+        for (int k = 0; k < kUserMaxObs; ++k) {
+            sigma_index[k] = est_sigma ? c->dim - 1 : -1;
+            sigma_value[k] = est_sigma ? 0.0 : sigma_fixed;
+        }
+        add_index = sigma_index;
+        add_fixed = sigma_value;
+    }
+    return set_model_user_noise(c, "smc_set_model_user7", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
+                                add_fixed, prop_index, prop_fixed, rtol, atol, method, in, ev, censor);
 }
 
 int smc_user_set_design_events(smc_ctx *c, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new) {
@@ -1417,7 +1552,7 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
 }
 static int design_too_large(smc_ctx *c, const UserModel *u, const char *who, int n_t) {
     return smc_fail(c, (std::string(who) + ": one row of the design does not fit the kernel's LDS table: " +
-                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs, u->noise)) + " B needed, " + std::to_string(kUserLdsCap) +
+                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs, u->noise, u->geom.censor != 0)) + " B needed, " + std::to_string(kUserLdsCap) +
                         " B available").c_str());
 }
 

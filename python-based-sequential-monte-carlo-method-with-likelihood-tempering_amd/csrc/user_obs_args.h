@@ -51,7 +51,11 @@ struct UserObsArgs {
 #ifdef SMC_USER_NOBS
 namespace smc_obs {
 constexpr int kObs = SMC_USER_NOBS;
+#ifdef SMC_USER_CENSOR
+constexpr int kRec = smc::obs_rec_words_censor(kObs);      // user_censor.h: the record's last word holds its outputs' flags
+#else  // SMC_USER_CENSOR
 constexpr int kRec = smc::obs_rec_words(kObs);
+#endif  // SMC_USER_CENSOR
 // one data time: x = t, y[k] = obs_k; from the row's end on x = +inf and y[0] = the row's end time
 struct alignas(16) Rec {
     double x;
@@ -116,7 +120,11 @@ struct Noise {
     double q[kObs];
 #endif
 };
+#ifdef SMC_USER_CENSOR
+__device__ __forceinline__ const double *noise_lds(int n_ex, int n_t) { return lds() + smc::obs_table_at(n_ex) + n_ex * (n_t + 1) * kRec; }
+#else  // SMC_USER_CENSOR
 __device__ __forceinline__ const double *noise_lds(int n_ex, int n_t) { return lds() + smc::obs_noise_at(n_ex, n_t, kObs); }
+#endif  // SMC_USER_CENSOR
 __device__ __forceinline__ double mek(int e, int k, int n_ex, int n_t) { return noise_lds(n_ex, n_t)[smc::kNoiseHdr + 8 * e + k]; }
 // parameter number idx (as a double) of th, or fixed: selects, so that th stays in registers
 __device__ __forceinline__ double noise_pick(const double *th, double idx, double fixed) {
@@ -162,6 +170,37 @@ __device__ __forceinline__ void noise_weights(Noise &nz, const double *th, int n
 #if SMC_USER_NOISE_PROP
 __device__ __attribute__((noinline)) double noise_half_log1p(double u) { return 0.5 * log1p(u); }
 #endif
+#ifdef SMC_USER_CENSOR
+// A censored value (user_censor.h; flag c = 1: the true value is <= obs, 2: >= obs): its term is log Phi(z), z = (obs - f) / sd
+// from the left and (f - obs) / sd from the right, with 1 / sd^2 = 2 w_k / (1 + q_k f^2) from the item's weights.  Floor 0, excess
+// x = -log Phi(z) >= 0: the item's sum still only grows.  r = obs - f.  A z that is not finite (f NaN or infinite) gives NaN, the
+// route a failed output takes; zeroed weights (parameters that make logL -inf) give z = 0 and a finite x that is never used.
+template <bool FUSE>
+__device__ __forceinline__ double censor_term(int c, double r, double f, const Noise &nz, int k) {
+    double z;
+#if SMC_USER_NOISE_PROP
+    if (FUSE) {
+        z = (c == smc::kCensorLeft ? r : -r) * sqrt(2.0 * nz.w[k] / (1.0 + nz.q[k] * (f * f)));
+    } else {
+        const double f2 = f * f;
+        const double u = nz.q[k] * f2;
+        const double den = 1.0 + u;
+        const double w2 = 2.0 * nz.w[k];
+        const double iv = w2 / den;
+        const double inv_sd = sqrt(iv);
+        const double rs = (c == smc::kCensorLeft) ? r : -r;
+        z = rs * inv_sd;
+    }
+#else
+    const double w2 = 2.0 * nz.w[k];
+    const double inv_sd = sqrt(w2);
+    const double rs = (c == smc::kCensorLeft) ? r : -r;
+    z = rs * inv_sd;
+    (void)f;
+#endif
+    return (fabs(z) < __longlong_as_double(0x7ff0000000000000LL)) ? smc_cens::censor_excess(z) : __longlong_as_double(0x7ff8000000000000LL);
+}
+#endif  // SMC_USER_CENSOR
 // emit under a noise model: x_ik added to the item's sum.  FUSE as above: one contracted expression per step where the RK45
 // kernel's -ffp-contract=on allows it, every product and sum rounded on its own in the BDF kernel.
 template <bool PRED, bool FUSE>
@@ -169,9 +208,19 @@ __device__ __forceinline__ void emit_noise(double &sx, double *&pred, const Nois
                                            double t_out, const double *obs) {
     double m[kObs];
     model_obs(t_out, yy, th, c, m);
+#ifdef SMC_USER_CENSOR
+    const int flags = (int)obs[kRec - 2];       // the record's last word, read with the record (obs = its y)
+#endif  // SMC_USER_CENSOR
 #pragma unroll
     for (int k = 0; k < kObs; ++k) {
         const double r = obs[k] - m[k];
+#ifdef SMC_USER_CENSOR
+        const int ck = (flags >> (2 * k)) & 3;
+        if (ck != 0) {                          // a flag stands on a finite value only (censor_layout)
+            sx += censor_term<FUSE>(ck, r, m[k], nz, k);
+            continue;
+        }
+#endif  // SMC_USER_CENSOR
 #if SMC_USER_NOISE_PROP
         double x;
         if (FUSE) {

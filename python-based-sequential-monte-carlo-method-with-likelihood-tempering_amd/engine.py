@@ -174,7 +174,7 @@ class HipEngine:
         self.model = ("mm", t.shape[0], t.shape[1])
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
-                       atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None, events=None):
+                       atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None, events=None, censor=None):
         """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
@@ -196,7 +196,13 @@ class HipEngine:
         row may end in NaN, or hold none) and the numbers of every event; the source defines smc_user_event(j, t, y, theta, cond),
         which changes y in place at event j and reads its numbers as smc_event_value(cond, j, k).  The solve is the chain of
         solve_ivp calls between the events (include/smc_hip.h); user_models.event_layout states the rules (ValueError for events
-        that break them).  events=None goes through the calls above exactly as before."""
+        that break them).  events=None goes through the calls above exactly as before.
+        Censored observations (smc_set_model_user7): censor (n_ex, n_t, n_obs) integer flags beside obs - 0: obs is the measured
+        value; -1: left-censored, the true value is <= obs, which holds the lower limit; +1: right-censored, >= obs, the upper limit.
+        A censored value contributes log Phi(z) (user_models.censored_loglik is the likelihood, censor_layout the rules: ValueError
+        for flags that break them, censor_data makes such data).  With a flag set the model takes the noise path; noise=None then
+        stands for every output at the last parameter (est_sigma) or fixed at sigma_fixed.  Combines with everything above.
+        censor=None or all zeros goes through the calls above exactly as before."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
@@ -224,12 +230,30 @@ class HipEngine:
             pi = None if pi is None else np.ascontiguousarray(pi, dtype=np.int32)
             pf = None if pf is None else np.ascontiguousarray(pf)
         n_in = n_ev = n_val = 0
-        in_t = in_u = None
+        in_t = in_u = ev_t = ev_v = None
+        if censor is not None:
+            from .user_models import censor_layout
+            censor = np.asarray(censor)
+            if not multi:      # a 2-D obs: the flags of its one output
+                obs3 = _f64(obs.reshape(obs.shape + (1,)))
+                censor = censor.reshape(censor.shape + (1,)) if censor.ndim == 2 else censor
+            censor_layout(t, obs if multi else obs3, censor)
+            censor = np.ascontiguousarray(censor, dtype=np.int8) if np.any(censor != 0) else None
+        if censor is not None and not multi:
+            multi, obs, n_obs, scale = True, obs3, 1, None
         if inputs is not None:
             in_t, in_u, n_in = self._inputs("set_model_user", inputs, t.shape[0])
         if events is not None:
             ev_t, ev_v, n_val = self._events("set_model_user", events, t)
             n_ev = ev_t.shape[1]
+        if censor is not None:
+            self._ck(self.L.smc_set_model_user7(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
+                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
+                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
+                                                int(bool(est_sigma)), float(sigma_fixed), fp(in_t), fp(in_u), n_in,
+                                                0 if in_t is None else in_t.shape[1], fp(ev_t), fp(ev_v), n_ev, n_val,
+                                                censor.ctypes.data_as(B.c_i8p)), "smc_set_model_user7")
+        elif events is not None:
             self._ck(self.L.smc_set_model_user6(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
                                                 None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
                                                 ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],

@@ -204,6 +204,104 @@ def noise_loglik(pred, t, obs, theta, noise, obs_scale=None):
     return np.where(np.all(a > 0, axis=1) & np.all(b >= 0, axis=1), lk, -np.inf)
 
 
+def censor_layout(t, obs, censor):
+    """The rules of the flags of censored observations (include/smc_hip.h: smc_set_model_user7), in NumPy, for t (n_ex, n_t) and
+    obs (n_ex, n_t, n_obs) that obs_layout accepts: censor has obs's shape; a flag is 0 (obs is the measured value), -1
+    (left-censored: the true value is <= obs, the lower limit) or +1 (right-censored: >= obs, the upper limit); a nonzero flag
+    stands on a finite value at a finite time of its row.  Returns {"quantified": (n_ex, n_obs) int, "censored": (n_ex, n_obs)
+    int}, the counts per experiment and output (quantified = m_ek); raises ValueError, in the library's words
+    (smc_user_censor_check), for flags the library refuses - the first offence in row-major order."""
+    import numpy as np
+    t = np.asarray(t, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    n_t_e = obs_layout(t, obs)["n_t_e"]
+    c = np.asarray(censor)
+    if c.shape != obs.shape:
+        raise ValueError(f"censor_layout: censor must have the shape of obs {tuple(int(v) for v in obs.shape)}, "
+                         f"got {tuple(int(v) for v in c.shape)}")
+    n_ex, n_t, n_obs = obs.shape
+    inside = (np.arange(n_t)[None, :] < n_t_e[:, None])[:, :, None]
+    set_ = c != 0
+    bad_flag = set_ & (c != -1) & (c != 1)
+    bad_end = set_ & ~inside
+    bad_nan = set_ & np.isnan(obs)
+    bad = bad_flag | bad_end | bad_nan
+    if bad.any():
+        e, i, k = (int(v) for v in np.unravel_index(int(np.flatnonzero(bad)[0]), c.shape))
+        where = f"row {e}, time {i}, output {k}"
+        if bad_flag[e, i, k]:
+            v = c[e, i, k]
+            raise ValueError(f"censor_layout: censor holds the flag {int(v) if v == int(v) else v} at {where} "
+                             "(0: measured, -1: at or below obs, +1: at or above obs)")
+        if bad_end[e, i, k]:
+            raise ValueError(f"censor_layout: censor flags a value past the end of its row at {where}")
+        raise ValueError(f"censor_layout: censor flags a value that was not measured (obs is NaN) at {where}")
+    seen = ~np.isnan(obs) & inside
+    return {"quantified": (seen & ~set_).sum(axis=1).astype(np.int64), "censored": set_.sum(axis=1).astype(np.int64)}
+
+
+def censor_excess(z):
+    """x = -log Phi(z), the excess of a censored term over its floor 0 (include/smc_hip.h: smc_set_model_user7), as the kernels
+    form it (csrc/user_censor.h): z > 0: -log1p(-erfc(z / sqrt 2) / 2); z <= 0: z^2 / 2 - log(erfcx(-z / sqrt 2) / 2).  Accurate
+    in both tails, >= 0 in floating point, finite out to z = -1e154 and exactly 0 from z = 40 on; NaN for NaN."""
+    import numpy as np
+    from scipy.special import erfc, erfcx
+    z = np.asarray(z, dtype=np.float64)
+    y = z / np.sqrt(2.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        right = -np.log1p(-0.5 * erfc(np.where(z > 0, y, 1.0)))
+        zl = np.where(z > 0, 0.0, z)
+        left = 0.5 * (zl * zl) - np.log(0.5 * erfcx(-zl / np.sqrt(2.0)))
+    return np.where(z > 0, right, np.where(np.isnan(z), np.nan, left))
+
+
+def censored_loglik(pred, t, obs, censor, theta, noise, obs_scale=None):
+    """The likelihood of a noise model with censored observations (include/smc_hip.h: smc_set_model_user7) applied to given model
+    outputs - its executable definition.  Arguments as noise_loglik's, and censor (n_ex, n_t, n_obs) by censor_layout's rules.
+    With sd as in noise_loglik:
+        logL = sum over quantified [-1/2 log(2 pi) - log sd - (obs - f)^2 / (2 sd^2)] + sum over censored log Phi(z),
+        z = (obs - f) / sd  (flag -1, the true value is <= obs),   z = (f - obs) / sd  (flag +1, the true value is >= obs),
+    log Phi(z) = -censor_excess(z); -inf where any a_k <= 0 or any b_k < 0.  Returns (n,).  With every flag 0 it is noise_loglik's
+    array exactly."""
+    import numpy as np
+    obs = np.asarray(obs, dtype=np.float64)
+    c = np.asarray(censor)
+    censor_layout(t, obs, c)
+    quantified = noise_loglik(pred, t, np.where(c != 0, np.nan, obs), theta, noise, obs_scale)
+    if not np.any(c != 0):
+        return quantified
+    pred = np.asarray(pred, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64)
+    n_obs = obs.shape[2]
+    ai, af, pi, pf = noise_layout(noise, n_obs, theta.shape[1])
+    scale = np.ones(n_obs) if obs_scale is None else np.asarray(obs_scale, dtype=np.float64).reshape(n_obs)
+    a = np.where(ai >= 0, theta[:, np.maximum(ai, 0)], af[None, :])
+    b = np.zeros_like(a) if pi is None else np.where(pi >= 0, theta[:, np.maximum(pi, 0)], pf[None, :])
+    cens = (c != 0)[None]
+    f = np.where(cens, pred, 0.0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        sd = np.sqrt((a * scale)[:, None, None, :] ** 2 + (b[:, None, None, :] * f) ** 2)
+        z = np.where(cens, np.where((c < 0)[None], obs[None] - f, f - obs[None]) / sd, 0.0)
+        term = np.where(cens, censor_excess(z), 0.0)
+        lk = quantified - term.sum(axis=(1, 2, 3))
+    return np.where(np.all(a > 0, axis=1) & np.all(b >= 0, axis=1), lk, -np.inf)
+
+
+def censor_data(values, lower=None, upper=None):
+    """Pseudo-data with limits of quantification: values (..., n_obs); lower, upper: a limit per output ((n_obs,) or a scalar; None
+    or NaN: no limit).  Returns (obs, censor) of values' shape: where a value falls below its lower limit obs holds that limit and
+    censor -1, above its upper limit the upper limit and +1, else the value and 0; NaN (not measured) stays NaN with flag 0."""
+    import numpy as np
+    v = np.array(values, dtype=np.float64)
+    n_obs = v.shape[-1]
+    lim = lambda x: np.full(n_obs, np.nan) if x is None else np.broadcast_to(np.asarray(x, dtype=np.float64), (n_obs,))
+    lo, hi = lim(lower), lim(upper)
+    with np.errstate(invalid="ignore"):
+        below, above = v < lo, v > hi
+    obs = np.where(below, lo, np.where(above, hi, v))
+    return obs, (above.astype(np.int8) - below.astype(np.int8))
+
+
 def input_layout(in_t, in_u, n_ex):
     """The data rules of a model's time-varying inputs (include/smc_hip.h: smc_set_model_user5), in NumPy: in_t (n_ex, n_knot) knot
     times, a row by the row rules of obs_layout's t - a strictly increasing finite run of at least one knot, possibly followed by

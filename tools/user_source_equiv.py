@@ -3,13 +3,15 @@
 
     tools/user_source_equiv.py PARENT/libsmc_hip.so CANDIDATE/libsmc_hip.so [--bytes] [--keep DIR] [--only SUBSTRING]
 
-For every case of the matrix below both libraries write what they would hand to hiprtc (smc_user_model_dump_source2 .. 6:
+For every case of the matrix below both libraries write what they would hand to hiprtc (smc_user_model_dump_source2 .. 7:
 no GPU is touched, so both load into this process).  The matrix: both methods over one-output and multi-output sources, with
 and without a cost hint or a Jacobian, under additive and proportional noise, with measured inputs; and the models of
 tests/dosed_model.py WITHOUT their scheduled events (the source without smc_user_event, n_ev = 0 - through
 smc_user_model_dump_source6 where a library has it, else through dump_source5): a model without events must be compiled from
 the text it had before events existed, byte for byte.  The event variants themselves have no counterpart in a parent without
-events; tools/user_event_bench.py --census reports their registers.  --bytes: every dumped
+events; tools/user_event_bench.py --census reports their registers.  Likewise the noise models of tests/noise_model_chain.py
+WITHOUT censored observations through smc_user_model_dump_source7 (censor = 0) where a library has it, else through
+dump_source4: the censored variants have no counterpart in a parent without them (tools/user_censor_bench.py --census).  --bytes: every dumped
 file of the candidate must be the parent's byte for byte (an edit that only moves text), and a header only one of the two has
 is reported.  Default: both dumps are compiled off line with hiprtc's flags
 (hipcc --offload-arch=gfx950 -O3 -ffp-contract=on -fno-fast-math -I <dump> -S --cuda-device-only) and the listings compared
@@ -47,7 +49,7 @@ def _load(path, name):
 def cases():
     """(label, source, n_states, method, n_obs, how) - n_obs None: the one-output dump (dump_source2), else dump_source3; how, when not
     None, says what dump_source4 / 5 need on top: dim, noise (0 none, 1 additive, 2 with a proportional part) and, for a model with
-    inputs, n_cond, n_in, n_knot; "n_ev": 0 asks for dump_source6 with no events.  The n_obs = 1 multi dumps are what a model of
+    inputs, n_cond, n_in, n_knot; "n_ev": 0 asks for dump_source6 with no events, "censor": 0 for dump_source7 without censoring.  The n_obs = 1 multi dumps are what a model of
     smc_set_model_user / 2 compiles at its first smc_user_predict."""
     um = _load(os.path.join(ROOT, "python-based-sequential-monte-carlo-method-with-likelihood-tempering_amd", "user_models.py"), "_um")
     chain8 = _load(os.path.join(ROOT, "tests", "test_user_model.py"), "_tum").CHAIN8
@@ -84,13 +86,19 @@ def cases():
         m = BDF if c["method"] == "BDF" else RK45
         out.append((f"{cid}.{tag(m)}.nobs{c['n_obs']}.noev", dosed.PLAIN[cid], c["ns"], m, c["n_obs"],
                     {"dim": c["dim"], "noise": 0, "n_cond": c["n_cond"], "n_in": c["n_in"], "n_knot": 5 if c["n_in"] else 0, "n_ev": 0}))
+    # the noise models without censored observations (dump_source7 with censor = 0, or dump_source4)
+    out += [(f"CONSECUTIVE_REACTIONS_AB.{tag(m)}.nobs2.{'prop' if k > 1 else 'add'}.nocens", um.CONSECUTIVE_REACTIONS_AB, 2, m, 2,
+             {"dim": chain_dim, "noise": k, "censor": 0}) for m in (RK45, BDF) for k in (1, 2)]
     return out
 
 
 def dump(lib, case, d):
     _, source, ns, method, n_obs, how = case
     os.makedirs(d)
-    if how is not None and "n_ev" in how and hasattr(lib, "smc_user_model_dump_source6"):
+    if how is not None and "censor" in how and hasattr(lib, "smc_user_model_dump_source7"):
+        rc = lib.smc_user_model_dump_source7(source.encode(), ns, how["dim"], method, n_obs, how["noise"], 0, 0, 0, 0, 0, how["censor"],
+                                             d.encode())
+    elif how is not None and "n_ev" in how and hasattr(lib, "smc_user_model_dump_source6"):
         rc = lib.smc_user_model_dump_source6(source.encode(), ns, how["dim"], method, n_obs, how["noise"], how["n_cond"], how["n_in"],
                                              how["n_knot"], how["n_ev"], 0, d.encode())
     elif how is not None and "n_in" in how:
