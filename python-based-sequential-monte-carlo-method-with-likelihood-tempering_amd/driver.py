@@ -281,6 +281,19 @@ def mvn_transform(cov_m):
     return np.sqrt(sv)[:, None] * v
 
 
+def fix_row_signs(factor):
+    """A multivariate_normal factor with the largest component of every row positive - the convention of the device's own
+    factor (csrc/mh_control.h).  LAPACK's signs are arbitrary and need not survive a change in the last bits of cov_m: the
+    cross-rank moment sums of W ranks round differently from one rank's, and a row that comes out negated turns every proposal
+    z @ factor of the iteration into another (equally valid) one, so a run with host-side reductions no longer followed the
+    one-rank run (seen at d = 8, 2 ranks against 1: tests/test_user_sharded.py).  With the signs fixed the factor is a
+    continuous function of cov_m wherever its singular values are distinct."""
+    a = np.array(factor, dtype=np.float64)
+    big = a[np.arange(a.shape[0]), np.argmax(np.abs(a), axis=1)]
+    a[big < 0.0] *= -1.0
+    return a
+
+
 def write_particles_csv(path, arr, header=None):
     """One particle table in the reference's two on-disk formats: bare `np.savetxt(..., delimiter=',')`
     (SMC_methanation_main.py:181,422; methanation_functions.py:233-234) or, with column names, the pandas CSV of
@@ -333,7 +346,10 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
 
     predictive: keyword arguments of HipEngine.predictive_summary (user models only; `which` defaults to the final posterior,
     SMC_SET_PRED): the summary is formed on the device before returning and stored as out["predictive"].  A design's "inputs"
-    and "events" (a feed profile or a dosing regimen that was never run) go through with the rest.
+    and "events" (a feed profile or a dosing regimen that was never run) go through with the rest.  With several ranks each
+    rank summarises its own block of particles, and with noise=True it draws the noise under its GLOBAL particle numbers:
+    global_offset defaults to the block's start rank * n_local, as in every other device-RNG call of the run, so the ranks' bands
+    are independent draws and do not depend on how the particles are sharded; a "global_offset" in the dict wins.
 
     Returns a dict: final particles (this rank's block), lk, schedule records, logZ, counters.
     """
@@ -522,7 +538,7 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
                     rr = np.random.uniform(0, 1, n)                           # :235
                     out = engine.mh_step_host_rng(gamma_new, mhstep_ratio, noise[lo:lo + n_local], rr[lo:lo + n_local])
                 else:
-                    out = engine.mh_step_device_rng(gamma_new, mhstep_ratio, mvn_transform(cov_m), seed_device,
+                    out = engine.mh_step_device_rng(gamma_new, mhstep_ratio, fix_row_signs(mvn_transform(cov_m)), seed_device,
                                                     (step << 16) | j, lo)
                 tot = comm.allreduce_sum_i64([out["accepted_ever"], out["accepted_now"], out["n_failed"]])
             account(out)
@@ -575,6 +591,6 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     out = {"p_pred": engine.download_particles(SMC_SET_PRED, **pin), "lk": engine.download_lk(SMC_SET_PRED, **pin),
            "records": records, "logZ": logZ, "gamma": gamma_new, "step": step, "stats": stats,
            "wall_s": time.perf_counter() - start_time}
-    if predictive is not None:
-        out["predictive"] = engine.predictive_summary(**{"which": SMC_SET_PRED, **predictive})
+    if predictive is not None:                    # this rank's block, its noise drawn under the block's global particle numbers
+        out["predictive"] = engine.predictive_summary(**{"which": SMC_SET_PRED, "global_offset": lo, **predictive})
     return out

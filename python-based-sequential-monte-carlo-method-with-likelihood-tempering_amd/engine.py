@@ -627,7 +627,10 @@ class HipEngine:
         value between them (user_models.quantile_ranks, linear_quantile); "n_failed", "rk_attempts"; "kernel_ms":
         {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
         global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
-        With several ranks the summary describes this rank's block only.  inputs, events: as predict_user_at's."""
+        With several ranks each rank summarises its own block only, and the caller passes the block's start as global_offset so
+        that the noise is drawn under the particles' global numbers - run_smc(predictive=...) does; with the default 0 every rank
+        would draw the noise of particles 0 .. n_local - 1 and the ranks' bands would be correlated copies.
+        inputs, events: as predict_user_at's."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("predictive_summary: no user model has been set")
         q = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))

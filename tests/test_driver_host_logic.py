@@ -219,3 +219,24 @@ def test_batched_methanation_loop_accounts_k8_work_from_the_batch_log(pkg, O, da
               "mutation_sweeps", "particle_mutation_steps"):
         assert a["stats"][k] == b["stats"][k] > 0, k
     assert b["stats"]["mh_syncs"] <= a["stats"]["mh_syncs"]
+
+
+def test_host_side_factor_has_the_devices_row_signs(pkg):
+    """driver.fix_row_signs on the pair of covariances at which a host-driven run of the eight-parameter user model over two
+    ranks left its one-rank run (tests/golden/user_sharded_cov_pair.npz: the same cov_m to 1.1e-14, from one and from two
+    ranks' moment sums; LAPACK negated two rows of the factor of one of them): with the device's convention both factors agree
+    to rounding (1e-10 of the largest entry: a singular vector moves by |E| / gap <= 8 x 1.1e-14 x 1.05e-3 / 2.8e-6 = 3.3e-11 of
+    its length), and the convention changes neither a row's direction nor factor^T factor."""
+    from smc_lt_amd import driver
+    pair = np.load(os.path.join(os.path.dirname(__file__), "golden", "user_sharded_cov_pair.npz"))
+    a, b = pair["one_rank"], pair["two_ranks"]
+    assert a.shape == (8, 8) and 0 < np.abs(a - b).max() <= 1e-13 * np.abs(a).max()
+    sv = np.linalg.svd(a)[1]
+    assert np.min(sv[:-1] / sv[1:]) > 1.1                      # distinct singular values: the rows are defined up to their sign
+    fa, fb = (driver.fix_row_signs(driver.mvn_transform(c)) for c in (a, b))
+    assert np.abs(fa - fb).max() <= 1e-10 * np.abs(fa).max()
+    raw = driver.mvn_transform(a)
+    assert np.array_equal(np.abs(fa), np.abs(raw)) and np.array_equal(driver.fix_row_signs(fa), fa)
+    assert np.array_equal(fa.T @ fa, raw.T @ raw)
+    assert np.all(fa[np.arange(8), np.argmax(np.abs(fa), axis=1)] > 0.0)
+    assert np.array_equal(driver.fix_row_signs(-raw), fa)      # whatever signs LAPACK hands out
