@@ -98,7 +98,11 @@ int smc_set_model_methanation(smc_ctx *ctx, const double *cond, const double *gu
  * gfx950) into a kernel that restates solve_ivp(RK45, t_eval = t[e], rtol, atol) and the Gaussian log-likelihood of
  * Micmem_likelihood.py:17-33,62-73 with sigma = the last parameter (est_sigma) or sigma_fixed; smc_loglik and
  * smc_mh_step_* then use it.  t, obs: n_ex x n_t; cond: n_ex x n_cond.  A source that does not compile fails with
- * hiprtc's log in smc_last_error.  smc_user_model_check only compiles (no GPU needed): 0 ok, 1 compile error (log).
+ * hiprtc's log in smc_last_error.  A model is DESCRIBED BY ONE STRUCT, smc_user_model_spec below, and set by
+ * smc_set_model_user_spec; what decides the text of the compiled kernel is the smaller smc_user_source_spec, which
+ * smc_user_model_check_spec only compiles (no GPU needed): 0 ok, 1 compile error (log), 2 bad arguments.  Every feature is
+ * documented once, at its fields; a feature whose fields are zero / NULL is absent, and the model then takes the path, and
+ * gives the bits, it had before the feature existed.
  * Optional fourth ingredient, a COST HINT (a source that contains the name must define it):
  *   __device__ double smc_user_cost(const double *theta);      rough number of RK45 step attempts of one solve with theta
  * Sweeps then hand the solves of particles above 220 attempts out before the index-ordered ones and run those above 3700
@@ -112,8 +116,7 @@ int smc_set_model_methanation(smc_ctx *ctx, const double *cond, const double *gu
  * needs a subnormal or infinite divisor or a * (1 / b) overflows), once with IEEE division; a step attempt runs on the first
  * and is repeated on the second whenever its error norm is not finite.  smc_user_y0, smc_user_obs and smc_user_cost always
  * run with IEEE division.
- * Integrator (smc_set_model_user2 / smc_user_model_check2 / smc_user_model_dump_source2, `method`; the functions without
- * the 2 are method SMC_USER_METHOD_RK45, and an unknown method fails or returns 2):
+ * Integrator (the field `method` of both structs; an unknown method fails or returns 2):
  *   SMC_USER_METHOD_RK45  explicit RK45, as above (the default);
  *   SMC_USER_METHOD_BDF   solve_ivp(method="BDF") as SciPy 1.15's bdf.py has it (variable-order NDF 1-5, Newton with at most four
  *                         iterations, LU of I - c J with partial pivoting, BdfDenseOutput at t) - for a STIFF model, where
@@ -126,181 +129,252 @@ int smc_set_model_methanation(smc_ctx *ctx, const double *cond, const double *gu
 #define SMC_USER_MAX_STATES 8
 #define SMC_USER_METHOD_RK45 0
 #define SMC_USER_METHOD_BDF 1
+#define SMC_USER_MAX_OBS 8
+#define SMC_USER_MAX_INPUTS 8
+#define SMC_USER_MAX_KNOTS 4096
+#define SMC_USER_MAX_EVENTS 256
+#define SMC_USER_MAX_EVENT_VALUES 8
+/* BOTH STRUCTS START WITH struct_size, the caller's sizeof: the library reads min(struct_size, its own sizeof) bytes over zeros, so
+ * a field that a later feature appends reads as absent for a caller built before it.  A struct_size that ends before the fields
+ * every caller has (smc_user_source_spec: through n_obs; smc_user_model_spec: through atol) or exceeds the library's own struct
+ * is refused: the functions return 2, or fail with a message that names struct_size.  Zero the struct, set struct_size, then
+ * the fields in use. */
+/* What decides the text of the run-time compiled kernel; each field is explained at the field of the same name below. */
+typedef struct smc_user_source_spec {
+    size_t struct_size;
+    const char *source;
+    int n_states;   /* 1 .. SMC_USER_MAX_STATES */
+    int dim;        /* parameters per particle, 1 .. SMC_MAX_DIM */
+    int method;     /* SMC_USER_METHOD_* */
+    int n_obs;      /* 0: the one-output source; 1 .. SMC_USER_MAX_OBS: the multi-output source */
+    int noise;      /* 0: the sigma rule, 1: a noise model, 2: one with a proportional part */
+    int n_cond;     /* with inputs or events: the numbers in front of the tables of a cond row */
+    int n_in, n_knot;
+    int n_ev, n_val;
+    int censor;     /* != 0: censored observations; needs noise = 1 or 2 */
+} smc_user_source_spec;
+/* A user model: its source, data, likelihood and tolerances. */
+typedef struct smc_user_model_spec {
+    size_t struct_size;
+    const char *source;
+    int n_states;
+    int method;
+    /* SEVERAL OBSERVED OUTPUTS, MISSING DATA, RAGGED ROWS: n_obs = 1 .. SMC_USER_MAX_OBS outputs per data time (n_obs = 0: the
+     * ONE-OUTPUT MODEL, obs n_ex x n_t compared with smc_user_obs, a NaN given to it makes logL NaN, and obs_scale, the noise
+     * arrays, inputs, events and censor must all be absent); the source defines
+     *   __device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out);   out[0 .. n_obs)
+     * (with n_obs = 1 a source may define smc_user_obs instead; a source that contains the name smc_user_obs_vec must define it).
+     * t: n_ex x n_t, obs: n_ex x n_t x n_obs, row-major.  NaN in obs = not measured: the entry adds nothing to the squared residuals
+     * nor to m_e, the number of finite entries of experiment e.  A row of t may end in a run of NaN times: that experiment has
+     * n_t_e times, is integrated to t[e][n_t_e - 1], and obs at its NaN times is ignored.  The finite times of a row strictly
+     * increase and every row has one; obs holds no infinite value; obs_scale (n_obs relative scales s_k, NULL = ones) is finite
+     * and > 0 - otherwise the set function fails with the reason.  With sigma as before (the last parameter or sigma_fixed):
+     *   logL = sum_e [ -m_e / 2 log(2 pi sigma^2) - sum_(observed i,k of e) log s_k - sum_(observed) ((obs - model) / s_k)^2 / (2 sigma^2) ]
+     * (sigma <= 0: -inf; an experiment with m_e = 0 adds 0).  Exact early rejection applies as before.  In a source spec n_obs >= 1
+     * selects the multi-output source (a dump also writes user_obs_args.h); n_obs outside 0 .. SMC_USER_MAX_OBS returns 2. */
+    int n_obs;
+    const double *t, *obs, *cond, *obs_scale;
+    int n_ex, n_t, n_cond;
+    int est_sigma;          /* the sigma rule: != 0 sigma is the last parameter, else sigma_fixed */
+    double sigma_fixed;
+    /* A NOISE MODEL: a noise level per output, and noise that grows with the signal.  add_index == NULL (then add_fixed,
+     * prop_index, prop_fixed NULL too) is the SIGMA RULE above (est_sigma / sigma_fixed); otherwise est_sigma and sigma_fixed are
+     * not used.  Data, source and obs_scale as above.  Output k has an additive level a_k and a proportional
+     * coefficient b_k, each one of the particle's parameters or a fixed number: add_index[k] is a parameter number in [0, dim), or
+     * -1 for add_fixed[k], which must then be finite and > 0; prop_index / prop_fixed in the same way with prop_fixed[k] >= 0; NULL
+     * for both means no proportional part.  Several outputs may name one parameter.  With f_ik the model's output and s_k = obs_scale:
+     *   sd_ik^2 = (a_k s_k)^2 + (b_k f_ik)^2
+     *   logL    = sum over observed (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ]
+     * (any a_k <= 0 or b_k < 0: -inf; an experiment without an observation adds 0; NaN and ragged rows as above).
+     * Exact early rejection applies: the kernels accumulate the excess of every term over its floor log(a_k s_k).
+     * smc_user_predict, smc_user_predict_at and smc_user_predict_summary work as for every user model; the summary's noise != 0
+     * draws pred + sd_ik z with the particle's own a_k, b_k and prediction.  A specification that is the sigma rule's model - no
+     * proportional part and every add_index dim - 1, or every output fixed to one value - takes the sigma rule's path and gives
+     * its bits.  Everything else that breaks a rule, and a data set whose image (40 + 8 n_ex words larger than the sigma rule's)
+     * exceeds the LDS table, fails with the reason (for the table: bytes needed and available).
+     * Limits: model constants and noise parameters together number at most SMC_MAX_DIM; a purely proportional model (a_k = 0) does
+     * not exist - the floor needs a_k > 0 - and a small fixed a_k stands in for it.
+     * smc_user_noise_check applies the rules of the specification alone (no GPU, no context: the reason is in smc_last_error(NULL)).
+     * In a source spec noise = 0 is the sigma rule's source, 1 a noise model's, 2 one with the proportional part compiled in (one
+     * log1p and one division per observed value; without it neither is compiled). */
+    const int *add_index;
+    const double *add_fixed;
+    const int *prop_index;
+    const double *prop_fixed;
+    double rtol, atol;      /* SciPy's defaults are 1e-3, 1e-6 */
+    /* TIME-VARYING MEASURED INPUTS: a feed rate, a temperature ramp, a logged
+     * inlet concentration - n_in = 1 .. SMC_USER_MAX_INPUTS profiles u_k(t) per experiment, linear between their knots, which the
+     * model reads from any of its functions (smc_user_y0, smc_user_rhs, smc_user_jac, smc_user_obs, smc_user_obs_vec) as
+     *   double smc_input(const double *cond, int k, double t);      input k in [0, n_in) of this experiment at time t
+     * `cond` is the pointer the function was handed - the handle to the experiment; cond[0 .. n_cond) read as before.  The value is
+     * np.interp(t, tk, u_k) over the row's finite knots tk[0] < ... < tk[m-1]: u[0] for t <= tk[0], u[m-1] for t >= tk[m-1], else
+     * with j the last knot <= t
+     *   u[j] + s_j (t - tk[j]),   s_j = (u[j+1] - u[j]) / (tk[j+1] - tk[j])   (the slope is formed once, on the host, by IEEE division);
+     * m = 1 is a constant.  It EQUALS u[j] at t == tk[j] and NEVER LEAVES [min(u[j], u[j+1]), max(u[j], u[j+1])] (clamped), and it
+     * is the same number in both namespaces of an RK45 source.  user_models.input_value is the definition in NumPy.  The
+     * integrators do NOT stop at knots: as solve_ivp with np.interp inside f, they step over the kinks under their own step
+     * control (a switch is a steep ramp between two close knots).  What does stop the integrator, and changes the state by a jump,
+     * is a scheduled event: ev_t below.
+     * Data: in_t n_ex x n_knot, a row by the row rules of t (a strictly increasing finite run of at least one knot, then only NaN);
+     * in_u n_ex x n_knot x n_in, finite at the row's finite knots (and every slope finite) and ignored past them; n_knot <=
+     * SMC_USER_MAX_KNOTS.  Anything else fails with the row, the knot and the rule.  smc_user_input_check applies these rules alone
+     * (no GPU, no context: the reason is in smc_last_error(NULL)).
+     * n_in == 0 needs in_t == in_u == NULL: a model without inputs, its path and its bits.  The table lies behind each
+     * experiment's cond numbers in device memory (n_cond + K + n_in (2 K + 1) doubles per experiment, K = the power of two >=
+     * n_knot: the compiled knot capacity); the LDS table and its limits are those of a model without inputs.  A source that calls smc_input is compiled only for a model with inputs: without them the
+     * compilation stops with "smc_input: this model has no inputs".  smc_loglik, smc_mh_step_*, early rejection, the cost hint,
+     * smc_user_predict and the BDF counters work as for every user model.
+     * A source spec holds the geometry the source is compiled for: n_cond, n_in and n_knot (n_in = 0: a model without inputs;
+     * n_knot is then not used).  A dump then also writes user_input.h.
+     * DESIGNS: t_new == NULL (the data's design) uses the data's inputs.  An explicit design of smc_user_predict_at /
+     * smc_user_predict_summary needs design inputs with the same n_ex_new, set beforehand by smc_user_set_design_inputs (in_t_new
+     * n_ex_new x n_knot_new, in_u_new n_ex_new x n_knot_new x n_in, the rules above; no row may hold more finite knots than K) and
+     * held until replaced; both pointers NULL clears them.  Without matching design inputs the call fails with the reason.  A design
+     * that runs in groups of experiments carries each group's rows of the table. */
+    const double *in_t, *in_u;
+    int n_in, n_knot;
+    /* SCHEDULED EVENTS (doses, feed additions, washouts, resets): at known times the state changes by a jump and the integrator
+     * stops there.  Each experiment e has a row of event times ev_t[e][0 .. n_ev) and per event n_val numbers
+     * ev_v[e][j][0 .. n_val) (a dose amount, a target compartment, ...).  The source of a model with events defines one more
+     * ingredient (a source that contains the name must define it) and may call smc_event_value from it:
+     *     __device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond);   // y changed in place
+     *     double smc_event_value(const double *cond, int j, int k);     // value k of event j of this experiment
+     * cond is the handle to the experiment, as for smc_input, which smc_user_event may read too; smc_user_event always runs with
+     * IEEE division, like smc_user_y0.
+     * A solve of experiment e is the chain of solve_ivp calls a SciPy user would write.  With t0 = t[e][0] and t_end the row's last
+     * finite time the events that fire are those with t0 < tau_j < t_end, in order; segment s is solve_ivp(f, (a, b), y, method,
+     * t_eval = the row's data times in (a, b] (the first: [t0, b]), rtol, atol) with b the next firing event time or t_end; at an
+     * event smc_user_event(j, tau_j, y, ...) is applied to the segment's end state and the next segment starts afresh from
+     * (tau_j, y): RK45 with a new first derivative, select_initial_step over the new interval and no memory of a rejected step, BDF
+     * at order 1 with a new Jacobian and the initial step rule.  A data time equal to tau_j sees the state before the event, the
+     * next representable time after it the state after.  An event with tau_j >= t_end never fires; a segment may hold no data
+     * time; rk_attempts counts step attempts only; a failed segment fails the solve as before (info bit 30, NaN from the stop on).
+     * Event TIMES are data: they cannot depend on theta (amounts can, through smc_user_event), and there are no state-triggered
+     * events.
+     * Row rules: a row of ev_t is a strictly increasing finite run and then only NaN - it may have no event at all; every finite
+     * event time is > t[e][0]; the values are finite at a row's finite events and ignored past them.  Anything else fails with the
+     * row, the event and the rule.  smc_user_event_check applies these rules alone (no GPU, no context; the reason in
+     * smc_last_error(NULL)).
+     * ev_t (n_ex x n_ev), ev_v (n_ex x n_ev x n_val; NULL with n_val == 0), n_ev <= SMC_USER_MAX_EVENTS, 0 <= n_val <=
+     * SMC_USER_MAX_EVENT_VALUES.  n_ev == 0 needs both pointers NULL: a model without events, its path and its bits.  A source spec
+     * holds the geometry n_ev, n_val the source is compiled for (and n_cond; a dump then also writes user_event.h); a source that defines or calls the event names compiles only for a model
+     * with events ("smc_user_event: this model has no events"), and a model with events needs a source with smc_user_event.
+     * smc_user_set_design_events: the events of an explicit design of smc_user_predict_at / smc_user_predict_summary (the what-if
+     * dosing regimen; nothing is compiled again): n_ex_new rows of n_ev_new <= the model's n_ev events, held until replaced, both
+     * pointers NULL clears them.  An explicit design on a model with events without design events of the same n_ex_new fails with
+     * the reason; t_new == NULL uses the data's events. */
+    const double *ev_t, *ev_v;
+    int n_ev, n_val;
+    /* CENSORED OBSERVATIONS: a value the assay could not quantify - below the
+     * limit of quantification in a washout tail, above the upper limit at a peak - is neither dropped (NaN) nor taken for a
+     * measurement of the limit, but contributes the probability of lying beyond it (Beal's M3).  censor: n_ex x n_t x n_obs flags
+     * beside obs, 0: obs is the measured value (the term of the functions above); -1: left-censored, the true value is <= obs, which
+     * holds the lower limit; +1: right-censored, the true value is >= obs, the upper limit.  With sd_ik as under A NOISE MODEL:
+     *   logL = sum over quantified (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ] + sum over censored log Phi(z_ik),
+     *   z_ik = (obs_ik - f_ik) / sd_ik  (left),   (f_ik - obs_ik) / sd_ik  (right);      any a_k <= 0 or b_k < 0: -inf.
+     * user_models.censored_loglik is the definition in NumPy.  The kernels add x = -log Phi(z) >= 0 as
+     *   z > 0:  -log1p(-erfc(z / sqrt 2) / 2),      z <= 0:  z^2 / 2 - log(erfcx(-z / sqrt 2) / 2)
+     * - accurate in both tails, never negative - to the sums of a noise model; a censored value's floor is 0 and m_e, m_ek count
+     * quantified values only, so exact early rejection applies unchanged.
+     * Rules: every flag is -1, 0 or +1; a nonzero flag stands on a finite value at a finite time of its row.  Anything else fails
+     * with the row, the time, the output and the rule.  smc_user_censor_check applies these rules alone to t and obs that
+     * the data rules accept (no GPU, no context; the reason in smc_last_error(NULL)); c_n_ex, c_n_t, c_n_obs: the shape of
+     * censor itself, which must be that of obs.
+     * censor NULL or all zeros: a model without censored observations, its path and its bits.  With a flag set the model is a noise model: add_index == NULL forms the equivalent specification - every
+     * output at parameter dim - 1 under est_sigma, else fixed at sigma_fixed, obs_scale as given.  Limits, times and events
+     * combine freely; a record of the LDS table holds the flags in its pad word (n_obs even) or grows by 16 bytes (n_obs odd), and a
+     * table that no longer fits fails with the bytes needed and available.  smc_user_predict returns lk under this likelihood;
+     * designs (smc_user_predict_at, smc_user_predict_summary) carry no observations and run as before.
+     * In a source spec censor != 0 is the source compiled with SMC_USER_CENSOR (it needs noise = 1 or 2); a dump then also writes
+     * user_censor.h. */
+    const signed char *censor;
+} smc_user_model_spec;
+/* DISPATCH, one rule over the fields (an absent feature takes the earlier path, and its bits with it):
+ *   n_obs == 0                        the one-output model; obs_scale, a noise array, inputs, events or censor given: refused;
+ *   n_in == 0 / n_ev == 0             in_t, in_u / ev_t, ev_v must be NULL;
+ *   censor NULL or all zeros          no censoring; else the data rules run, then the flags' rules, and the model takes the noise
+ *                                     path - with add_index NULL under the specification formed from est_sigma / sigma_fixed;
+ *   add_index given                   the specification's rules run; one that is the sigma rule's model (no prop_index, no
+ *                                     censoring, every output at the last parameter or fixed at one value) takes the sigma rule's path;
+ *   add_index NULL                    the sigma rule; another noise array given: refused.
+ * Messages about the consistency of the arguments start with the name of the called function, a feature's own messages with the
+ * name of the entry point that introduced it (smc_set_model_user5: inputs, 6: events, 7: censoring, 3 / 4: the LDS table). */
+int smc_set_model_user_spec(smc_ctx *ctx, const smc_user_model_spec *spec);
+int smc_user_model_check_spec(const smc_user_source_spec *spec, char *log, int log_cap);
+/* smc_user_model_dump_source_spec writes exactly what hiprtc is given for the spec into the existing directory `dir`: smc_user_model.hip (the user's functions
+ * followed by the library's kernel) and the headers it includes - to read, or to compile off line
+ * (`hipcc --offload-arch=gfx950 -O3 -ffp-contract=on -fno-fast-math -I dir -S dir/smc_user_model.hip`; the build container's
+ * tests run the compiler's uniformity analysis on it).  0 ok, 1 a file could not be written, 2 bad arguments.  No GPU needed. */
+int smc_user_model_dump_source_spec(const smc_user_source_spec *spec, const char *dir);
+/* sizeof and, in declaration order, offsetof of every field of smc_user_source_spec (which = 0) or smc_user_model_spec (which = 1)
+ * as this library was compiled: returns sizeof, or -1 for another `which`, and fills offsets[0 .. min(cap, fields)).  A binding
+ * that mirrors the structs compares its own layout with it. */
+int smc_user_spec_layout(int which, int *offsets, int cap);
+/* the rules of one feature alone (no GPU, no context: the reason is in smc_last_error(NULL)), and the inputs / events of a design */
+int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double *add_fixed, const int *prop_index,
+                         const double *prop_fixed);
+int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n_in, int n_knot);
+int smc_user_event_check(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val);
+int smc_user_censor_check(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs, int c_n_ex,
+                          int c_n_t, int c_n_obs);
+int smc_user_set_design_inputs(smc_ctx *ctx, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new);
+int smc_user_set_design_events(smc_ctx *ctx, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new);
+/* EARLIER ENTRY POINTS, kept with their signatures, return codes and messages: each fills the fields named by its arguments and
+ * leaves every other field zero.  Where they take an n_obs it is 1 .. SMC_USER_MAX_OBS (0 is refused, not the one-output model).
+ *   smc_set_model_user         n_obs = 0, method RK45: source, n_states, t, obs, cond, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol
+ *   smc_set_model_user2        ... and method
+ *   smc_set_model_user3        n_obs and obs_scale as well; no noise arrays (never the noise path), inputs, events, censor
+ *   smc_set_model_user4        as 3 with the four noise arrays in place of est_sigma / sigma_fixed; a NULL add_index is refused
+ *   smc_set_model_user5        as 3 and 4 together (add_index NULL: the sigma rule), and in_t, in_u, n_in, n_knot
+ *   smc_set_model_user6        ... and ev_t, ev_v, n_ev, n_val
+ *   smc_set_model_user7        every field
+ *   smc_user_model_check / dump_source       source, n_states, dim; method RK45, n_obs = 0
+ *   ...2                       ... and method
+ *   ...3                       ... and n_obs
+ *   ...4                       ... and noise = 1, or 2 with `proportional` != 0
+ *   ...5                       ... noise as given, and n_cond, n_in, n_knot
+ *   ...6                       ... and n_ev, n_val
+ *   ...7                       every field */
 int smc_set_model_user(smc_ctx *ctx, const char *source, int n_states, const double *t, const double *obs, const double *cond,
                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol);
 int smc_set_model_user2(smc_ctx *ctx, const char *source, int n_states, const double *t, const double *obs, const double *cond,
                         int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method);
 int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap);
 int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap);
-/* Writes exactly what hiprtc is given for `source` into the existing directory `dir`: smc_user_model.hip (the user's functions
- * followed by the library's kernel) and the four headers it includes - to read, or to compile off line
- * (`hipcc --offload-arch=gfx950 -O3 -ffp-contract=on -fno-fast-math -I dir -S dir/smc_user_model.hip`; the build container's
- * tests run the compiler's uniformity analysis on it).  0 ok, 1 a file could not be written, 2 bad arguments.  No GPU needed. */
 int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir);
 int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir);
-/* SEVERAL OBSERVED OUTPUTS, MISSING DATA, RAGGED ROWS (additive; the functions above keep their behaviour, a NaN given to them
- * still makes logL NaN).  n_obs = 1 .. SMC_USER_MAX_OBS outputs per data time; the source defines
- *   __device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out);   out[0 .. n_obs)
- * (with n_obs = 1 a source may define smc_user_obs instead; a source that contains the name smc_user_obs_vec must define it).
- * t: n_ex x n_t, obs: n_ex x n_t x n_obs, row-major.  NaN in obs = not measured: the entry adds nothing to the squared residuals
- * nor to m_e, the number of finite entries of experiment e.  A row of t may end in a run of NaN times: that experiment has
- * n_t_e times, is integrated to t[e][n_t_e - 1], and obs at its NaN times is ignored.  The finite times of a row strictly
- * increase and every row has one; obs holds no infinite value; obs_scale (n_obs relative scales s_k, NULL = ones) is finite
- * and > 0 - otherwise smc_set_model_user3 fails with the reason.  With sigma as before (the last parameter or sigma_fixed):
- *   logL = sum_e [ -m_e / 2 log(2 pi sigma^2) - sum_(observed i,k of e) log s_k - sum_(observed) ((obs - model) / s_k)^2 / (2 sigma^2) ]
- * (sigma <= 0: -inf; an experiment with m_e = 0 adds 0).  Exact early rejection applies as before.  check3 / dump_source3:
- * as check2 / dump_source2 (dump_source3 also writes user_obs_args.h); n_obs outside 1 .. SMC_USER_MAX_OBS returns 2. */
-#define SMC_USER_MAX_OBS 8
 int smc_set_model_user3(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                         const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed,
                         double rtol, double atol, int method);
 int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap);
 int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir);
-/* A NOISE MODEL: a noise level per output, and noise that grows with the signal (additive; the functions above keep their
- * behaviour).  Data, source and obs_scale as smc_set_model_user3.  Output k has an additive level a_k and a proportional
- * coefficient b_k, each one of the particle's parameters or a fixed number: add_index[k] is a parameter number in [0, dim), or
- * -1 for add_fixed[k], which must then be finite and > 0; prop_index / prop_fixed in the same way with prop_fixed[k] >= 0; NULL
- * for both means no proportional part.  Several outputs may name one parameter.  With f_ik the model's output and s_k = obs_scale:
- *   sd_ik^2 = (a_k s_k)^2 + (b_k f_ik)^2
- *   logL    = sum over observed (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ]
- * (any a_k <= 0 or b_k < 0: -inf; an experiment without an observation adds 0; NaN and ragged rows as smc_set_model_user3).
- * Exact early rejection applies: the kernels accumulate the excess of every term over its floor log(a_k s_k).
- * smc_user_predict, smc_user_predict_at and smc_user_predict_summary work as for every user model; the summary's noise != 0
- * draws pred + sd_ik z with the particle's own a_k, b_k and prediction.  A specification that is the model of
- * smc_set_model_user3 - no proportional part and every add_index dim - 1, or every output fixed to one value - takes that
- * function's path and gives its bits.  Everything else that breaks a rule, and a data set whose image (40 + 8 n_ex words larger
- * than smc_set_model_user3's) exceeds the LDS table, fails with the reason (for the table: bytes needed and available).
- * Limits: model constants and noise parameters together number at most SMC_MAX_DIM; a purely proportional model (a_k = 0) does
- * not exist - the floor needs a_k > 0 - and a small fixed a_k stands in for it.
- * smc_user_noise_check applies the rules of the specification alone (no GPU, no context: the reason is in smc_last_error(NULL)).
- * check4 / dump_source4: as check3 / dump_source3 for the source of a noise model, `proportional` != 0 with the proportional
- * part compiled in (one log1p and one division per observed value; without it neither is compiled). */
 int smc_set_model_user4(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                         const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                         const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method);
-int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double *add_fixed, const int *prop_index,
-                         const double *prop_fixed);
 int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap);
 int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir);
-/* TIME-VARYING MEASURED INPUTS (additive; the functions above keep their behaviour): a feed rate, a temperature ramp, a logged
- * inlet concentration - n_in = 1 .. SMC_USER_MAX_INPUTS profiles u_k(t) per experiment, linear between their knots, which the
- * model reads from any of its functions (smc_user_y0, smc_user_rhs, smc_user_jac, smc_user_obs, smc_user_obs_vec) as
- *   double smc_input(const double *cond, int k, double t);      input k in [0, n_in) of this experiment at time t
- * `cond` is the pointer the function was handed - the handle to the experiment; cond[0 .. n_cond) read as before.  The value is
- * np.interp(t, tk, u_k) over the row's finite knots tk[0] < ... < tk[m-1]: u[0] for t <= tk[0], u[m-1] for t >= tk[m-1], else
- * with j the last knot <= t
- *   u[j] + s_j (t - tk[j]),   s_j = (u[j+1] - u[j]) / (tk[j+1] - tk[j])   (the slope is formed once, on the host, by IEEE division);
- * m = 1 is a constant.  It EQUALS u[j] at t == tk[j] and NEVER LEAVES [min(u[j], u[j+1]), max(u[j], u[j+1])] (clamped), and it
- * is the same number in both namespaces of an RK45 source.  user_models.input_value is the definition in NumPy.  The
- * integrators do NOT stop at knots: as solve_ivp with np.interp inside f, they step over the kinks under their own step
- * control (a switch is a steep ramp between two close knots).  What does stop the integrator, and changes the state by a jump,
- * is a scheduled event: smc_set_model_user6 below.
- * Data: in_t n_ex x n_knot, a row by the row rules of t (a strictly increasing finite run of at least one knot, then only NaN);
- * in_u n_ex x n_knot x n_in, finite at the row's finite knots (and every slope finite) and ignored past them; n_knot <=
- * SMC_USER_MAX_KNOTS.  Anything else fails with the row, the knot and the rule.  smc_user_input_check applies these rules alone
- * (no GPU, no context: the reason is in smc_last_error(NULL)).
- * smc_set_model_user5: the arguments of smc_set_model_user4, then est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot.  add_index ==
- * NULL (then add_fixed, prop_index, prop_fixed NULL too) selects the sigma rule of smc_set_model_user3 (est_sigma / sigma_fixed),
- * otherwise the noise model of smc_set_model_user4 applies.  n_in == 0 with in_t == in_u == NULL takes the existing function's
- * path and gives its bits.  The table lies behind each experiment's cond numbers in device memory (n_cond + K + n_in (2 K + 1)
- * doubles per experiment, K = the power of two >= n_knot: the compiled knot capacity); the LDS table and its limits are those
- * of the function without inputs.  A source that calls smc_input is compiled only for a model with inputs: without them the
- * compilation stops with "smc_input: this model has no inputs".  smc_loglik, smc_mh_step_*, early rejection, the cost hint,
- * smc_user_predict and the BDF counters work as for every user model.
- * check5 / dump_source5: as check4 / dump_source4 with noise = 0 (the sigma rule: the source of smc_set_model_user3), 1 (a noise
- * model) or 2 (with a proportional part) and the geometry the source is compiled for: n_cond, n_in and n_knot (n_in = 0: a model
- * without inputs; n_cond and n_knot are then not used).  dump_source5 also writes user_input.h.  No GPU needed.
- * DESIGNS: t_new == NULL (the data's design) uses the data's inputs.  An explicit design of smc_user_predict_at /
- * smc_user_predict_summary needs design inputs with the same n_ex_new, set beforehand by smc_user_set_design_inputs (in_t_new
- * n_ex_new x n_knot_new, in_u_new n_ex_new x n_knot_new x n_in, the rules above; no row may hold more finite knots than K) and
- * held until replaced; both pointers NULL clears them.  Without matching design inputs the call fails with the reason.  A design
- * that runs in groups of experiments carries each group's rows of the table. */
-#define SMC_USER_MAX_INPUTS 8
-#define SMC_USER_MAX_KNOTS 4096
 int smc_set_model_user5(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                         const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                         const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
                         int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot);
-int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n_in, int n_knot);
 int smc_user_model_check5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
                           char *log, int log_cap);
 int smc_user_model_dump_source5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, const char *dir);
-int smc_user_set_design_inputs(smc_ctx *ctx, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new);
-/* Scheduled events (doses, feed additions, washouts, resets): at known times the state changes by a jump and the integrator
- * stops there.  Each experiment e has a row of event times ev_t[e][0 .. n_ev) and per event n_val numbers
- * ev_v[e][j][0 .. n_val) (a dose amount, a target compartment, ...).  The source of a model with events defines one more
- * ingredient (a source that contains the name must define it) and may call smc_event_value from it:
- *     __device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond);   // y changed in place
- *     double smc_event_value(const double *cond, int j, int k);     // value k of event j of this experiment
- * cond is the handle to the experiment, as for smc_input, which smc_user_event may read too; smc_user_event always runs with
- * IEEE division, like smc_user_y0.
- * A solve of experiment e is the chain of solve_ivp calls a SciPy user would write.  With t0 = t[e][0] and t_end the row's last
- * finite time the events that fire are those with t0 < tau_j < t_end, in order; segment s is solve_ivp(f, (a, b), y, method,
- * t_eval = the row's data times in (a, b] (the first: [t0, b]), rtol, atol) with b the next firing event time or t_end; at an
- * event smc_user_event(j, tau_j, y, ...) is applied to the segment's end state and the next segment starts afresh from
- * (tau_j, y): RK45 with a new first derivative, select_initial_step over the new interval and no memory of a rejected step, BDF
- * at order 1 with a new Jacobian and the initial step rule.  A data time equal to tau_j sees the state before the event, the
- * next representable time after it the state after.  An event with tau_j >= t_end never fires; a segment may hold no data
- * time; rk_attempts counts step attempts only; a failed segment fails the solve as before (info bit 30, NaN from the stop on).
- * Event TIMES are data: they cannot depend on theta (amounts can, through smc_user_event), and there are no state-triggered
- * events.
- * Row rules: a row of ev_t is a strictly increasing finite run and then only NaN - it may have no event at all; every finite
- * event time is > t[e][0]; the values are finite at a row's finite events and ignored past them.  Anything else fails with the
- * row, the event and the rule.  smc_user_event_check applies these rules alone (no GPU, no context; the reason in
- * smc_last_error(NULL)).
- * smc_set_model_user6: the arguments of smc_set_model_user5, then ev_t (n_ex x n_ev), ev_v (n_ex x n_ev x n_val; NULL with
- * n_val == 0), n_ev <= SMC_USER_MAX_EVENTS, 0 <= n_val <= SMC_USER_MAX_EVENT_VALUES.  n_ev == 0 with both pointers NULL is
- * smc_set_model_user5, its path and its bits.  smc_user_model_check6 / smc_user_model_dump_source6: as the 5 functions plus the
- * geometry n_ev, n_val the source is compiled for; a source that defines or calls the event names compiles only for a model
- * with events ("smc_user_event: this model has no events"), and a model with events needs a source with smc_user_event.
- * smc_user_set_design_events: the events of an explicit design of smc_user_predict_at / smc_user_predict_summary (the what-if
- * dosing regimen; nothing is compiled again): n_ex_new rows of n_ev_new <= the model's n_ev events, held until replaced, both
- * pointers NULL clears them.  An explicit design on a model with events without design events of the same n_ex_new fails with
- * the reason; t_new == NULL uses the data's events. */
-#define SMC_USER_MAX_EVENTS 256
-#define SMC_USER_MAX_EVENT_VALUES 8
 int smc_set_model_user6(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                         const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                         const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
                         int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot,
                         const double *ev_t, const double *ev_v, int n_ev, int n_val);
-int smc_user_event_check(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val);
 int smc_user_model_check6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
                           int n_ev, int n_val, char *log, int log_cap);
 int smc_user_model_dump_source6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, int n_ev, int n_val, const char *dir);
-int smc_user_set_design_events(smc_ctx *ctx, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new);
-/* CENSORED OBSERVATIONS (additive; the functions above keep their behaviour): a value the assay could not quantify - below the
- * limit of quantification in a washout tail, above the upper limit at a peak - is neither dropped (NaN) nor taken for a
- * measurement of the limit, but contributes the probability of lying beyond it (Beal's M3).  censor: n_ex x n_t x n_obs flags
- * beside obs, 0: obs is the measured value (the term of the functions above); -1: left-censored, the true value is <= obs, which
- * holds the lower limit; +1: right-censored, the true value is >= obs, the upper limit.  With sd_ik as in smc_set_model_user4:
- *   logL = sum over quantified (e,i,k) [ -1/2 log(2 pi) - log sd_ik - (obs_ik - f_ik)^2 / (2 sd_ik^2) ] + sum over censored log Phi(z_ik),
- *   z_ik = (obs_ik - f_ik) / sd_ik  (left),   (f_ik - obs_ik) / sd_ik  (right);      any a_k <= 0 or b_k < 0: -inf.
- * user_models.censored_loglik is the definition in NumPy.  The kernels add x = -log Phi(z) >= 0 as
- *   z > 0:  -log1p(-erfc(z / sqrt 2) / 2),      z <= 0:  z^2 / 2 - log(erfcx(-z / sqrt 2) / 2)
- * - accurate in both tails, never negative - to the sums of smc_set_model_user4; a censored value's floor is 0 and m_e, m_ek count
- * quantified values only, so exact early rejection applies unchanged.
- * Rules: every flag is -1, 0 or +1; a nonzero flag stands on a finite value at a finite time of its row.  Anything else fails
- * with the row, the time, the output and the rule.  smc_user_censor_check applies these rules alone to t and obs that
- * smc_set_model_user3 accepts (no GPU, no context; the reason in smc_last_error(NULL)); c_n_ex, c_n_t, c_n_obs: the shape of
- * censor itself, which must be that of obs.
- * smc_set_model_user7: the arguments of smc_set_model_user6, then censor.  NULL or all zeros is smc_set_model_user6, its path
- * and its bits.  With a flag set the model is a noise model: add_index == NULL forms the equivalent specification - every
- * output at parameter dim - 1 under est_sigma, else fixed at sigma_fixed, obs_scale as given.  Limits, times and events
- * combine freely; a record of the LDS table holds the flags in its pad word (n_obs even) or grows by 16 bytes (n_obs odd), and a
- * table that no longer fits fails with the bytes needed and available.  smc_user_predict returns lk under this likelihood;
- * designs (smc_user_predict_at, smc_user_predict_summary) carry no observations and run as before.
- * check7 / dump_source7: as the 6 functions plus censor != 0: the source compiled with SMC_USER_CENSOR (it needs noise = 1 or 2);
- * dump_source7 then also writes user_censor.h.  With censor == 0 they are check6 / dump_source6. */
 int smc_set_model_user7(smc_ctx *ctx, const char *source, int n_states, int n_obs, const double *t, const double *obs,
                         const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
                         const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol, int method,
                         int est_sigma, double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot,
                         const double *ev_t, const double *ev_v, int n_ev, int n_val, const signed char *censor);
-int smc_user_censor_check(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs, int c_n_ex,
-                          int c_n_t, int c_n_obs);
 int smc_user_model_check7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
                           int n_ev, int n_val, int censor, char *log, int log_cap);
 int smc_user_model_dump_source7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,

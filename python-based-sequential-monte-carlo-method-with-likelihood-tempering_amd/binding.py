@@ -48,6 +48,31 @@ c_ip = ctypes.POINTER(ctypes.c_int)
 c_ctx = ctypes.c_void_p
 i64, f64, cint, u64 = ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_uint64
 
+
+class UserSourceSpec(ctypes.Structure):
+    """smc_user_source_spec (include/smc_hip.h): what decides the text of a user model's run-time compiled kernel.  Fields not
+    given are zero, i.e. the feature is absent; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("source", ctypes.c_char_p), ("n_states", cint), ("dim", cint), ("method", cint),
+                ("n_obs", cint), ("noise", cint), ("n_cond", cint), ("n_in", cint), ("n_knot", cint), ("n_ev", cint), ("n_val", cint),
+                ("censor", cint)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **fields)
+
+
+class UserModelSpec(ctypes.Structure):
+    """smc_user_model_spec (include/smc_hip.h): a user model by named fields.  The struct holds pointers only: whoever fills it
+    keeps the arrays alive until smc_set_model_user_spec has returned."""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("source", ctypes.c_char_p), ("n_states", cint), ("method", cint), ("n_obs", cint),
+                ("t", c_dp), ("obs", c_dp), ("cond", c_dp), ("obs_scale", c_dp), ("n_ex", cint), ("n_t", cint), ("n_cond", cint),
+                ("est_sigma", cint), ("sigma_fixed", f64), ("add_index", c_ip), ("add_fixed", c_dp), ("prop_index", c_ip),
+                ("prop_fixed", c_dp), ("rtol", f64), ("atol", f64), ("in_t", c_dp), ("in_u", c_dp), ("n_in", cint), ("n_knot", cint),
+                ("ev_t", c_dp), ("ev_v", c_dp), ("n_ev", cint), ("n_val", cint), ("censor", c_i8p)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **fields)
+
+
 # name -> (restype, argtypes); one entry per function of include/smc_hip.h
 SIGNATURES = {
     "smc_abi_version": (cint, []),
@@ -61,6 +86,11 @@ SIGNATURES = {
     "smc_set_model_user": (cint, [c_ctx, ctypes.c_char_p, cint, c_dp, c_dp, c_dp, cint, cint, cint, cint, f64, f64, f64]),
     "smc_user_model_check": (cint, [ctypes.c_char_p, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source": (cint, [ctypes.c_char_p, cint, cint, ctypes.c_char_p]),
+    "smc_set_model_user_spec": (cint, [c_ctx, ctypes.POINTER(UserModelSpec)]),
+    "smc_user_model_check_spec": (cint, [ctypes.POINTER(UserSourceSpec), ctypes.c_char_p, cint]),
+    "smc_user_model_dump_source_spec": (cint, [ctypes.POINTER(UserSourceSpec), ctypes.c_char_p]),
+    "smc_user_spec_layout": (cint, [cint, c_ip, cint]),
+    # the earlier, positional entry points: tests and tools call them through lib()
     "smc_set_model_user2": (cint, [c_ctx, ctypes.c_char_p, cint, c_dp, c_dp, c_dp, cint, cint, cint, cint, f64, f64, f64, cint]),
     "smc_user_model_check2": (cint, [ctypes.c_char_p, cint, cint, cint, ctypes.c_char_p, cint]),
     "smc_user_model_dump_source2": (cint, [ctypes.c_char_p, cint, cint, cint, ctypes.c_char_p]),

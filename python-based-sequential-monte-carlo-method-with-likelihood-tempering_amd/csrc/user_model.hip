@@ -177,7 +177,6 @@ user_bdf_count_kernel(const uint8_t *__restrict__ p0mask, const unsigned *__rest
 struct UserInputGeom {
     int n_cond = 0, n_in = 0, kcap = 0;
     int n_ev = 0, n_val = 0;
-    int censor = 0;      // 1: censored observations (user_censor.h) - SMC_USER_CENSOR, records with a flag word; no part of a cond row
     int in_words() const { return n_in > 0 ? n_cond + kcap + n_in * (2 * kcap + 1) : n_cond; }      // = the offset of the event table
     int ev_words() const { return n_ev > 0 ? n_ev + 1 + n_ev * n_val : 0; }
     int row_words() const { return in_words() + ev_words(); }
@@ -198,6 +197,15 @@ static int knot_capacity(int n_knot) {
     while (k < n_knot) k <<= 1;
     return k;
 }
+// Everything that decides the text hiprtc reads for a source (build_source, user_headers): smc_user_source_spec (include/smc_hip.h)
+// after user_source_spec_of has accepted it, n_knot as the knot capacity of geom.  n_obs = 0: the one-output source of
+// smc_set_model_user / 2; n_obs >= 1: the multi-output source.  noise: 0 the sigma rule, 1 a noise model, 2 with its proportional
+// part; censor: 1 censored observations (user_censor.h) - SMC_USER_CENSOR, records with a flag word.
+struct UserSourceSpec {
+    int n_states = 0, dim = 0, method = SMC_USER_METHOD_RK45, n_obs = 0;
+    int noise = 0, censor = 0;
+    UserInputGeom geom{};
+};
 
 struct UserModel {
     hipModule_t module = nullptr;
@@ -209,10 +217,9 @@ struct UserModel {
     int parity = 0;
     double *d_t = nullptr, *d_obs = nullptr, *d_cond = nullptr, *d_sum = nullptr;
     int *d_info = nullptr;
-    int n_ex = 0, n_t = 0, n_cond = 0, n_states = 0, est_sigma = 1;
+    int n_ex = 0, n_t = 0, n_cond = 0, est_sigma = 1;
     int blocks_per_cu = 4;   // persistent blocks (4 waves each) per CU: what the compiled kernel's registers and LDS allow
     double sigma_fixed = 0, rtol = 1e-3, atol = 1e-6;
-    int method = SMC_USER_METHOD_RK45;
     unsigned *d_bdf_counts = nullptr;          // BDF: per item {accepted steps, Newton iterations, LU factorisations, Jacobians}
     unsigned long long *d_bdf_totals = nullptr;   // ... their sums over the last sweep (user_bdf_count_kernel)
     double *d_const = nullptr;            // [2 n_ex]: m_e, then sum log s_k (user_finish_kernel); n_t and 0 for a one-output model
@@ -236,13 +243,13 @@ struct UserModel {
     bool noise = false;
     UserNoise nz{};
     // smc_set_model_user5: time-varying inputs (user_input.h).  The table lies behind each experiment's cond row, so d_cond holds
-    // rows of geom.row_words() doubles; h_rows keeps the data's rows and design_* the inputs of an explicit design
+    // rows of spec.geom.row_words() doubles; h_rows keeps the data's rows and design_* the inputs of an explicit design
     // smc_set_model_user6: scheduled events (user_event.h).  Their table follows in the same rows; design_ev_* are the events of
     // an explicit design (smc_user_set_design_events)
-    UserInputGeom geom{};
+    UserSourceSpec spec{};      // what the module was compiled for: n_states, method, the row geometry, ...
     std::vector<double> h_rows, design_t, design_u, design_ev_t, design_ev_v;
     int design_n_ex = 0, design_n_knot = 0, design_ev_n_ex = 0, design_ev_n_ev = 0;
-    int cond_stride() const { return geom.tabled() ? geom.row_words() : n_cond; }
+    int cond_stride() const { return spec.geom.tabled() ? spec.geom.row_words() : n_cond; }
 };
 
 // an optional ingredient (smc_user_cost, smc_user_jac, smc_user_obs_vec; smc_div): a source that mentions it must define it
@@ -257,9 +264,10 @@ static bool mentions(const char *user_source, const char *name) { return strstr(
 // geom.n_ev > 0 (smc_set_model_user6): SMC_USER_EVENTS, SMC_USER_EVAT / NEV / NVAL and user_event.h in front, smc_event_value made
 // visible to the user's text, and the kernel file with its SMC_USER_EVENTS blocks (k_..._ev).  The event names and a model
 // without events, or events and a source without smc_user_event, stop with an #error that says so.
-static std::string build_source(const char *user_source, int n_states, int dim, int method, int n_obs, int noise = 0,
-                                const UserInputGeom &geom = UserInputGeom()) {
-    const bool bdf = method == SMC_USER_METHOD_BDF;
+static std::string build_source(const char *user_source, const UserSourceSpec &sp) {
+    const UserInputGeom &geom = sp.geom;
+    const int n_obs = sp.n_obs, noise = sp.noise;
+    const bool bdf = sp.method == SMC_USER_METHOD_BDF;
     std::string s;
     if (geom.n_in > 0)
         s = "#define SMC_USER_NCOND " + std::to_string(geom.n_cond) + "\n#define SMC_USER_NIN " + std::to_string(geom.n_in) +
@@ -275,13 +283,13 @@ static std::string build_source(const char *user_source, int n_states, int dim, 
     } else if (mentions(user_source, "smc_user_event") || mentions(user_source, "smc_event_value")) {
         s += "#error \"smc_user_event: this model has no events (n_ev = 0) - set it with ev_t / ev_v through smc_set_model_user6\"\n";
     }
-    s += "#define SMC_USER_NS " + std::to_string(n_states) + "\n#define SMC_USER_DIM " + std::to_string(dim) + "\n";
+    s += "#define SMC_USER_NS " + std::to_string(sp.n_states) + "\n#define SMC_USER_DIM " + std::to_string(sp.dim) + "\n";
     if (n_obs > 0)
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
              ((n_obs > 1 || mentions(user_source, "smc_user_obs_vec")) ? "1\n" : "0\n");
     // smc_set_model_user4: the SMC_USER_NOISE blocks of the kernel files and of user_obs_args.h (noise = 2: with log1p and the division)
     // smc_set_model_user7: SMC_USER_CENSOR, user_censor.h in front and user_obs_args.h with its SMC_USER_CENSOR blocks (a noise model always)
-    if (n_obs > 0 && noise > 0 && geom.censor) s += "#define SMC_USER_CENSOR 1\n#include \"user_censor.h\"\n";
+    if (n_obs > 0 && noise > 0 && sp.censor) s += "#define SMC_USER_CENSOR 1\n#include \"user_censor.h\"\n";
     if (n_obs > 0 && noise > 0) s += std::string("#define SMC_USER_NOISE 1\n#define SMC_USER_NOISE_PROP ") + (noise > 1 ? "1\n" : "0\n");
     if (mentions(user_source, "smc_user_cost")) s += "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n";
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
@@ -305,26 +313,26 @@ constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
 // user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs, user_event.h with one that
 // has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks -, user_censor.h with one that has censored observations
 // - and user_obs_args.h then with its SMC_USER_CENSOR blocks
-static int user_headers(int n_obs, const UserInputGeom &geom, const char **texts, const char **names) {
+static int user_headers(const UserSourceSpec &sp, const char **texts, const char **names) {
+    const UserInputGeom &geom = sp.geom;
     int n = 0;
     for (const auto &h : kUserHeaders) {
-        if ((h.text == k_user_obs_args_h && n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
-            (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !geom.censor))
+        if ((h.text == k_user_obs_args_h && sp.n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
+            (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !sp.censor))
             continue;
         texts[n] = (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev
-                   : (h.text == k_user_obs_args_h && geom.censor) ? k_user_obs_args_h_cn : h.text;
+                   : (h.text == k_user_obs_args_h && sp.censor) ? k_user_obs_args_h_cn : h.text;
         names[n++] = h.name;
     }
     return n;
 }
 
 // compile build_source(...) for gfx950; on failure `log` holds hiprtc's diagnostics
-static bool compile_user(const char *user_source, int n_states, int dim, int method, int n_obs, std::vector<char> &code,
-                         std::string &log, int noise = 0, const UserInputGeom &geom = UserInputGeom()) {
-    const std::string src = build_source(user_source, n_states, dim, method, n_obs, noise, geom);
+static bool compile_user(const char *user_source, const UserSourceSpec &sp, std::vector<char> &code, std::string &log) {
+    const std::string src = build_source(user_source, sp);
     hiprtcProgram prog;
     const char *headers[kUserHeaderCount], *names[kUserHeaderCount];
-    const int n_headers = user_headers(n_obs, geom, headers, names);
+    const int n_headers = user_headers(sp, headers, names);
     if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", n_headers, headers, names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return false;
@@ -419,7 +427,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const bool multi = u->multi || pred;
-    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->geom.censor != 0) : user_lds_bytes(u->n_states, u->n_ex, u->n_t));
+    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->spec.censor != 0) : user_lds_bytes(u->spec.n_states, u->n_ex, u->n_t));
     if (lists) {
         u->parity ^= 1;
         UserScanArgs sa{};
@@ -466,7 +474,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     void *args1[] = {&a, &u->d_bdf_counts};     // the RK45 kernel takes the first only
     void *args3[] = {&a, &o};                   // multi-output kernels: RK45 ...
     void *args3b[] = {&a, &u->d_bdf_counts, &o};   // ... and BDF
-    void **args = !multi ? args1 : (u->method == SMC_USER_METHOD_BDF ? args3b : args3);
+    void **args = !multi ? args1 : (u->spec.method == SMC_USER_METHOD_BDF ? args3b : args3);
     {
         ScopedTimer tm(c, SMC_T_SOLVE);
         (void)hipMemsetAsync(c->d_queue, 0, sizeof(unsigned long long), c->stream);
@@ -485,7 +493,7 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
         hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
                            c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
                            lk, c->d_counters);
-    if (u->method == SMC_USER_METHOD_BDF) {
+    if (u->spec.method == SMC_USER_METHOD_BDF) {
         if (!pred) (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
         const int64_t items = n * u->n_ex, gb = (items + 255) / 256;
         hipLaunchKernelGGL(user_bdf_count_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0, c->stream, p0mask, u->d_bdf_counts,
@@ -616,7 +624,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
 
 // occupancy and LDS limit of the prediction kernel (u->fn_pred)
 static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
-    const size_t lds = user_lds_bytes3(u->n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->geom.censor != 0);
+    const size_t lds = user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->spec.censor != 0);
     int nb = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu_pred = nb;
     if (lds > 48 * 1024 &&
@@ -645,12 +653,12 @@ struct DesignItems {
     }
 };
 static size_t design_item_bytes(const UserModel *u) {      // per (experiment, particle)
-    return sizeof(double) + sizeof(int) + (u->method == SMC_USER_METHOD_BDF ? 4 * sizeof(unsigned) : 0);
+    return sizeof(double) + sizeof(int) + (u->spec.method == SMC_USER_METHOD_BDF ? 4 * sizeof(unsigned) : 0);
 }
 static bool design_items_alloc(const UserModel *u, DesignItems &it, int64_t n, int g) {
     const size_t items = (size_t)n * g;
     return hipMalloc(&it.d_sum, items * sizeof(double)) == hipSuccess && hipMalloc(&it.d_info, items * sizeof(int)) == hipSuccess &&
-           (u->method != SMC_USER_METHOD_BDF || hipMalloc(&it.d_bdf_counts, 4 * items * sizeof(unsigned)) == hipSuccess);
+           (u->spec.method != SMC_USER_METHOD_BDF || hipMalloc(&it.d_bdf_counts, 4 * items * sizeof(unsigned)) == hipSuccess);
 }
 
 struct DesignGroup {
@@ -670,7 +678,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
     std::vector<double> me, ls;
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
     const std::vector<double> img = build_obs_image(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls,
-                                                    u->noise ? &u->nz : nullptr, u->geom.censor != 0);      // no flag set
+                                                    u->noise ? &u->nz : nullptr, u->spec.censor != 0);      // no flag set
     const int cs = u->cond_stride();      // a model with inputs or events: cond holds whole rows, the tables included
     const size_t nc = (size_t)g * (cs > 0 ? cs : 1) * sizeof(double);
     dg.e0 = e0;
@@ -683,7 +691,7 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
               hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && cs > 0)
         ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * cs, nc, hipMemcpyHostToDevice) == hipSuccess;
-    const size_t lds = user_lds_bytes3(u->n_states, g, n_t, u->n_obs, u->noise, u->geom.censor != 0);
+    const size_t lds = user_lds_bytes3(u->spec.n_states, g, n_t, u->n_obs, u->noise, u->spec.censor != 0);
     int nb = 0;
     if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
     (void)c;
@@ -715,16 +723,22 @@ struct DesignScope {
 // the largest run of experiments whose image fits the LDS cap (0: not even one row)
 static int design_lds_group(const UserModel *u, int n_ex, int n_t) {
     int g = 0;
-    while (g < n_ex && user_lds_bytes3(u->n_states, g + 1, n_t, u->n_obs, u->noise, u->geom.censor != 0) <= kUserLdsCap) ++g;
+    while (g < n_ex && user_lds_bytes3(u->spec.n_states, g + 1, n_t, u->n_obs, u->noise, u->spec.censor != 0) <= kUserLdsCap) ++g;
     return g;
 }
 
+// the source of the prediction kernel of a one-output model: the multi-output source with one output under the sigma rule
+static UserSourceSpec pred_source_spec(const UserModel *u) {
+    UserSourceSpec sp = u->spec;
+    sp.n_obs = 1;
+    return sp;
+}
 // the prediction kernel of the model: part of a multi-output module, else compiled at the first call that needs it
 static int ensure_pred_kernel(smc_ctx *c, UserModel *u, const char *who) {
     if (u->fn_pred) return 0;
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg, 0, u->geom))
+    if (!compile_user(u->source.c_str(), pred_source_spec(u), code, lg))
         return smc_fail(c, (std::string(who) + ": the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
     if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
         hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
@@ -732,7 +746,7 @@ static int ensure_pred_kernel(smc_ctx *c, UserModel *u, const char *who) {
         return smc_fail(c, (std::string(who) + ": loading the prediction module failed").c_str());
     }
     // the data's own image may be one the kernel cannot hold (smc_user_predict refuses it): then only designs are predicted
-    if (user_lds_bytes3(u->n_states, u->n_ex, u->n_t, 1) <= kUserLdsCap && prepare_pred_kernel(c, u) != 0) {
+    if (user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, 1) <= kUserLdsCap && prepare_pred_kernel(c, u) != 0) {
         u->fn_pred = nullptr;
         return 1;
     }
@@ -754,19 +768,44 @@ extern "C" {
 static bool user_method_ok(int method) { return method == SMC_USER_METHOD_RK45 || method == SMC_USER_METHOD_BDF; }
 static bool user_obs_ok(int n_obs) { return n_obs >= 1 && n_obs <= SMC_USER_MAX_OBS; }
 
-// The exported check and dump functions: one implementation each.  n_obs = 0: the one-output source (build_source); the
-// functions that take an n_obs pass -1 for one that is out of range, which is refused here like every other bad argument.
-static bool user_source_args_ok(const char *source, int n_states, int dim, int method, int n_obs) {
-    return source && n_states >= 1 && n_states <= SMC_USER_MAX_STATES && dim >= 1 && dim <= SMC_MAX_DIM && user_method_ok(method) &&
-           (n_obs == 0 || user_obs_ok(n_obs));
+// A spec struct as its caller knows it: the first min(struct_size, sizeof) bytes over zeros, so that a field a later feature
+// appends reads as absent for an older caller.  False (the functions return 2 or fail) for a struct_size that ends before
+// `required` bytes (the offset of the first field that may be left out) or exceeds the library's own struct.
+static bool user_spec_copy(const void *in, size_t required, void *out, size_t size) {
+    size_t n = 0;      // struct_size, the first field of both structs
+    memset(out, 0, size);
+    if (in) memcpy(&n, in, sizeof n);
+    if (n < required || n > size) return false;
+    memcpy(out, in, n);
+    return true;
 }
 
-static int user_model_check_impl(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap, int noise = 0,
-                                 const UserInputGeom &geom = UserInputGeom()) {
-    if (!user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
+// The one validator of check and dump: the source spec as what build_source reads, false for arguments that are refused
+// (return 2).  n_obs = 0, the one-output source, goes with no feature; n_in = 0: a model without inputs (n_knot is then not used),
+// n_ev = 0: one without events; censored observations need a noise model's source.
+static bool user_source_spec_of(const smc_user_source_spec *in, smc_user_source_spec &s, UserSourceSpec &sp) {
+    if (!user_spec_copy(in, offsetof(smc_user_source_spec, noise), &s, sizeof s)) return false;
+    if (!s.source || s.n_states < 1 || s.n_states > SMC_USER_MAX_STATES || s.dim < 1 || s.dim > SMC_MAX_DIM || !user_method_ok(s.method)) return false;
+    if (s.n_obs == 0 ? (s.noise || s.n_in || s.n_ev || s.censor) : !user_obs_ok(s.n_obs)) return false;
+    if (s.noise < 0 || s.noise > 2 || s.n_cond < 0 || s.n_in < 0 || s.n_in > SMC_USER_MAX_INPUTS) return false;
+    if (s.n_in > 0 && (s.n_knot < 1 || s.n_knot > SMC_USER_MAX_KNOTS)) return false;
+    if (s.n_ev < 0 || s.n_ev > SMC_USER_MAX_EVENTS || s.n_val < 0 || s.n_val > SMC_USER_MAX_EVENT_VALUES) return false;
+    if (s.censor != 0 && s.noise == 0) return false;
+    sp.n_states = s.n_states, sp.dim = s.dim, sp.method = s.method, sp.n_obs = s.n_obs;
+    sp.noise = s.noise, sp.censor = s.censor != 0 ? 1 : 0;
+    sp.geom.n_cond = s.n_cond;
+    if (s.n_in > 0) sp.geom.n_in = s.n_in, sp.geom.kcap = knot_capacity(s.n_knot);
+    if (s.n_ev > 0) sp.geom.n_ev = s.n_ev, sp.geom.n_val = s.n_val;
+    return true;
+}
+
+int smc_user_model_check_spec(const smc_user_source_spec *spec, char *log, int log_cap) {
+    smc_user_source_spec s;
+    UserSourceSpec sp;
+    if (!user_source_spec_of(spec, s, sp)) return 2;
     std::vector<char> code;
     std::string lg;
-    const bool ok = compile_user(source, n_states, dim, method, n_obs, code, lg, noise, geom);
+    const bool ok = compile_user(s.source, sp, code, lg);
     if (log && log_cap > 0) {
         strncpy(log, lg.c_str(), (size_t)log_cap - 1);
         log[log_cap - 1] = 0;
@@ -774,72 +813,14 @@ static int user_model_check_impl(const char *source, int n_states, int dim, int 
     return ok ? 0 : 1;
 }
 
-int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap) {
-    return user_model_check_impl(source, n_states, dim, SMC_USER_METHOD_RK45, 0, log, log_cap);
-}
-int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap) {
-    return user_model_check_impl(source, n_states, dim, method, 0, log, log_cap);
-}
-int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap) {
-    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap);
-}
-int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap) {
-    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, proportional ? 2 : 1);
-}
-// the geometry of check5 / dump_source5: false for arguments that are refused (return 2); n_in = 0 is a model without inputs
-static bool user_geom_of(int noise, int n_cond, int n_in, int n_knot, UserInputGeom &geom) {
-    if (noise < 0 || noise > 2 || n_cond < 0 || n_in < 0 || n_in > SMC_USER_MAX_INPUTS) return false;
-    if (n_in == 0) return true;
-    if (n_knot < 1 || n_knot > SMC_USER_MAX_KNOTS) return false;
-    geom.n_cond = n_cond;
-    geom.n_in = n_in;
-    geom.kcap = knot_capacity(n_knot);
-    return true;
-}
-int smc_user_model_check5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
-                          char *log, int log_cap) {
-    UserInputGeom geom;
-    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
-    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
-}
-// ... and of check6 / dump_source6: n_ev = 0 is a model without events, whose geometry is check5's
-static bool user_geom_of6(int noise, int n_cond, int n_in, int n_knot, int n_ev, int n_val, UserInputGeom &geom) {
-    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return false;
-    if (n_ev < 0 || n_ev > SMC_USER_MAX_EVENTS || n_val < 0 || n_val > SMC_USER_MAX_EVENT_VALUES) return false;
-    if (n_ev == 0) return true;
-    geom.n_cond = n_cond;
-    geom.n_ev = n_ev;
-    geom.n_val = n_val;
-    return true;
-}
-int smc_user_model_check6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
-                          int n_ev, int n_val, char *log, int log_cap) {
-    UserInputGeom geom;
-    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
-    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
-}
-// ... and of check7 / dump_source7: censor = 0 is a model without censored observations, whose geometry is check6's; with it
-// the source is a noise model's (noise = 1 or 2)
-static bool user_geom_of7(int noise, int n_cond, int n_in, int n_knot, int n_ev, int n_val, int censor, UserInputGeom &geom) {
-    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return false;
-    if (censor != 0 && noise == 0) return false;
-    geom.censor = censor != 0 ? 1 : 0;
-    return true;
-}
-int smc_user_model_check7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
-                          int n_ev, int n_val, int censor, char *log, int log_cap) {
-    UserInputGeom geom;
-    if (!user_geom_of7(noise, n_cond, n_in, n_knot, n_ev, n_val, censor, geom)) return 2;
-    return user_model_check_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, log, log_cap, noise, geom);
-}
-
 // everything hiprtc would read, as files: `hipcc -I <dir>` compiles <dir>/smc_user_model.hip off line
-static int user_model_dump_impl(const char *source, int n_states, int dim, int method, int n_obs, const char *dir, int noise = 0,
-                                const UserInputGeom &geom = UserInputGeom()) {
-    if (!dir || !user_source_args_ok(source, n_states, dim, method, n_obs)) return 2;
-    const std::string src = build_source(source, n_states, dim, method, n_obs, noise, geom);
+int smc_user_model_dump_source_spec(const smc_user_source_spec *spec, const char *dir) {
+    smc_user_source_spec s;
+    UserSourceSpec sp;
+    if (!dir || !user_source_spec_of(spec, s, sp)) return 2;
+    const std::string src = build_source(s.source, sp);
     const char *texts[kUserHeaderCount], *names[kUserHeaderCount];
-    const int n_headers = user_headers(n_obs, geom, texts, names);
+    const int n_headers = user_headers(sp, texts, names);
     for (int i = -1; i < n_headers; ++i) {
         FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : names[i])).c_str(), "w");
         if (!f) return 1;
@@ -849,35 +830,65 @@ static int user_model_dump_impl(const char *source, int n_states, int dim, int m
     return 0;
 }
 
+// The earlier entry points: each fills the fields it knows, in the struct's order, and leaves the rest zero.  Those that take an
+// n_obs never meant the one-output source by it: one out of range is passed on as -1, which the validator refuses.
+static int obs_or_bad(int n_obs) { return user_obs_ok(n_obs) ? n_obs : -1; }
+static int user_check(const smc_user_source_spec &s, char *log, int log_cap) { return smc_user_model_check_spec(&s, log, log_cap); }
+static int user_dump(const smc_user_source_spec &s, const char *dir) { return smc_user_model_dump_source_spec(&s, dir); }
+int smc_user_model_check(const char *source, int n_states, int dim, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, SMC_USER_METHOD_RK45}, log, log_cap);
+}
+int smc_user_model_check2(const char *source, int n_states, int dim, int method, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method}, log, log_cap);
+}
+int smc_user_model_check3(const char *source, int n_states, int dim, int method, int n_obs, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs)}, log, log_cap);
+}
+int smc_user_model_check4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs),
+                       proportional ? 2 : 1}, log, log_cap);
+}
+int smc_user_model_check5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in,
+                       n_knot}, log, log_cap);
+}
+int smc_user_model_check6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in, n_knot,
+                       n_ev, n_val}, log, log_cap);
+}
+int smc_user_model_check7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in, int n_knot,
+                          int n_ev, int n_val, int censor, char *log, int log_cap) {
+    return user_check({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in, n_knot,
+                       n_ev, n_val, censor}, log, log_cap);
+}
 int smc_user_model_dump_source(const char *source, int n_states, int dim, const char *dir) {
-    return user_model_dump_impl(source, n_states, dim, SMC_USER_METHOD_RK45, 0, dir);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, SMC_USER_METHOD_RK45}, dir);
 }
 int smc_user_model_dump_source2(const char *source, int n_states, int dim, int method, const char *dir) {
-    return user_model_dump_impl(source, n_states, dim, method, 0, dir);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method}, dir);
 }
 int smc_user_model_dump_source3(const char *source, int n_states, int dim, int method, int n_obs, const char *dir) {
-    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs)}, dir);
 }
 int smc_user_model_dump_source4(const char *source, int n_states, int dim, int method, int n_obs, int proportional, const char *dir) {
-    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, proportional ? 2 : 1);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), proportional ? 2 : 1}, dir);
 }
 int smc_user_model_dump_source5(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, const char *dir) {
-    UserInputGeom geom;
-    if (!user_geom_of(noise, n_cond, n_in, n_knot, geom)) return 2;
-    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in,
+                      n_knot}, dir);
 }
 int smc_user_model_dump_source6(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, int n_ev, int n_val, const char *dir) {
-    UserInputGeom geom;
-    if (!user_geom_of6(noise, n_cond, n_in, n_knot, n_ev, n_val, geom)) return 2;
-    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in, n_knot,
+                      n_ev, n_val}, dir);
 }
 int smc_user_model_dump_source7(const char *source, int n_states, int dim, int method, int n_obs, int noise, int n_cond, int n_in,
                                 int n_knot, int n_ev, int n_val, int censor, const char *dir) {
-    UserInputGeom geom;
-    if (!user_geom_of7(noise, n_cond, n_in, n_knot, n_ev, n_val, censor, geom)) return 2;
-    return user_model_dump_impl(source, n_states, dim, method, user_obs_ok(n_obs) ? n_obs : -1, dir, noise, geom);
+    return user_dump({sizeof(smc_user_source_spec), source, n_states, dim, method, obs_or_bad(n_obs), noise, n_cond, n_in, n_knot,
+                      n_ev, n_val, censor}, dir);
 }
 
 // the rules of the flags of censored observations (include/smc_hip.h: smc_set_model_user7; user_models.censor_layout is the same
@@ -1057,17 +1068,98 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
     return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_noise_check: " + bad).c_str());
 }
 
-// The models of all three set functions.  multi: smc_set_model_user3 (obs n_ex x n_t x n_obs, validated, the multi-output
-// source); else the one-output source and data exactly as before, plus the image for a later smc_user_predict when the data
-// allows one.
-static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs,
-                               const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma,
-                               double sigma_fixed, double rtol, double atol, int method, bool multi, const UserNoise *nz = nullptr,
-                               const UserInputs *in = nullptr, const UserEvents *ev = nullptr, const signed char *censor = nullptr) {
-    // censor: flags with at least one set (smc_set_model_user7 has checked them against t and obs); only with a noise model
+// What the device part needs of a smc_user_model_spec: user_model_plan forms it, the one place where the rules live by which an
+// absent feature takes the earlier path, and its bits with it.
+struct UserModelPlan {
+    bool multi = false;      // the multi-output source and data (n_obs >= 1); else the one-output model of smc_set_model_user / 2
+    int n_obs = 1;
+    bool noise = false;      // the noise path (nz), else the sigma rule (est_sigma, sigma_fixed)
+    UserNoise nz{};
+    int est_sigma = 1;
+    double sigma_fixed = 0.0;
+    bool in = false, ev = false;      // inputs, events: the spec's in_* and ev_* fields
+    const signed char *censor = nullptr;      // flags with at least one set, which censor_layout_error has accepted
+};
+
+// The spec as a plan, or the failure.  Messages about the arguments' consistency carry `who`, the called function; who == nullptr:
+// a numbered entry point, and they carry the name of the newest feature its arguments use, as its chain of predecessors did.
+static int user_model_plan(smc_ctx *c, const smc_user_model_spec &s, const char *who, UserModelPlan &p) {
+    const size_t n_flags = (s.censor && s.n_ex >= 1 && s.n_t >= 1 && user_obs_ok(s.n_obs)) ? (size_t)s.n_ex * s.n_t * s.n_obs : 0;
+    const bool censored = std::any_of(s.censor, s.censor + n_flags, [](signed char f) { return f != 0; });
+    const bool inputs = s.n_in != 0, events = s.n_ev != 0;
+    const std::string gen = censored ? "smc_set_model_user7" : events ? "smc_set_model_user6" : "smc_set_model_user5";
+    const std::string me = who ? who : gen;
+    if (s.n_obs == 0) {      // the one-output model: none of the later features
+        if (s.obs_scale || s.add_index || s.add_fixed || s.prop_index || s.prop_fixed || inputs || s.in_t || s.in_u || events || s.ev_t || s.ev_v || s.censor)
+            return smc_fail(c, (me + ": n_obs = 0 (the one-output model) with obs_scale, a noise model, inputs, events or censor given").c_str());
+        p.est_sigma = s.est_sigma, p.sigma_fixed = s.sigma_fixed;
+        return 0;
+    }
+    p.multi = true;
+    p.n_obs = s.n_obs;
+    if (censored) {      // the data's own rules first (the flags' rules assume them), then the flags'
+        std::vector<double> m, l;
+        std::string bad = (s.t && s.obs) ? obs_layout(s.t, s.obs, s.obs_scale, s.n_ex, s.n_t, s.n_obs, m, l) : std::string("NULL t or obs");
+        if (bad.empty()) bad = censor_layout_error(s.t, s.obs, s.censor, s.n_ex, s.n_t, s.n_obs, s.n_ex, s.n_t, s.n_obs);
+        if (!bad.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad).c_str());
+        p.censor = s.censor;
+    }
+    if (!events && (s.ev_t || s.ev_v))
+        return smc_fail(c, ((who ? who : censored ? gen : "smc_set_model_user6") + std::string(": n_ev = 0 with ev_t or ev_v given (both must be NULL)")).c_str());
+    if (!inputs && (s.in_t || s.in_u)) return smc_fail(c, (me + ": n_in = 0 with in_t or in_u given (both must be NULL)").c_str());
+    p.in = inputs, p.ev = events;
+    const int *add_index = s.add_index;
+    const double *add_fixed = s.add_fixed;
+    int sigma_index[kUserMaxObs];
+    double sigma_value[kUserMaxObs];
+    if (!add_index) {      // the sigma rule; under censoring as the equivalent noise specification
+        if (s.add_fixed || s.prop_index || s.prop_fixed)
+            return smc_fail(c, (me + ": add_index is NULL (the sigma rule) and another part of a noise model is given").c_str());
+        p.est_sigma = s.est_sigma, p.sigma_fixed = s.sigma_fixed;
+        if (!censored) return 0;
+        if (!s.est_sigma && !(std::isfinite(s.sigma_fixed) && s.sigma_fixed > 0.0)) return smc_fail(c, (me + ": sigma_fixed must be finite and > 0").c_str());
+        std::fill_n(sigma_index, kUserMaxObs, s.est_sigma ? c->dim - 1 : -1);
+        std::fill_n(sigma_value, kUserMaxObs, s.est_sigma ? 0.0 : s.sigma_fixed);
+        add_index = sigma_index, add_fixed = sigma_value;
+    }
+    const std::string bad = noise_spec_error(s.n_obs, c->dim, add_index, add_fixed, s.prop_index, s.prop_fixed);
+    if (!bad.empty()) return smc_fail(c, ((who ? who : censored || events ? gen : inputs ? "smc_set_model_user5" : "smc_set_model_user4") + (": " + bad)).c_str());
+    if (!s.prop_index && !censored) {      // one sigma for every output: the sigma rule's path and its bits
+        bool last = true, fixed = true;
+        for (int k = 0; k < s.n_obs; ++k) {
+            last = last && add_index[k] == c->dim - 1;
+            fixed = fixed && add_index[k] == -1 && add_fixed[k] == add_fixed[0];
+        }
+        p.est_sigma = last ? 1 : 0, p.sigma_fixed = last ? 0.0 : add_fixed[0];
+        if (last || fixed) return 0;
+    }
+    p.noise = true;
+    p.est_sigma = 0, p.sigma_fixed = 1.0;
+    for (int k = 0; k < kUserMaxObs; ++k) {
+        p.nz.add_index[k] = k < s.n_obs ? add_index[k] : -1;
+        p.nz.add_fixed[k] = (k < s.n_obs && add_index[k] < 0) ? add_fixed[k] : 1.0;
+        p.nz.prop_index[k] = (k < s.n_obs && s.prop_index) ? s.prop_index[k] : -1;
+        p.nz.prop_fixed[k] = (k < s.n_obs && s.prop_index && s.prop_index[k] < 0) ? s.prop_fixed[k] : 0.0;
+        p.nz.scale[k] = (k < s.n_obs && s.obs_scale) ? s.obs_scale[k] : 1.0;
+    }
+    p.nz.prop = s.prop_index ? 1 : 0;
+    return 0;
+}
+
+// Every set function: the spec as its caller gave it (user_spec_copy has applied struct_size), planned, checked against the
+// kernel's limits and brought to the device.
+static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const char *who) {
     if (!c) return smc_fail(nullptr, "NULL context");
-    if (!source) return smc_fail(c, "smc_set_model_user: NULL source");
-    if (censor && !(nz && multi)) return smc_fail(c, "smc_set_model_user7: censored observations need a noise model");
+    UserModelPlan plan;
+    if (user_model_plan(c, s, who, plan) != 0) return 1;
+    const double *t = s.t, *obs = s.obs, *cond = s.cond, *obs_scale = s.obs_scale;
+    const int n_states = s.n_states, n_obs = plan.n_obs, n_ex = s.n_ex, n_t = s.n_t, n_cond = s.n_cond, method = s.method;
+    const bool multi = plan.multi;
+    const UserNoise *nz = plan.noise ? &plan.nz : nullptr;
+    const signed char *censor = plan.censor;
+    const UserInputs inputs{s.in_t, s.in_u, s.n_in, s.n_knot}, *in = plan.in ? &inputs : nullptr;
+    const UserEvents events_{s.ev_t, s.ev_v, s.n_ev, s.n_val}, *ev = plan.ev ? &events_ : nullptr;
+    if (!s.source) return smc_fail(c, "smc_set_model_user: NULL source");
     if (!user_method_ok(method)) return smc_fail(c, "smc_set_model_user: unknown method (SMC_USER_METHOD_RK45 or SMC_USER_METHOD_BDF)");
     if (n_states < 1 || n_states > SMC_USER_MAX_STATES) return smc_fail(c, "smc_set_model_user: n_states out of range");
     if (multi && !user_obs_ok(n_obs)) return smc_fail(c, "smc_set_model_user3: n_obs out of range (1 .. SMC_USER_MAX_OBS)");
@@ -1088,8 +1180,10 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
                             "rounded down to even) + 40 + 8 n_ex) x 8 B + pools): " +
                             std::to_string(user_lds_bytes3(n_states, n_ex, n_t, n_obs, true)) + " B needed, " + std::to_string(kUserLdsCap) +
                             " B available").c_str());
-    UserInputGeom geom;
-    geom.censor = censor ? 1 : 0;
+    UserSourceSpec sp;
+    sp.n_states = n_states, sp.dim = c->dim, sp.method = method, sp.n_obs = multi ? n_obs : 0;
+    sp.noise = nz ? 1 + nz->prop : 0, sp.censor = censor ? 1 : 0;
+    UserInputGeom &geom = sp.geom;
     std::vector<double> rows;      // the cond rows of a model with inputs, the table behind each
     if (in) {
         std::vector<int> knots;
@@ -1114,7 +1208,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     std::vector<char> code;
     std::string lg;
-    if (!compile_user(source, n_states, c->dim, method, multi ? n_obs : 0, code, lg, nz ? 1 + nz->prop : 0, geom)) {
+    if (!compile_user(s.source, sp, code, lg)) {
         std::string msg = "user model does not compile:\n" + lg;
         if (msg.size() > 3500) msg.resize(3500);
         return smc_fail(c, msg.c_str());
@@ -1129,7 +1223,7 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
         user_model_release(c);
         return smc_fail(c, "smc_set_model_user: loading the compiled module failed");
     }
-    if (mentions(source, "smc_user_cost") && hipModuleGetFunction(&u->fn_scan, u->module, "smc_user_cost_scan_kernel") != hipSuccess) {
+    if (mentions(s.source, "smc_user_cost") && hipModuleGetFunction(&u->fn_scan, u->module, "smc_user_cost_scan_kernel") != hipSuccess) {
         user_model_release(c);
         return smc_fail(c, "smc_set_model_user: the source mentions smc_user_cost but the scan kernel is missing from the module");
     }
@@ -1203,8 +1297,8 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
             return smc_fail(c, "smc_set_model_user: raising the dynamic LDS limit of the compiled kernel failed");
         }
     }
-    u->source = source;
-    u->geom = geom;
+    u->source = s.source;
+    u->spec = sp;
     u->h_rows.swap(rows);
     if (t) u->h_t.assign(t, t + (size_t)n_ex * n_t);
     if (n_cond > 0) u->h_cond.assign(cond, cond + (size_t)n_ex * n_cond);
@@ -1212,12 +1306,10 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     u->n_ex = n_ex;
     u->n_t = n_t;
     u->n_cond = n_cond;
-    u->n_states = n_states;
-    u->est_sigma = est_sigma;
-    u->sigma_fixed = sigma_fixed;
-    u->rtol = rtol;
-    u->atol = atol;
-    u->method = method;
+    u->est_sigma = plan.est_sigma;
+    u->sigma_fixed = plan.sigma_fixed;
+    u->rtol = s.rtol;
+    u->atol = s.atol;
     if (multi && prepare_pred_kernel(c, u) != 0) {
         user_model_release(c);
         return 1;
@@ -1227,159 +1319,81 @@ static int set_model_user_impl(smc_ctx *c, const char *source, int n_states, int
     return 0;
 }
 
-int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
-                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method) {
-    return set_model_user_impl(c, source, n_states, 1, t, obs, cond, nullptr, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
-                               method, false);
+int smc_set_model_user_spec(smc_ctx *c, const smc_user_model_spec *spec) {
+    smc_user_model_spec s;
+    if (!user_spec_copy(spec, offsetof(smc_user_model_spec, in_t), &s, sizeof s))
+        return smc_fail(c, "smc_set_model_user_spec: NULL spec, or a struct_size that ends before in_t or exceeds this library's struct");
+    return set_model_user_impl(c, s, "smc_set_model_user_spec");
 }
 
+// The earlier entry points: each fills the fields it knows, in the struct's order, and leaves the rest zero.  Those that take an
+// n_obs never meant the one-output model by it (obs_or_bad: one out of range fails as it always did).
 int smc_set_model_user(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol) {
-    return smc_set_model_user2(c, source, n_states, t, obs, cond, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
-                               SMC_USER_METHOD_RK45);
+    return smc_set_model_user2(c, source, n_states, t, obs, cond, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol, SMC_USER_METHOD_RK45);
 }
-
+int smc_set_model_user2(smc_ctx *c, const char *source, int n_states, const double *t, const double *obs, const double *cond,
+                        int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol, double atol, int method) {
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, 0, t, obs, cond, nullptr, n_ex, n_t, n_cond,
+                                   est_sigma, sigma_fixed, nullptr, nullptr, nullptr, nullptr, rtol, atol}, nullptr);
+}
 int smc_set_model_user3(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
                         const double *obs_scale, int n_ex, int n_t, int n_cond, int est_sigma, double sigma_fixed, double rtol,
                         double atol, int method) {
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol,
-                               atol, method, true);
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, obs_or_bad(n_obs), t, obs, cond, obs_scale,
+                                   n_ex, n_t, n_cond, est_sigma, sigma_fixed, nullptr, nullptr, nullptr, nullptr, rtol,
+                                   atol}, nullptr);
 }
-
-// a model with a noise specification: smc_set_model_user4, and smc_set_model_user5 / 6 (`in`: its inputs, `ev`: its events)
-static int set_model_user_noise(smc_ctx *c, const char *who, const char *source, int n_states, int n_obs, const double *t, const double *obs,
-                                const double *cond, const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index,
-                                const double *add_fixed, const int *prop_index, const double *prop_fixed, double rtol, double atol,
-                                int method, const UserInputs *in, const UserEvents *ev = nullptr, const signed char *censor = nullptr) {
-    if (!c) return smc_fail(nullptr, "NULL context");
-    const std::string bad = noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed);
-    if (!bad.empty()) return smc_fail(c, (std::string(who) + ": " + bad).c_str());
-    if (!prop_index && !censor) {      // today's model: one sigma for every output - the smc_set_model_user3 path and its bits
-        bool last = true, fixed = true;
-        for (int k = 0; k < n_obs; ++k) {
-            last = last && add_index[k] == c->dim - 1;
-            fixed = fixed && add_index[k] == -1 && add_fixed[k] == add_fixed[0];
-        }
-        if (last || fixed)
-            return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, last ? 1 : 0,
-                                       last ? 0.0 : add_fixed[0], rtol, atol, method, true, nullptr, in, ev);
-    }
-    UserNoise nz{};
-    for (int k = 0; k < kUserMaxObs; ++k) {
-        nz.add_index[k] = k < n_obs ? add_index[k] : -1;
-        nz.add_fixed[k] = (k < n_obs && add_index[k] < 0) ? add_fixed[k] : 1.0;
-        nz.prop_index[k] = (k < n_obs && prop_index) ? prop_index[k] : -1;
-        nz.prop_fixed[k] = (k < n_obs && prop_index && prop_index[k] < 0) ? prop_fixed[k] : 0.0;
-        nz.scale[k] = (k < n_obs && obs_scale) ? obs_scale[k] : 1.0;
-    }
-    nz.prop = prop_index ? 1 : 0;
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, 0, 1.0, rtol, atol, method, true, &nz, in, ev, censor);
-}
-
 int smc_set_model_user4(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
                         const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
                         const int *prop_index, const double *prop_fixed, double rtol, double atol, int method) {
-    return set_model_user_noise(c, "smc_set_model_user4", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
-                                add_fixed, prop_index, prop_fixed, rtol, atol, method, nullptr);
+    if (c && !add_index)      // no sigma rule here: the specification's own rules say what is missing
+        return smc_fail(c, ("smc_set_model_user4: " + noise_spec_error(n_obs, c->dim, add_index, add_fixed, prop_index, prop_fixed)).c_str());
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, obs_or_bad(n_obs), t, obs, cond, obs_scale,
+                                   n_ex, n_t, n_cond, 0, 0.0, add_index, add_fixed, prop_index, prop_fixed, rtol, atol}, nullptr);
 }
-
 int smc_set_model_user5(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
                         const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
                         const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
                         double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot) {
-    if (!c) return smc_fail(nullptr, "NULL context");
-    const UserInputs inputs{in_t, in_u, n_in, n_knot};
-    const UserInputs *in = &inputs;
-    if (n_in == 0) {      // no inputs: the existing functions' paths and their bits
-        if (in_t || in_u) return smc_fail(c, "smc_set_model_user5: n_in = 0 with in_t or in_u given (both must be NULL)");
-        in = nullptr;
-    }
-    if (add_index)
-        return set_model_user_noise(c, in ? "smc_set_model_user5" : "smc_set_model_user4", source, n_states, n_obs, t, obs, cond, obs_scale,
-                                    n_ex, n_t, n_cond, add_index, add_fixed, prop_index, prop_fixed, rtol, atol, method, in);
-    if (add_fixed || prop_index || prop_fixed)
-        return smc_fail(c, "smc_set_model_user5: add_index is NULL (the sigma rule) and another part of a noise model is given");
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
-                               method, true, nullptr, in);
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, obs_or_bad(n_obs), t, obs, cond, obs_scale,
+                                   n_ex, n_t, n_cond, est_sigma, sigma_fixed, add_index, add_fixed, prop_index, prop_fixed, rtol,
+                                   atol, in_t, in_u, n_in, n_knot}, nullptr);
 }
-
 int smc_set_model_user6(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
                         const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
                         const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
                         double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot, const double *ev_t,
                         const double *ev_v, int n_ev, int n_val) {
-    if (!c) return smc_fail(nullptr, "NULL context");
-    if (n_ev == 0) {      // no events: smc_set_model_user5's path and its bits
-        if (ev_t || ev_v) return smc_fail(c, "smc_set_model_user6: n_ev = 0 with ev_t or ev_v given (both must be NULL)");
-        return smc_set_model_user5(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index, add_fixed, prop_index,
-                                   prop_fixed, rtol, atol, method, est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot);
-    }
-    const UserInputs inputs{in_t, in_u, n_in, n_knot};
-    const UserInputs *in = &inputs;
-    if (n_in == 0) {
-        if (in_t || in_u) return smc_fail(c, "smc_set_model_user6: n_in = 0 with in_t or in_u given (both must be NULL)");
-        in = nullptr;
-    }
-    const UserEvents events{ev_t, ev_v, n_ev, n_val};
-    if (add_index)
-        return set_model_user_noise(c, "smc_set_model_user6", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
-                                    add_fixed, prop_index, prop_fixed, rtol, atol, method, in, &events);
-    if (add_fixed || prop_index || prop_fixed)
-        return smc_fail(c, "smc_set_model_user6: add_index is NULL (the sigma rule) and another part of a noise model is given");
-    return set_model_user_impl(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, est_sigma, sigma_fixed, rtol, atol,
-                               method, true, nullptr, in, &events);
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, obs_or_bad(n_obs), t, obs, cond, obs_scale,
+                                   n_ex, n_t, n_cond, est_sigma, sigma_fixed, add_index, add_fixed, prop_index, prop_fixed, rtol,
+                                   atol, in_t, in_u, n_in, n_knot, ev_t, ev_v, n_ev, n_val}, nullptr);
 }
-
-// censored observations: smc_set_model_user6's arguments, then the flags.  NULL or all zeros: smc_set_model_user6, its path and
-// its bits.  Else the model takes the noise path; without a noise specification (add_index NULL) the equivalent one is formed
-// here - every output at the last parameter under est_sigma, else fixed at sigma_fixed.
 int smc_set_model_user7(smc_ctx *c, const char *source, int n_states, int n_obs, const double *t, const double *obs, const double *cond,
                         const double *obs_scale, int n_ex, int n_t, int n_cond, const int *add_index, const double *add_fixed,
                         const int *prop_index, const double *prop_fixed, double rtol, double atol, int method, int est_sigma,
                         double sigma_fixed, const double *in_t, const double *in_u, int n_in, int n_knot, const double *ev_t,
                         const double *ev_v, int n_ev, int n_val, const signed char *censor) {
-    if (!c) return smc_fail(nullptr, "NULL context");
-    bool any = false;
-    if (censor && n_ex >= 1 && n_t >= 1 && user_obs_ok(n_obs))
-        for (size_t i = 0; i < (size_t)n_ex * n_t * n_obs && !any; ++i) any = censor[i] != 0;
-    if (!any)
-        return smc_set_model_user6(c, source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index, add_fixed, prop_index,
-                                   prop_fixed, rtol, atol, method, est_sigma, sigma_fixed, in_t, in_u, n_in, n_knot, ev_t, ev_v, n_ev, n_val);
-    {   // the data's own rules first (the flags' rules assume them), then the flags'
-        std::vector<double> me, ls;
-        const std::string bad_obs = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls) : std::string("NULL t or obs");
-        if (!bad_obs.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad_obs).c_str());
-        const std::string bad = censor_layout_error(t, obs, censor, n_ex, n_t, n_obs, n_ex, n_t, n_obs);
-        if (!bad.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad).c_str());
-    }
-    const UserInputs inputs{in_t, in_u, n_in, n_knot};
-    const UserInputs *in = &inputs;
-    if (n_in == 0) {
-        if (in_t || in_u) return smc_fail(c, "smc_set_model_user7: n_in = 0 with in_t or in_u given (both must be NULL)");
-        in = nullptr;
-    }
-    const UserEvents events{ev_t, ev_v, n_ev, n_val};
-    const UserEvents *ev = &events;
-    if (n_ev == 0) {
-        if (ev_t || ev_v) return smc_fail(c, "smc_set_model_user7: n_ev = 0 with ev_t or ev_v given (both must be NULL)");
-        ev = nullptr;
-    }
-    int sigma_index[kUserMaxObs];
-    double sigma_value[kUserMaxObs];
-    if (!add_index) {
-        if (add_fixed || prop_index || prop_fixed)
-            return smc_fail(c, "smc_set_model_user7: add_index is NULL (the sigma rule) and another part of a noise model is given");
-        if (!est_sigma && !(std::isfinite(sigma_fixed) && sigma_fixed > 0.0))
-            return smc_fail(c, "smc_set_model_user7: sigma_fixed must be finite and > 0");
-        for (int k = 0; k < kUserMaxObs; ++k) {
-            sigma_index[k] = est_sigma ? c->dim - 1 : -1;
-            sigma_value[k] = est_sigma ? 0.0 : sigma_fixed;
-        }
-        add_index = sigma_index;
-        add_fixed = sigma_value;
-    }
-    return set_model_user_noise(c, "smc_set_model_user7", source, n_states, n_obs, t, obs, cond, obs_scale, n_ex, n_t, n_cond, add_index,
-                                add_fixed, prop_index, prop_fixed, rtol, atol, method, in, ev, censor);
+    return set_model_user_impl(c, {sizeof(smc_user_model_spec), source, n_states, method, obs_or_bad(n_obs), t, obs, cond, obs_scale,
+                                   n_ex, n_t, n_cond, est_sigma, sigma_fixed, add_index, add_fixed, prop_index, prop_fixed, rtol,
+                                   atol, in_t, in_u, n_in, n_knot, ev_t, ev_v, n_ev, n_val, censor}, nullptr);
+}
+
+int smc_user_spec_layout(int which, int *offsets, int cap) {
+#define SRC(f) (int)offsetof(smc_user_source_spec, f)
+#define MOD(f) (int)offsetof(smc_user_model_spec, f)
+    static const int src[] = {SRC(struct_size), SRC(source), SRC(n_states), SRC(dim), SRC(method), SRC(n_obs), SRC(noise), SRC(n_cond), SRC(n_in),
+                              SRC(n_knot), SRC(n_ev), SRC(n_val), SRC(censor)};
+    static const int mod[] = {MOD(struct_size), MOD(source), MOD(n_states), MOD(method), MOD(n_obs), MOD(t), MOD(obs), MOD(cond), MOD(obs_scale),
+                              MOD(n_ex), MOD(n_t), MOD(n_cond), MOD(est_sigma), MOD(sigma_fixed), MOD(add_index), MOD(add_fixed), MOD(prop_index),
+                              MOD(prop_fixed), MOD(rtol), MOD(atol), MOD(in_t), MOD(in_u), MOD(n_in), MOD(n_knot), MOD(ev_t), MOD(ev_v), MOD(n_ev),
+                              MOD(n_val), MOD(censor)};
+#undef SRC
+#undef MOD
+    if (which != 0 && which != 1) return -1;
+    const int n = which == 0 ? (int)(sizeof src / sizeof src[0]) : (int)(sizeof mod / sizeof mod[0]);
+    for (int i = 0; i < n && i < cap && offsets; ++i) offsets[i] = which == 0 ? src[i] : mod[i];
+    return which == 0 ? (int)sizeof(smc_user_source_spec) : (int)sizeof(smc_user_model_spec);
 }
 
 int smc_user_set_design_events(smc_ctx *c, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new) {
@@ -1392,16 +1406,16 @@ int smc_user_set_design_events(smc_ctx *c, const double *ev_t_new, const double 
         u->design_ev_n_ex = u->design_ev_n_ev = 0;
         return 0;
     }
-    if (u->geom.n_ev == 0) return smc_fail(c, "smc_user_set_design_events: the model has no events (set it through smc_set_model_user6)");
-    if (n_ev_new > u->geom.n_ev)
+    if (u->spec.geom.n_ev == 0) return smc_fail(c, "smc_user_set_design_events: the model has no events (set it through smc_set_model_user6)");
+    if (n_ev_new > u->spec.geom.n_ev)
         return smc_fail(c, ("smc_user_set_design_events: n_ev_new = " + std::to_string(n_ev_new) + " above the event capacity " +
-                            std::to_string(u->geom.n_ev) + " the model was compiled for (its n_ev)").c_str());
+                            std::to_string(u->spec.geom.n_ev) + " the model was compiled for (its n_ev)").c_str());
     std::vector<int> events;      // the rule about t[e][0] waits for the design's times (resolve_design)
-    const std::string bad = event_layout_error(nullptr, ev_t_new, ev_v_new, n_ex_new, 0, n_ev_new, u->geom.n_val, events);
+    const std::string bad = event_layout_error(nullptr, ev_t_new, ev_v_new, n_ex_new, 0, n_ev_new, u->spec.geom.n_val, events);
     if (!bad.empty()) return smc_fail(c, ("smc_user_set_design_events: " + bad + " (of the design)").c_str());
     u->design_ev_t.assign(ev_t_new, ev_t_new + (size_t)n_ex_new * n_ev_new);
     u->design_ev_v.clear();
-    if (ev_v_new) u->design_ev_v.assign(ev_v_new, ev_v_new + (size_t)n_ex_new * n_ev_new * u->geom.n_val);
+    if (ev_v_new) u->design_ev_v.assign(ev_v_new, ev_v_new + (size_t)n_ex_new * n_ev_new * u->spec.geom.n_val);
     u->design_ev_n_ex = n_ex_new;
     u->design_ev_n_ev = n_ev_new;
     return 0;
@@ -1417,17 +1431,17 @@ int smc_user_set_design_inputs(smc_ctx *c, const double *in_t_new, const double 
         u->design_n_ex = u->design_n_knot = 0;
         return 0;
     }
-    if (u->geom.n_in == 0) return smc_fail(c, "smc_user_set_design_inputs: the model has no inputs (set it through smc_set_model_user5)");
+    if (u->spec.geom.n_in == 0) return smc_fail(c, "smc_user_set_design_inputs: the model has no inputs (set it through smc_set_model_user5)");
     std::vector<int> knots;
-    const std::string bad = input_layout_error(in_t_new, in_u_new, n_ex_new, u->geom.n_in, n_knot_new, knots);
+    const std::string bad = input_layout_error(in_t_new, in_u_new, n_ex_new, u->spec.geom.n_in, n_knot_new, knots);
     if (!bad.empty()) return smc_fail(c, ("smc_user_set_design_inputs: " + bad + " (of the design)").c_str());
     for (int e = 0; e < n_ex_new; ++e)
-        if (knots[e] > u->geom.kcap)
+        if (knots[e] > u->spec.geom.kcap)
             return smc_fail(c, ("smc_user_set_design_inputs: row " + std::to_string(e) + " of in_t has " + std::to_string(knots[e]) +
-                                " knots, above the knot capacity " + std::to_string(u->geom.kcap) +
+                                " knots, above the knot capacity " + std::to_string(u->spec.geom.kcap) +
                                 " the model was compiled for (the power of two >= its n_knot)").c_str());
     u->design_t.assign(in_t_new, in_t_new + (size_t)n_ex_new * n_knot_new);
-    u->design_u.assign(in_u_new, in_u_new + (size_t)n_ex_new * n_knot_new * u->geom.n_in);
+    u->design_u.assign(in_u_new, in_u_new + (size_t)n_ex_new * n_knot_new * u->spec.geom.n_in);
     u->design_n_ex = n_ex_new;
     u->design_n_knot = n_knot_new;
     return 0;
@@ -1444,11 +1458,11 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
     if (n == 0) return 0;
     if (!u->d_img) return smc_fail(c, u->img_error.c_str());
     if (!u->fn_pred) {      // a one-output model of smc_set_model_user / 2: its prediction kernel, compiled once
-        if (user_lds_bytes3(u->n_states, u->n_ex, u->n_t, 1) > kUserLdsCap)
+        if (user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, 1) > kUserLdsCap)
             return smc_fail(c, "smc_user_predict: data set too large for the prediction kernel's LDS table");
         std::vector<char> code;
         std::string lg;
-        if (!compile_user(u->source.c_str(), u->n_states, c->dim, u->method, 1, code, lg, 0, u->geom))
+        if (!compile_user(u->source.c_str(), pred_source_spec(u), code, lg))
             return smc_fail(c, ("smc_user_predict: the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
         if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
             hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
@@ -1477,7 +1491,7 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
     }
     double *aos = u->d_pt, *soa = u->d_pt + (size_t)u->p_cap * dim;
     if (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-        (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess))
+        (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess))
         return smc_fail(c, "smc_user_predict: clearing the counters failed");
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t m = (n - off < chunk) ? n - off : chunk;
@@ -1511,7 +1525,7 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
     if (!t) {
         if (!u->d_img) return smc_fail(c, u->img_error.c_str());
         t = u->h_t.data();
-        cond = u->geom.tabled() ? u->h_rows.data() : u->h_cond.data();
+        cond = u->spec.geom.tabled() ? u->h_rows.data() : u->h_cond.data();
         n_ex = u->n_ex;
         n_t = u->n_t;
         return 0;
@@ -1522,37 +1536,37 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
     std::vector<double> me, ls;
     const std::string bad = obs_layout(t, nan_obs.data(), u->scale, n_ex, n_t, u->n_obs, me, ls);
     if (!bad.empty()) return smc_fail(c, (w + bad + " (t_new)").c_str());
-    if (u->geom.n_in > 0) {
+    if (u->spec.geom.n_in > 0) {
         if (u->design_n_ex != n_ex)
             return smc_fail(c, (w + "the model has inputs and the design has no matching design inputs: " +
                                 (u->design_n_ex ? "smc_user_set_design_inputs holds " + std::to_string(u->design_n_ex) + " rows"
                                                 : std::string("none are set")) +
                                 ", the design has " + std::to_string(n_ex) + " experiments (smc_user_set_design_inputs)").c_str());
         std::vector<int> knots;
-        if (!input_layout_error(u->design_t.data(), u->design_u.data(), n_ex, u->geom.n_in, u->design_n_knot, knots).empty())
+        if (!input_layout_error(u->design_t.data(), u->design_u.data(), n_ex, u->spec.geom.n_in, u->design_n_knot, knots).empty())
             return smc_fail(c, (w + "the design inputs are no longer valid").c_str());
         // a row whose finite knots fit the capacity may still be stored wider (trailing NaN): only its knots are copied
-        rows = build_input_rows(cond, u->geom, u->design_t.data(), u->design_u.data(), n_ex, u->design_n_knot, knots);
+        rows = build_input_rows(cond, u->spec.geom, u->design_t.data(), u->design_u.data(), n_ex, u->design_n_knot, knots);
         cond = rows.data();
     }
-    if (u->geom.n_ev > 0) {      // the what-if regimen: the design's own events, behind what the rows hold so far
+    if (u->spec.geom.n_ev > 0) {      // the what-if regimen: the design's own events, behind what the rows hold so far
         if (u->design_ev_n_ex != n_ex)
             return smc_fail(c, (w + "the model has events and the design has no matching design events: " +
                                 (u->design_ev_n_ex ? "smc_user_set_design_events holds " + std::to_string(u->design_ev_n_ex) + " rows"
                                                    : std::string("none are set")) +
                                 ", the design has " + std::to_string(n_ex) + " experiments (smc_user_set_design_events)").c_str());
         std::vector<int> events;
-        const std::string bad_ev = event_layout_error(t, u->design_ev_t.data(), u->geom.n_val > 0 ? u->design_ev_v.data() : nullptr, n_ex, n_t,
-                                                      u->design_ev_n_ev, u->geom.n_val, events);
+        const std::string bad_ev = event_layout_error(t, u->design_ev_t.data(), u->spec.geom.n_val > 0 ? u->design_ev_v.data() : nullptr, n_ex, n_t,
+                                                      u->design_ev_n_ev, u->spec.geom.n_val, events);
         if (!bad_ev.empty()) return smc_fail(c, (w + bad_ev + " (of the design events)").c_str());
-        rows = build_event_rows(cond, u->geom, u->design_ev_t.data(), u->design_ev_v.data(), n_ex, u->design_ev_n_ev, events);
+        rows = build_event_rows(cond, u->spec.geom, u->design_ev_t.data(), u->design_ev_v.data(), n_ex, u->design_ev_n_ev, events);
         cond = rows.data();
     }
     return 0;
 }
 static int design_too_large(smc_ctx *c, const UserModel *u, const char *who, int n_t) {
     return smc_fail(c, (std::string(who) + ": one row of the design does not fit the kernel's LDS table: " +
-                        std::to_string(user_lds_bytes3(u->n_states, 1, n_t, u->n_obs, u->noise, u->geom.censor != 0)) + " B needed, " + std::to_string(kUserLdsCap) +
+                        std::to_string(user_lds_bytes3(u->spec.n_states, 1, n_t, u->n_obs, u->noise, u->spec.censor != 0)) + " B needed, " + std::to_string(kUserLdsCap) +
                         " B available").c_str());
 }
 
@@ -1594,7 +1608,7 @@ int smc_user_predict_at(smc_ctx *c, const double *particle, int64_t n, const dou
     if (!ok) rc = smc_fail(c, "smc_user_predict_at: device allocation / upload failed");
     double *aos = d_pt, *soa = d_pt + (size_t)chunk * dim;
     if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-                    (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
+                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
         rc = smc_fail(c, "smc_user_predict_at: clearing the counters failed");
     for (int64_t off = 0; rc == 0 && off < n; off += chunk) {
         const int64_t m = (n - off < chunk) ? n - off : chunk;
@@ -1698,7 +1712,7 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
     if (!ok) rc = smc_fail(c, "smc_user_predict_summary: device allocation / upload failed");
     if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-                    (u->method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
+                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
         rc = smc_fail(c, "smc_user_predict_summary: clearing the counters failed");
     const ParticleSet &P = c->set[set];
     for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
@@ -1778,7 +1792,7 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
 int smc_user_sweep_counters(smc_ctx *c, int64_t out[4]) {
     if (!c) return smc_fail(nullptr, "NULL context");
     UserModel *u = (UserModel *)c->user;
-    if (c->model_kind != 3 || !u || u->method != SMC_USER_METHOD_BDF)
+    if (c->model_kind != 3 || !u || u->spec.method != SMC_USER_METHOD_BDF)
         return smc_fail(c, "smc_user_sweep_counters: the model is not a user model with method SMC_USER_METHOD_BDF");
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     unsigned long long h[4];

@@ -175,41 +175,43 @@ class HipEngine:
 
     def set_model_user(self, source: str, n_states: int, t, obs, cond=None, est_sigma=True, sigma_fixed=5.0, rtol=1e-3,
                        atol=1e-6, method="RK45", obs_scale=None, noise=None, inputs=None, events=None, censor=None):
-        """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_set_model_user): `source`
+        """A user-written model in place of Micmem_likelihood.py (include/smc_hip.h, smc_user_model_spec): `source`
         defines smc_user_y0 / smc_user_rhs / smc_user_obs as HIP device functions; t, obs: (n_ex, n_t); cond: (n_ex, n_cond)
         per-experiment numbers (e.g. the initial concentration).  method: "RK45" (solve_ivp's default) or "BDF" for a stiff
         model (then the source may also define smc_user_jac).  Raises ValueError for another method and SmcError with the
         compiler log if the source does not compile.
-        Several measured outputs, missing data, ragged rows (smc_set_model_user3): obs (n_ex, n_t, n_obs) with NaN for a value
+        Several measured outputs, missing data, ragged rows: obs (n_ex, n_t, n_obs) with NaN for a value
         that was not measured, t rows that may end in NaN times, obs_scale (n_obs,) relative noise scales; the source then
         defines smc_user_obs_vec.  A 3-D obs or any obs_scale takes this path (ValueError for data it refuses, see
-        user_models.obs_layout); a 2-D obs without obs_scale goes through smc_set_model_user2 exactly as before.
-        A noise model (smc_set_model_user4): noise={"additive": [("param", j) | ("fixed", v), ...], "proportional": [...]}, one
+        user_models.obs_layout); a 2-D obs without obs_scale, noise, inputs, events or
+        censoring is the one-output model (n_obs = 0 in the spec) exactly as before.
+        A noise model: noise={"additive": [("param", j) | ("fixed", v), ...], "proportional": [...]}, one
         entry per output, "proportional" optional - sd^2 = (a_k s_k)^2 + (b_k f)^2 (user_models.noise_loglik is the likelihood).
         est_sigma and sigma_fixed are then not used; ValueError for a specification that breaks user_models.noise_layout's rules.
-        Time-varying measured inputs (smc_set_model_user5): inputs={"t": (n_ex, n_knot), "u": (n_ex, n_knot, n_in)} - knot times (a
+        Time-varying measured inputs: inputs={"t": (n_ex, n_knot), "u": (n_ex, n_knot, n_in)} - knot times (a
         row may end in NaN) and the values of n_in inputs at them (2-D for one input); the source reads them as
         smc_input(cond, k, t), linear between knots (user_models.input_value is the definition, input_layout the rules: ValueError
-        for inputs that break them).  With obs, obs_scale, noise / est_sigma as above.  inputs=None goes through the calls above
-        exactly as before.
-        Scheduled events (smc_set_model_user6): events={"t": (n_ex, n_ev), "values": (n_ex, n_ev, n_val) or None} - event times (a
+        for inputs that break them).  With obs, obs_scale, noise / est_sigma as above.  inputs=None leaves the model as it is
+        without them.
+        Scheduled events: events={"t": (n_ex, n_ev), "values": (n_ex, n_ev, n_val) or None} - event times (a
         row may end in NaN, or hold none) and the numbers of every event; the source defines smc_user_event(j, t, y, theta, cond),
         which changes y in place at event j and reads its numbers as smc_event_value(cond, j, k).  The solve is the chain of
         solve_ivp calls between the events (include/smc_hip.h); user_models.event_layout states the rules (ValueError for events
-        that break them).  events=None goes through the calls above exactly as before.
-        Censored observations (smc_set_model_user7): censor (n_ex, n_t, n_obs) integer flags beside obs - 0: obs is the measured
+        that break them).  events=None leaves the model as it is without them.
+        Censored observations: censor (n_ex, n_t, n_obs) integer flags beside obs - 0: obs is the measured
         value; -1: left-censored, the true value is <= obs, which holds the lower limit; +1: right-censored, >= obs, the upper limit.
         A censored value contributes log Phi(z) (user_models.censored_loglik is the likelihood, censor_layout the rules: ValueError
         for flags that break them, censor_data makes such data).  With a flag set the model takes the noise path; noise=None then
         stands for every output at the last parameter (est_sigma) or fixed at sigma_fixed.  Combines with everything above.
-        censor=None or all zeros goes through the calls above exactly as before."""
+        censor=None or all zeros leaves the model as it is without them.  Every feature is a group of fields of one
+        smc_user_model_spec, set by smc_set_model_user_spec; an absent feature takes the path, and gives the bits, it always had."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
         t = _f64(t)
         obs = np.asarray(obs)
         multi = obs.ndim == 3 or obs_scale is not None or noise is not None or inputs is not None or events is not None
         if multi:
-            # several outputs, NaN = not measured, ragged rows (smc_set_model_user3); the same checks as the library's
+            # several outputs, NaN = not measured, ragged rows; the same checks as the library's
             obs = _f64(obs if obs.ndim == 3 else obs.reshape(obs.shape + (1,)))
             from .user_models import obs_layout
             obs_layout(t, obs, obs_scale)
@@ -221,14 +223,9 @@ class HipEngine:
         cond = np.zeros((t.shape[0], 0)) if cond is None else _f64(np.asarray(cond).reshape(t.shape[0], -1))
         cbuf = np.ascontiguousarray(cond if cond.size else np.zeros((t.shape[0], 1)))
         ai = af = pi = pf = None
-        ip = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(B.c_ip)
-        fp = lambda a: None if a is None else _dp(np.ascontiguousarray(a, dtype=np.float64))
         if noise is not None:
             from .user_models import noise_layout
             ai, af, pi, pf = noise_layout(noise, n_obs, self.dim)
-            ai, af = np.ascontiguousarray(ai, dtype=np.int32), np.ascontiguousarray(af)
-            pi = None if pi is None else np.ascontiguousarray(pi, dtype=np.int32)
-            pf = None if pf is None else np.ascontiguousarray(pf)
         n_in = n_ev = n_val = 0
         in_t = in_u = ev_t = ev_v = None
         if censor is not None:
@@ -238,7 +235,7 @@ class HipEngine:
                 obs3 = _f64(obs.reshape(obs.shape + (1,)))
                 censor = censor.reshape(censor.shape + (1,)) if censor.ndim == 2 else censor
             censor_layout(t, obs if multi else obs3, censor)
-            censor = np.ascontiguousarray(censor, dtype=np.int8) if np.any(censor != 0) else None
+            censor = censor if np.any(censor != 0) else None
         if censor is not None and not multi:
             multi, obs, n_obs, scale = True, obs3, 1, None
         if inputs is not None:
@@ -246,40 +243,26 @@ class HipEngine:
         if events is not None:
             ev_t, ev_v, n_val = self._events("set_model_user", events, t)
             n_ev = ev_t.shape[1]
-        if censor is not None:
-            self._ck(self.L.smc_set_model_user7(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
-                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
-                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
-                                                int(bool(est_sigma)), float(sigma_fixed), fp(in_t), fp(in_u), n_in,
-                                                0 if in_t is None else in_t.shape[1], fp(ev_t), fp(ev_v), n_ev, n_val,
-                                                censor.ctypes.data_as(B.c_i8p)), "smc_set_model_user7")
-        elif events is not None:
-            self._ck(self.L.smc_set_model_user6(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
-                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
-                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
-                                                int(bool(est_sigma)), float(sigma_fixed), fp(in_t), fp(in_u), n_in,
-                                                0 if in_t is None else in_t.shape[1], _dp(ev_t), fp(ev_v), n_ev, n_val),
-                     "smc_set_model_user6")
-        elif inputs is not None:
-            self._ck(self.L.smc_set_model_user5(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
-                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
-                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol), B.USER_METHODS[method],
-                                                int(bool(est_sigma)), float(sigma_fixed), _dp(in_t), _dp(in_u), n_in, in_t.shape[1]),
-                     "smc_set_model_user5")
-        elif noise is not None:
-            self._ck(self.L.smc_set_model_user4(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
-                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
-                                                ip(ai), fp(af), ip(pi), fp(pf), float(rtol), float(atol),
-                                                B.USER_METHODS[method]), "smc_set_model_user4")
-        elif multi:
-            self._ck(self.L.smc_set_model_user3(self.ctx, source.encode(), int(n_states), n_obs, _dp(t), _dp(obs), _dp(cbuf),
-                                                None if scale is None else _dp(scale), t.shape[0], t.shape[1], cond.shape[1],
-                                                int(bool(est_sigma)), float(sigma_fixed), float(rtol), float(atol),
-                                                B.USER_METHODS[method]), "smc_set_model_user3")
-        else:
-            self._ck(self.L.smc_set_model_user2(self.ctx, source.encode(), int(n_states), _dp(t), _dp(obs), _dp(cbuf), t.shape[0],
-                                                t.shape[1], cond.shape[1], int(bool(est_sigma)), float(sigma_fixed), float(rtol),
-                                                float(atol), B.USER_METHODS[method]), "smc_set_model_user")
+        # one description by field name (include/smc_hip.h: smc_user_model_spec); n_obs = 0: the one-output model.  `keep` holds the
+        # arrays the struct points to until the call has returned
+        keep = []
+
+        def ptr(a, dtype, ctype):
+            if a is None:
+                return None
+            keep.append(np.ascontiguousarray(a, dtype=dtype))
+            return keep[-1].ctypes.data_as(ctype)
+
+        spec = B.UserModelSpec(
+            source=source.encode(), n_states=int(n_states), method=B.USER_METHODS[method], n_obs=n_obs if multi else 0,
+            t=ptr(t, np.float64, B.c_dp), obs=ptr(obs, np.float64, B.c_dp), cond=ptr(cbuf, np.float64, B.c_dp),
+            obs_scale=ptr(scale if multi else None, np.float64, B.c_dp), n_ex=t.shape[0], n_t=t.shape[1], n_cond=cond.shape[1],
+            est_sigma=int(bool(est_sigma)), sigma_fixed=float(sigma_fixed), add_index=ptr(ai, np.int32, B.c_ip),
+            add_fixed=ptr(af, np.float64, B.c_dp), prop_index=ptr(pi, np.int32, B.c_ip), prop_fixed=ptr(pf, np.float64, B.c_dp),
+            rtol=float(rtol), atol=float(atol), in_t=ptr(in_t, np.float64, B.c_dp), in_u=ptr(in_u, np.float64, B.c_dp), n_in=n_in,
+            n_knot=0 if in_t is None else in_t.shape[1], ev_t=ptr(ev_t, np.float64, B.c_dp), ev_v=ptr(ev_v, np.float64, B.c_dp),
+            n_ev=n_ev, n_val=n_val, censor=ptr(censor, np.int8, B.c_i8p))
+        self._ck(self.L.smc_set_model_user_spec(self.ctx, ctypes.byref(spec)), "smc_set_model_user_spec")
         self.model = ("user", t.shape[0], t.shape[1])      # the driver indexes this 3-tuple
         self.user_n_obs = n_obs
         self.user_n_cond = cond.shape[1]

@@ -19,6 +19,10 @@ line by line after dropping the `__hip_cuid_<hash>` symbol, which differs betwee
 smc_user_solve_kernel, smc_user_predict_kernel and smc_user_cost_scan_kernel, their .amdhsa_ blocks and the metadata
 (registers, scratch, LDS) must agree.  One line per case; exit status 1 if any case differs.
 
+Both libraries are asked through the numbered dump functions, not through smc_user_model_dump_source_spec: a parent from before
+the spec structs has no such function, and the numbered ones fill the same struct in a library that has it
+(tests/test_user_spec.py compares the two entries case by case).
+
 It is a tool, not a test: it needs a second build (the parent revision's), which the test suite has not got.
 """
 import argparse
