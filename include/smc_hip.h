@@ -134,6 +134,8 @@ int smc_set_model_methanation(smc_ctx *ctx, const double *cond, const double *gu
 #define SMC_USER_MAX_KNOTS 4096
 #define SMC_USER_MAX_EVENTS 256
 #define SMC_USER_MAX_EVENT_VALUES 8
+#define SMC_USER_MAX_ROOTS 4        /* event functions of a source with state-triggered events (smc_user_root) */
+#define SMC_USER_MAX_ROOT_FIRES 256 /* ... and how often they may fire in one solve */
 /* BOTH STRUCTS START WITH struct_size, the caller's sizeof: the library reads min(struct_size, its own sizeof) bytes over zeros, so
  * a field that a later feature appends reads as absent for a caller built before it.  A struct_size that ends before the fields
  * every caller has (smc_user_source_spec: through n_obs; smc_user_model_spec: through atol) or exceeds the library's own struct
@@ -249,8 +251,8 @@ typedef struct smc_user_model_spec {
      * at order 1 with a new Jacobian and the initial step rule.  A data time equal to tau_j sees the state before the event, the
      * next representable time after it the state after.  An event with tau_j >= t_end never fires; a segment may hold no data
      * time; rk_attempts counts step attempts only; a failed segment fails the solve as before (info bit 30, NaN from the stop on).
-     * Event TIMES are data: they cannot depend on theta (amounts can, through smc_user_event), and there are no state-triggered
-     * events.
+     * The TIMES of these events are data: they cannot depend on theta (amounts can, through smc_user_event).  An event whose time
+     * follows from the state - and so from theta - is a state-triggered event, below.
      * Row rules: a row of ev_t is a strictly increasing finite run and then only NaN - it may have no event at all; every finite
      * event time is > t[e][0]; the values are finite at a row's finite events and ignored past them.  Anything else fails with the
      * row, the event and the rule.  smc_user_event_check applies these rules alone (no GPU, no context; the reason in
@@ -262,7 +264,44 @@ typedef struct smc_user_model_spec {
      * smc_user_set_design_events: the events of an explicit design of smc_user_predict_at / smc_user_predict_summary (the what-if
      * dosing regimen; nothing is compiled again): n_ex_new rows of n_ev_new <= the model's n_ev events, held until replaced, both
      * pointers NULL clears them.  An explicit design on a model with events without design events of the same n_ex_new fails with
-     * the reason; t_new == NULL uses the data's events. */
+     * the reason; t_new == NULL uses the data's events.
+     * STATE-TRIGGERED EVENTS (a feed that switches on when the substrate runs out, a re-dose when a level falls to a threshold, a
+     * relay, a tank that overflows): the switching time is where a function of the state crosses zero, which solve_ivp users write
+     * as events=.  They need no field: the contract lives in the source, like smc_user_jac and smc_user_cost.  A source that
+     * contains the name smc_user_root has state-triggered events and defines all three of
+     *     __device__ const int smc_user_root_dir[] = {-1, 0};   // one entry per event function: -1 falling, +1 rising, 0 either
+     *     __device__ void smc_user_root(double t, const double *y, const double *theta, const double *cond, double *g);   // g[0 .. n_root)
+     *     __device__ void smc_user_root_event(int k, double t, double *y, const double *theta, const double *cond);      // y changed in place
+     * n_root, the length of smc_user_root_dir, is 1 .. SMC_USER_MAX_ROOTS.  Both functions always run with IEEE division (in an
+     * RK45 source: the smc_user_ieee compilation) and may call smc_input and smc_event_value where the model has those features.
+     * A source with smc_user_root and without smc_user_root_dir or smc_user_root_event, more than SMC_USER_MAX_ROOTS entries, or a
+     * direction that is not written as one of the integers -1, 0, +1 does not compile, with a message that says so.  The structs,
+     * SMC_ABI_VERSION and smc_user_spec_layout are what they were; explicit designs need nothing new, the functions travel with
+     * the compiled kernel; a dump of such a source also writes user_root.h.
+     * A solve is the chain of solve_ivp calls with every event function terminal, in the arithmetic of SciPy 1.15 (ivp.py,
+     * base.py; user_models.root_chain is the chain, user_models.brentq the root solver, both in Python).
+     *   Start of a segment - the start of the solve, after a scheduled event, after a triggered one: g = smc_user_root(t, y) there.
+     *   Detection: after every accepted step g_new = smc_user_root(t_new, y_new) on the solver's own y_new.  Event k is active when
+     * up = g_k <= 0 and g_new_k >= 0 (direction +1 or 0) or down = g_k >= 0 and g_new_k <= 0 (direction -1 or 0) - find_active_events;
+     * a NaN is never active.  With no active event g = g_new and nothing else changes.
+     *   Locating the root: for each active event brentq(s -> g_k(s, sol(s)), t_old, t_new, xtol = rtol = 4 * 2.220446049250313e-16,
+     * maxiter = 100) on that step's dense output sol (RK45: the quartic; BDF: BdfDenseOutput after the step).  The earliest root
+     * wins, on a tie the lowest k.
+     *   Truncating the step: t* = that root, y* = sol(t*).  The data times <= t* the step covers are served from sol, so a data
+     * time equal to t* sees the state before the jump and the next representable time the state after it.
+     *   Restart: smc_user_root_event(k, t*, y*), then the next segment starts afresh from (t*, y*) - as after a scheduled event:
+     * RK45 with a new first derivative, select_initial_step over the rest of the segment and no memory of a rejected step, BDF at
+     * order 1 with a new Jacobian and the initial step rule - and runs to the segment's bound, the next scheduled event time or
+     * the row's end.
+     *   Failures: a brentq that does not converge, meets a non-finite value, or finds g_k of one sign at both ends of the step
+     * (sol(t_new) is not y_new to the last bit; SciPy raises there) fails the solve - info bit 30, NaN from the stop on, as a
+     * failed segment does.  So does a root equal to the start of its own segment: the jump left the state on a firing surface
+     * (g_k == 0 in a firing direction), and the chain of solve_ivp calls would stop there for ever.  So does fire number
+     * SMC_USER_MAX_ROOT_FIRES + 1 of a solve.  A fired event is otherwise free.
+     *   Edge cases: a root at the row's end finishes the solve.  At t* equal to a scheduled event's time the triggered jump is
+     * applied first, then the scheduled one, and one restart follows.  rk_attempts counts step attempts only: evaluations of the
+     * event functions and the right-hand sides of a restart are none; BDF's step counter counts the truncated step, as SciPy does.
+     * A source whose event functions never fire gives the bits of the same source without the names. */
     const double *ev_t, *ev_v;
     int n_ev, n_val;
     /* CENSORED OBSERVATIONS: a value the assay could not quantify - below the

@@ -19,6 +19,7 @@ SMC_USER_METHOD_RK45, SMC_USER_METHOD_BDF = 0, 1
 SMC_USER_MAX_OBS = 8
 SMC_USER_MAX_INPUTS, SMC_USER_MAX_KNOTS = 8, 4096
 SMC_USER_MAX_EVENTS, SMC_USER_MAX_EVENT_VALUES = 256, 8
+SMC_USER_MAX_ROOTS, SMC_USER_MAX_ROOT_FIRES = 4, 256      # state-triggered events (smc_user_root)
 USER_METHODS = {"RK45": SMC_USER_METHOD_RK45, "BDF": SMC_USER_METHOD_BDF}
 SMC_PRIOR_UNIFORM, SMC_PRIOR_NORMAL, SMC_PRIOR_FLAT = 0, 1, 2
 SMC_PRIOR_MODE_MASK, SMC_PRIOR_MODE_RATIO_MASK, SMC_PRIOR_MODE_RATIO = 0, 1, 2

@@ -74,6 +74,10 @@ struct Item {
 #ifdef SMC_USER_EVENTS
     double t_end;   // scheduled events (user_item_ops.h: item_cache_times): the row's end; t_bound is the SEGMENT's bound
     int i_ev;       // the next event of the row: the first with tau > t
+#ifdef SMC_USER_ROOTS
+    double g[smc_root::kRoots], t_seg;   // state-triggered events (user_item_ops.h: root_segment): the event functions at (t, y); the
+    int n_fire;                          // segment's start; the events that have fired
+#endif  // SMC_USER_ROOTS
 #endif  // SMC_USER_EVENTS
 };
 // what a lane sets up for an item that has not had an attempt yet (item_begin and the pool's unpack)
@@ -382,6 +386,9 @@ __device__ void item_begin(Item &it, const double *theta, const double *cond, co
     }
 #ifdef SMC_USER_EVENTS
     item_cache_times(it, cond, tp, n_t);
+#ifdef SMC_USER_ROOTS
+    root_begin(it, it.D[0], theta, cond);
+#endif  // SMC_USER_ROOTS
 #else  // SMC_USER_EVENTS
     item_cache_times(it, tp, n_t);
 #endif  // SMC_USER_EVENTS
@@ -611,6 +618,106 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         }
     }
     if (cd) change_D(it, cd_order, cd_factor);
+#ifdef SMC_USER_ROOTS
+    // State-triggered events (user_root.h; ivp.py's loop body after solver.step()): after an accepted step the event functions at
+    // the solver's own (t_new, y_new); if one of them crossed in its direction, the root of every active event on the step's
+    // BdfDenseOutput (built after the step, as solve_ivp builds it), the earliest one t*, the outputs of the data times <= t* from
+    // the same dense output (a data time equal to t* sees the state before the jump), then y* = sol(t*), the jump
+    // smc_user_root_event(k, t*, y*) and the restart of a new solve_ivp call from (t*, y*): segment_start (order 1, a new
+    // Jacobian, the initial step rule), the event functions there, t_seg = t*.  The truncated step has been counted as a step,
+    // as SciPy counts it.  A root AT t_bound < t_end also meets scheduled event i_ev: the triggered jump first, then the
+    // scheduled one, then the one restart.  A root at the row's end finishes the solve.
+    // Failures (status -1: info bit 30, NaN from the first output not served): a root solve that fails (user_root.h: brentq), a
+    // root at the start of its own segment - the jump left the state on a firing surface, and the chain of solve_ivp calls would
+    // stop there for ever -, and a fire beyond SMC_USER_MAX_ROOT_FIRES.
+    // Termination: the loop over the events has kRoots <= 4 passes and each brentq at most 100 iterations.  A fire either fails
+    // the solve or raises n_fire, and n_fire > 256 fails it, so an item has at most 256 triggered restarts besides the
+    // SMC_USER_NEV scheduled ones argued below.  A segment that starts at a fire starts at t* > t_seg (t* == t_seg fails), and
+    // t* <= t_bound, so every segment has positive length and t never decreases; inside a segment the item is the solve it always
+    // was, and Ops::attempt's hard bound on the attempts stays.  No unbounded loop is added.
+    if (accepted) {
+        const int k = it.order;
+        const double hd = it.h_abs;
+        const auto sol = [&](double s, double *yy) {
+            double p = 1.0;
+#pragma unroll
+            for (int q = 0; q < NS; ++q) yy[q] = 0.0;
+#pragma unroll
+            for (int j = 0; j < kMaxOrder; ++j) {
+                const double t_shift = t_new - hd * j, denom = hd * (1 + j);
+                p = (j == 0) ? (s - t_shift) / denom : p * ((s - t_shift) / denom);
+#pragma unroll
+                for (int q = 0; q < NS; ++q) yy[q] = (j < k) ? yy[q] + it.D[j + 1][q] * p : yy[q];
+            }
+#pragma unroll
+            for (int q = 0; q < NS; ++q) yy[q] += it.D[0][q];
+        };
+        double g_new[smc_root::kRoots];
+        smc_root::eval(t_new, y_new, theta, cond, g_new);
+        const bool fired = smc_root::any_active(it.g, g_new);
+        double t_stop = t_new;
+        int k_fire = -1;
+        if (fired) {
+            k_fire = smc_root::first_root(it.g, g_new, sol, t, t_new, theta, cond, t_stop);
+            if (k_fire < 0 || t_stop == it.t_seg) {
+                it.status = -1;
+                return;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < smc_root::kRoots; ++q) it.g[q] = g_new[q];      // ivp.py: g = g_new
+        if (it.t_next <= t_stop) {
+            int i_out = it.i_out;
+            DataRec nx = tp[i_out];
+            do {
+                double yy[NS];
+                sol(nx.x, yy);
+                emit(it, yy, theta, cond, nx.x, nx.y);
+                ++i_out;
+                nx = tp[i_out];
+            } while (nx.x <= t_stop);
+            it.i_out = i_out;
+            it.t_next = nx.x;
+        }
+        if (fired) {
+            double y[NS];
+            sol(t_stop, y);
+            it.t = t_stop;
+            smc_user_ieee::smc_user_root_event(k_fire, t_stop, y, theta, cond);
+            ++it.n_fire;
+            if (it.n_fire > smc_root::kMaxFires) {
+                it.status = -1;
+                return;
+            }
+            if (t_stop - it.t_end >= 0) {      // a root at the row's end
+                it.status = 1;
+                return;
+            }
+            if (t_stop - t_bound >= 0) {       // ... at a scheduled event's time (t_bound < t_end here)
+                smc_user_ieee::smc_user_event(it.i_ev, t_stop, y, theta, cond);
+                ++it.i_ev;
+                it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+            }
+            segment_start(it, y, theta, cond, rtol, atol);
+            root_segment(it, it.D[0], theta, cond);
+            it.status = 0;
+            return;
+        }
+        // the segment ends at scheduled event i_ev, as below; the next one starts with the event functions at (tau, y)
+        if (t_new - t_bound >= 0 && t_bound < it.t_end) {
+            double y[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) y[s] = it.D[0][s];
+            smc_user_ieee::smc_user_event(it.i_ev, t_new, y, theta, cond);
+            ++it.i_ev;
+            it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+            segment_start(it, y, theta, cond, rtol, atol);
+            root_segment(it, it.D[0], theta, cond);
+            it.status = 0;
+            return;
+        }
+    }
+#else  // SMC_USER_ROOTS
     if (accepted && it.t_next <= t_new) {     // outputs in (t, t_new] (and t_eval[0] = t0 on the first step): BdfDenseOutput
         const int k = it.order;
         const double hd = it.h_abs;
@@ -656,6 +763,7 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         return;
     }
 #endif  // SMC_USER_EVENTS
+#endif  // SMC_USER_ROOTS
     it.status = (accepted && t_new - t_bound >= 0) ? 1 : 0;    // base.py
 }
 // What user_item_ops.h needs to know about the integrator (see the list at the top of that file).  Pool words 6 ..: y = D[0],
@@ -715,6 +823,10 @@ struct Bdf {
         u.n_jac = (unsigned)__builtin_amdgcn_readlane((int)s.n_jac, src);
     }
     static __device__ __forceinline__ void no_work(Item &s) { s.n_steps = s.n_newton = s.n_lu = s.n_jac = 0u; }
+#ifdef SMC_USER_ROOTS
+    // an item out of the pool (it stands at t0): the event functions there again, no fire yet
+    static __device__ __forceinline__ void root_begin(Item &s, const double *theta, const double *cond) { smc_user_item::root_begin(s, s.D[0], theta, cond); }
+#endif  // SMC_USER_ROOTS
     // counts[k * m + idx], k: accepted steps, Newton iterations, LU factorisations, Jacobians
     static __device__ __forceinline__ void publish_work(unsigned *counts, long long m, long long idx, const Item &s) {
         counts[idx] = s.n_steps;

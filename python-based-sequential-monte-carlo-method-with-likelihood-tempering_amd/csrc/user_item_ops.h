@@ -38,6 +38,9 @@
 #include "reject_bound.h"   // the tail of the early-rejection bound (with philox.h: it re-derives the acceptance uniform),
 #include "solve_sched.h"    // the scheduler the built-in Michaelis-Menten kernel uses
 #define NS SMC_USER_NS
+#ifdef SMC_USER_ROOTS
+#include "user_root.h"      // state-triggered events: the test, the root solve and the choice of the earliest root
+#endif  // SMC_USER_ROOTS
 namespace smc_user_item {
 __device__ __forceinline__ double py_min(double a, double b) { return (b < a) ? b : a; }   // Python's min / max
 __device__ __forceinline__ double py_max(double a, double b) { return (b > a) ? b : a; }
@@ -83,6 +86,23 @@ __device__ __forceinline__ void item_cache_times(It &it, const double *cond, con
     it.t_bound = smc_ev::segment_bound(cond, 0, it.t_end);
     it.t_next = tp[it.i_out].x;
 }
+#ifdef SMC_USER_ROOTS
+// State-triggered events (user_root.h): an item also holds g, the event functions at its last accepted point, t_seg, the start
+// of the segment it is in (a root there fails the solve), and n_fire, the events that have fired.  They are registers: the pool
+// holds only items that have had no attempt, for which root_begin computes them again from (t0, y0) - the numbers item_begin
+// computed, from the same operands through the same function - and the uniform tail reads them from the lane (lane_progress).
+// root_segment: the start of a segment at (it.t, y).
+template <class It>
+__device__ __forceinline__ void root_segment(It &it, const double *y, const double *theta, const double *cond) {
+    smc_root::eval(it.t, y, theta, cond, it.g);
+    it.t_seg = it.t;
+}
+template <class It>
+__device__ __forceinline__ void root_begin(It &it, const double *y, const double *theta, const double *cond) {
+    root_segment(it, y, theta, cond);
+    it.n_fire = 0;
+}
+#endif  // SMC_USER_ROOTS
 #else  // SMC_USER_EVENTS
 template <class It>
 __device__ __forceinline__ void item_cache_times(It &it, const DataRec *tp, int n_t) {
@@ -102,6 +122,12 @@ __device__ __forceinline__ void lane_progress(It &u, const It &s, int src) {
 #ifdef SMC_USER_EVENTS
     u.t_end = smc::lane_value(s.t_end, src);
     u.i_ev = __builtin_amdgcn_readlane(s.i_ev, src);
+#ifdef SMC_USER_ROOTS
+#pragma unroll
+    for (int k = 0; k < smc_root::kRoots; ++k) u.g[k] = smc::lane_value(s.g[k], src);
+    u.t_seg = smc::lane_value(s.t_seg, src);
+    u.n_fire = __builtin_amdgcn_readlane(s.n_fire, src);
+#endif  // SMC_USER_ROOTS
 #endif  // SMC_USER_EVENTS
 }
 template <class It>
@@ -226,6 +252,9 @@ struct Ops {
         item_cache_times(it.s, row(it.e), a.n_t);
 #endif  // SMC_USER_EVENTS
         load_theta(it, particle(it));      // the parameters come from HBM / L2 again, not through the pool
+#ifdef SMC_USER_ROOTS
+        Integ::root_begin(it.s, it.th, cond(it.e));
+#endif  // SMC_USER_ROOTS
     }
     __device__ __forceinline__ int attempt(Item &it) const {
         Integ::attempt(it.s, it.th, cond(it.e), row(it.e), a.rtol, a.atol);

@@ -264,6 +264,45 @@ static bool mentions(const char *user_source, const char *name) { return strstr(
 // geom.n_ev > 0 (smc_set_model_user6): SMC_USER_EVENTS, SMC_USER_EVAT / NEV / NVAL and user_event.h in front, smc_event_value made
 // visible to the user's text, and the kernel file with its SMC_USER_EVENTS blocks (k_..._ev).  The event names and a model
 // without events, or events and a source without smc_user_event, stop with an #error that says so.
+// A source that contains the name smc_user_root has state-triggered events (user_root.h): SMC_USER_ROOTS, and the kernel file
+// with its SMC_USER_ROOTS blocks and its SMC_USER_EVENTS blocks (k_..._rt) - without scheduled events SMC_USER_EVENTS is defined
+// here with SMC_USER_NO_SCHEDULE, for which user_root.h supplies a table that never holds an event.  Such a source defines
+// smc_user_root_dir and smc_user_root_event too, or stops with an #error that says so; the number of event functions and their
+// directions are checked by static_asserts of user_root.h.
+static bool has_roots(const char *user_source) { return mentions(user_source, "smc_user_root"); }
+// The directions of a source's event functions, read from its text: the initialiser list that follows the definition - the
+// first "smc_user_root_dir" that is followed by '[', so that a comment or a use that names the array is passed over - up to the
+// next ';' holds integer literals -1, 0, +1 and nothing else ("" = it does; else the refusal).
+// The compiler cannot check it: the elements of a __device__ array are no constant expressions.
+static std::string root_dir_error(const char *user_source) {
+    const char *p = user_source;
+    for (;;) {
+        p = strstr(p, "smc_user_root_dir");
+        if (!p) break;
+        const char *q = p + strlen("smc_user_root_dir");
+        while (*q == ' ' || *q == '\t') ++q;
+        if (*q == '[') break;
+        p = q;
+    }
+    const char *open = p ? strchr(p, '{') : nullptr, *semi = p ? strchr(p, ';') : nullptr;
+    const char *close = open ? strchr(open, '}') : nullptr;
+    const std::string how = "smc_user_root_dir: the directions are written as a list of the integers -1 (falling), 0 (either) or +1 (rising) "
+                            "behind the first smc_user_root_dir[ of the source";
+    if (!open || !close || (semi && semi < open)) return how;
+    for (const char *q = open + 1; q < close;) {
+        while (q < close && (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')) ++q;
+        if (q == close) break;
+        char *end = nullptr;
+        const long v = strtol(q, &end, 10);
+        if (end == q) return how;
+        if (v < -1 || v > 1) return "smc_user_root_dir: direction " + std::to_string(v) + " is none of -1 (falling), 0 (either), +1 (rising)";
+        q = end;
+        while (q < close && (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')) ++q;
+        if (q < close && *q != ',') return how;
+        if (q < close) ++q;
+    }
+    return "";
+}
 static std::string build_source(const char *user_source, const UserSourceSpec &sp) {
     const UserInputGeom &geom = sp.geom;
     const int n_obs = sp.n_obs, noise = sp.noise;
@@ -283,6 +322,17 @@ static std::string build_source(const char *user_source, const UserSourceSpec &s
     } else if (mentions(user_source, "smc_user_event") || mentions(user_source, "smc_event_value")) {
         s += "#error \"smc_user_event: this model has no events (n_ev = 0) - set it with ev_t / ev_v through smc_set_model_user6\"\n";
     }
+    const bool roots = has_roots(user_source);
+    if (roots) {
+        if (!events) s += "#define SMC_USER_EVENTS 1\n#define SMC_USER_NO_SCHEDULE 1\n";
+        s += "#define SMC_USER_ROOTS 1\n";
+        if (!mentions(user_source, "smc_user_root_dir"))
+            s += "#error \"smc_user_root: a source with state-triggered events defines smc_user_root_dir, the direction of every event function\"\n";
+        else if (!root_dir_error(user_source).empty())
+            s += "#error \"" + root_dir_error(user_source) + "\"\n";
+        if (!mentions(user_source, "smc_user_root_event"))
+            s += "#error \"smc_user_root: a source with state-triggered events defines smc_user_root_event, the jump at an event\"\n";
+    }
     s += "#define SMC_USER_NS " + std::to_string(sp.n_states) + "\n#define SMC_USER_DIM " + std::to_string(sp.dim) + "\n";
     if (n_obs > 0)
         s += "#define SMC_USER_NOBS " + std::to_string(n_obs) + "\n#define SMC_USER_HAS_OBS_VEC " +
@@ -299,7 +349,8 @@ static std::string build_source(const char *user_source, const UserSourceSpec &s
                              "#line 1 \"user_model\"\n" + user_source + "\n";
     s += bdf ? kUserBdfPrelude + text : kUserPreludeLean + text + kUserPreludeIeee + text;
     s += "}  // namespace smc_user_ieee\n";
-    const char *kernel = bdf ? (events ? k_user_bdf_kernel_h_ev : k_user_bdf_kernel_h) : (events ? k_user_rk45_kernel_h_ev : k_user_rk45_kernel_h);
+    const char *kernel = bdf ? (roots ? k_user_bdf_kernel_h_rt : events ? k_user_bdf_kernel_h_ev : k_user_bdf_kernel_h)
+                             : (roots ? k_user_rk45_kernel_h_rt : events ? k_user_rk45_kernel_h_ev : k_user_rk45_kernel_h);
     if (n_obs > 0) s = s + "#include \"user_obs_args.h\"\n" + kernel + "#define SMC_USER_PRED 1\n";
     return s + kernel + k_user_cost_scan_h;
 }
@@ -308,19 +359,24 @@ static std::string build_source(const char *user_source, const UserSourceSpec &s
 static const struct { const char *name, *text; } kUserHeaders[] = {
     {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"reject_bound.h", k_reject_bound_h}, {"solve_sched.h", k_solve_sched_h},
     {"rk45_math.h", k_rk45_math_h}, {"user_item_ops.h", k_user_item_ops_h}, {"user_obs_args.h", k_user_obs_args_h},
-    {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}, {"user_censor.h", k_user_censor_h}};
+    {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}, {"user_censor.h", k_user_censor_h},
+    {"user_root.h", k_user_root_h}};
 constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
 // user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs, user_event.h with one that
 // has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks -, user_censor.h with one that has censored observations
-// - and user_obs_args.h then with its SMC_USER_CENSOR blocks
-static int user_headers(const UserSourceSpec &sp, const char **texts, const char **names) {
+// - and user_obs_args.h then with its SMC_USER_CENSOR blocks -, user_root.h with a source that has state-triggered events - and
+// user_item_ops.h then as it is
+static int user_headers(const char *user_source, const UserSourceSpec &sp, const char **texts, const char **names) {
     const UserInputGeom &geom = sp.geom;
+    const bool roots = has_roots(user_source);
     int n = 0;
     for (const auto &h : kUserHeaders) {
         if ((h.text == k_user_obs_args_h && sp.n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
-            (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !sp.censor))
+            (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !sp.censor) ||
+            (h.text == k_user_root_h && !roots))
             continue;
-        texts[n] = (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev
+        texts[n] = (h.text == k_user_item_ops_h && roots) ? k_user_item_ops_h_rt
+                   : (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev
                    : (h.text == k_user_obs_args_h && sp.censor) ? k_user_obs_args_h_cn : h.text;
         names[n++] = h.name;
     }
@@ -332,7 +388,7 @@ static bool compile_user(const char *user_source, const UserSourceSpec &sp, std:
     const std::string src = build_source(user_source, sp);
     hiprtcProgram prog;
     const char *headers[kUserHeaderCount], *names[kUserHeaderCount];
-    const int n_headers = user_headers(sp, headers, names);
+    const int n_headers = user_headers(user_source, sp, headers, names);
     if (hiprtcCreateProgram(&prog, src.c_str(), "smc_user_model.hip", n_headers, headers, names) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return false;
@@ -820,7 +876,7 @@ int smc_user_model_dump_source_spec(const smc_user_source_spec *spec, const char
     if (!dir || !user_source_spec_of(spec, s, sp)) return 2;
     const std::string src = build_source(s.source, sp);
     const char *texts[kUserHeaderCount], *names[kUserHeaderCount];
-    const int n_headers = user_headers(sp, texts, names);
+    const int n_headers = user_headers(s.source, sp, texts, names);
     for (int i = -1; i < n_headers; ++i) {
         FILE *f = fopen((std::string(dir) + "/" + (i < 0 ? "smc_user_model.hip" : names[i])).c_str(), "w");
         if (!f) return 1;

@@ -69,6 +69,10 @@ struct Item {
 #ifdef SMC_USER_EVENTS
     double t_end;   // scheduled events (user_item_ops.h: item_cache_times): the row's end; t_bound is the SEGMENT's bound
     int i_ev;       // the next event of the row: the first with tau > t
+#ifdef SMC_USER_ROOTS
+    double g[smc_root::kRoots], t_seg;   // state-triggered events (user_item_ops.h: root_segment): the event functions at (t, y); the
+    int n_fire;                          // segment's start; the events that have fired
+#endif  // SMC_USER_ROOTS
 #endif  // SMC_USER_EVENTS
 };
 #ifdef SMC_USER_EVENTS
@@ -149,6 +153,9 @@ __device__ void item_begin(Item &it, const double *theta, const double *cond, co
     }
 #ifdef SMC_USER_EVENTS
     item_cache_times(it, cond, tp, n_t);
+#ifdef SMC_USER_ROOTS
+    root_begin(it, it.y, theta, cond);
+#endif  // SMC_USER_ROOTS
 #else  // SMC_USER_EVENTS
     item_cache_times(it, tp, n_t);
 #endif  // SMC_USER_EVENTS
@@ -222,6 +229,128 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
     double pw = 0.9 * smc::pow_minus_fifth<false>(st.error_norm);
     bool accept = st.error_norm < 1.0;                   // false for a NaN norm: Python's max(0.2, nan) is 0.2
     const bool redo = SMC_USER_USES_DIV && !__builtin_isfinite(st.error_norm);
+#ifdef SMC_USER_ROOTS
+    // State-triggered events (user_root.h; ivp.py's loop body after solver.step()).  The event functions are evaluated at the end
+    // of every attempt - an accepted step needs them, and a select is cheaper than a branch around them - and an accepted step
+    // on which one of them crosses in its direction joins the rare branch.  There, on the K of the stage run that was accepted
+    // (Lean, or the IEEE re-run, after which the event functions are evaluated again on ITS y_new): the root of every active event
+    // on the step's dense output, the earliest one t*, the outputs of the data times <= t* from the same dense output (a data
+    // time equal to t* sees the state before the jump), then y* = sol(t*), the jump smc_user_root_event(k, t*, y*) and the
+    // restart of a new solve_ivp call from (t*, y*): segment_start, the event functions there, t_seg = t*.  A root AT t_bound <
+    // t_end also meets scheduled event i_ev: the triggered jump first, then the scheduled one, then the one restart.  A root at
+    // the row's end finishes the solve.
+    // Failures (status -1: info bit 30, NaN from the first output not served): a root solve that fails (user_root.h: brentq), a
+    // root at the start of its own segment - the jump left the state on a firing surface, and the chain of solve_ivp calls would
+    // stop there for ever -, and a fire beyond SMC_USER_MAX_ROOT_FIRES.
+    // Termination: the loop over the events has kRoots <= 4 passes and each brentq at most 100 iterations.  A fire either fails
+    // the solve or raises n_fire, and n_fire > 256 fails it, so an item has at most 256 triggered restarts besides the
+    // SMC_USER_NEV scheduled ones argued below.  A segment that starts at a fire starts at t* > t_seg (t* == t_seg fails), and
+    // t* <= t_bound, so every segment has positive length and t never decreases; inside a segment the item is the solve it always
+    // was, and Ops::attempt's hard bound on the attempts stays.  No unbounded loop is added.
+    double g_new[smc_root::kRoots];
+    smc_root::eval(t_new, st.y_new, theta, cond, g_new);
+    if (fail || redo || (accept && (smc_root::any_active(it.g, g_new) || it.t_next <= t_new || (t_new - t_bound >= 0 && t_bound < it.t_end)))) {
+        if (fail) {
+            it.status = -1;
+            return;
+        }
+        if (redo) {
+            rk_stages<Ieee>(st, it, t, h, theta, cond, rtol, atol);
+            pw = 0.9 * smc::pow_minus_fifth<false>(st.error_norm);
+            accept = st.error_norm < 1.0;
+            smc_root::eval(t_new, st.y_new, theta, cond, g_new);
+        }
+        const bool fired = accept && smc_root::any_active(it.g, g_new);
+        if (accept && (fired || it.t_next <= t_new)) {
+            double Q[NS][4];      // the quartic dense output, as below
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j)
+                        if (RK_P[j][k] != 0.0) acc += st.K[j][i] * RK_P[j][k];
+                    Q[i][k] = acc;
+                }
+            const double hd = t_new - t;
+            const auto sol = [&](double s, double *yy) {
+                const double x = smc::checked_lean_div(s - t, hd);
+                const double p1 = x, p2 = p1 * x, p3 = p2 * x, p4 = p3 * x;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) {
+                    double acc = 0.0;
+                    acc += Q[i][0] * p1;
+                    acc += Q[i][1] * p2;
+                    acc += Q[i][2] * p3;
+                    acc += Q[i][3] * p4;
+                    yy[i] = hd * acc + it.y[i];
+                }
+            };
+            double t_stop = t_new;
+            int k_fire = -1;
+            if (fired) {
+                k_fire = smc_root::first_root(it.g, g_new, sol, t, t_new, theta, cond, t_stop);
+                if (k_fire < 0 || t_stop == it.t_seg) {
+                    it.status = -1;
+                    return;
+                }
+            }
+            if (it.t_next <= t_stop) {
+                int i_out = it.i_out;
+                DataRec nx = tp[i_out];
+                do {
+                    double yy[NS];
+                    sol(nx.x, yy);
+                    emit(it, yy, theta, cond, nx.x, nx.y);
+                    ++i_out;
+                    nx = tp[i_out];
+                } while (nx.x <= t_stop);
+                it.i_out = i_out;
+                it.t_next = nx.x;
+            }
+            if (fired) {
+                double ys[NS];
+                sol(t_stop, ys);
+                it.t = t_stop;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) it.y[i] = ys[i];
+                smc_user_ieee::smc_user_root_event(k_fire, t_stop, it.y, theta, cond);
+                ++it.n_fire;
+                if (it.n_fire > smc_root::kMaxFires) {
+                    it.status = -1;
+                    return;
+                }
+                if (t_stop - it.t_end >= 0) {      // a root at the row's end
+                    it.status = 1;
+                    return;
+                }
+                if (t_stop - t_bound >= 0) {       // ... at a scheduled event's time (t_bound < t_end here)
+                    smc_user_ieee::smc_user_event(it.i_ev, t_stop, it.y, theta, cond);
+                    ++it.i_ev;
+                    it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+                }
+                segment_start(it, theta, cond, rtol, atol);
+                root_segment(it, it.y, theta, cond);
+                it.status = 0;
+                return;
+            }
+        }
+        // the segment ends at scheduled event i_ev, as below; the next one starts with the event functions at (tau, y)
+        if (accept && t_new - t_bound >= 0 && t_bound < it.t_end) {
+            it.t = t_new;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) it.y[i] = st.y_new[i];
+            smc_user_ieee::smc_user_event(it.i_ev, t_new, it.y, theta, cond);
+            ++it.i_ev;
+            it.t_bound = smc_ev::segment_bound(cond, it.i_ev, it.t_end);
+            segment_start(it, theta, cond, rtol, atol);
+            root_segment(it, it.y, theta, cond);
+            it.status = 0;
+            return;
+        }
+    }
+#else  // SMC_USER_ROOTS
 #ifdef SMC_USER_EVENTS
     // ... and an accepted step that ends a segment in front of an event (t_bound < t_end: the row goes on behind it)
     if (fail || redo || (accept && (it.t_next <= t_new || (t_new - t_bound >= 0 && t_bound < it.t_end)))) {
@@ -295,6 +424,7 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         }
 #endif  // SMC_USER_EVENTS
     }
+#endif  // SMC_USER_ROOTS
     double fac_acc = py_min(10.0, pw);
     fac_acc = it.rejected ? py_min(1.0, fac_acc) : fac_acc;
     const double fac_rej = py_max(0.2, pw);
@@ -306,6 +436,10 @@ __device__ __forceinline__ void item_attempt(Item &it, const double *theta, cons
         it.y[i] = accept ? st.y_new[i] : it.y[i];
         it.f[i] = accept ? st.K[6][i] : it.f[i];
     }
+#ifdef SMC_USER_ROOTS
+#pragma unroll
+    for (int k = 0; k < smc_root::kRoots; ++k) it.g[k] = accept ? g_new[k] : it.g[k];   // ivp.py: g = g_new
+#endif  // SMC_USER_ROOTS
     it.status = (accept && (t_new - t_bound >= 0)) ? 1 : 0;   // base.py:196
 }
 // What user_item_ops.h needs to know about the integrator (see the list at the top of that file).  Pool words 6 ..: y, f; the
@@ -344,6 +478,10 @@ struct Rk45 {
     }
     static __device__ __forceinline__ void no_work(Item &) {}
     static __device__ __forceinline__ void publish_work(unsigned *, long long, long long, const Item &) {}
+#ifdef SMC_USER_ROOTS
+    // an item out of the pool (it stands at t0): the event functions there again, no fire yet
+    static __device__ __forceinline__ void root_begin(Item &s, const double *theta, const double *cond) { smc_user_item::root_begin(s, s.y, theta, cond); }
+#endif  // SMC_USER_ROOTS
 };
 }  // namespace smc_user
 

@@ -198,6 +198,17 @@ class HipEngine:
         which changes y in place at event j and reads its numbers as smc_event_value(cond, j, k).  The solve is the chain of
         solve_ivp calls between the events (include/smc_hip.h); user_models.event_layout states the rules (ValueError for events
         that break them).  events=None leaves the model as it is without them.
+        State-triggered events (a re-dose when a level falls to a threshold, a relay, a tank that overflows) need no
+        argument: a source that contains the name smc_user_root defines
+            __device__ const int smc_user_root_dir[] = {-1, 0};   // per event function: -1 falling, +1 rising, 0 either; 1 .. 4
+            __device__ void smc_user_root(double t, const double *y, const double *theta, const double *cond, double *g);
+            __device__ void smc_user_root_event(int k, double t, double *y, const double *theta, const double *cond);
+        and its solve is the chain of solve_ivp(events=...) calls with every event terminal: the root of an event function that
+        crosses zero in its direction is found on the step's dense output (SciPy's brentq: user_models.brentq), the data times up
+        to and including it see the state before the jump, smc_user_root_event changes y in place, and the integrator starts
+        afresh from there (user_models.root_chain is the reference; include/smc_hip.h has the rules, among them that a jump which
+        leaves the state on a firing surface, or fire number 257 of a solve, fails the solve).  Both functions may call smc_input
+        and smc_event_value where the model has them; it combines with everything above and below.
         Censored observations: censor (n_ex, n_t, n_obs) integer flags beside obs - 0: obs is the measured
         value; -1: left-censored, the true value is <= obs, which holds the lower limit; +1: right-censored, >= obs, the upper limit.
         A censored value contributes log Phi(z) (user_models.censored_loglik is the likelihood, censor_layout the rules: ValueError

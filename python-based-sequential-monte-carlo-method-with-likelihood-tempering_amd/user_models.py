@@ -100,6 +100,148 @@ __device__ void smc_user_event(int j, double t, double *y, const double *theta, 
 }
 """
 
+# State-triggered events (include/smc_hip.h: STATE-TRIGGERED EVENTS).  A level that decays and is re-dosed whenever it falls to a
+# threshold: theta = (k, D, sigma), cond = (y0, L), dC/dt = -k C; event function g = C - L, falling; the event adds D = theta[1].
+# The fire times depend on the parameters: the first at log(y0 / L) / k, then every log((L + D) / L) / k.
+THRESHOLD_REDOSED = r"""
+__device__ void smc_user_y0(const double *theta, const double *cond, double *y) { y[0] = cond[0]; }
+__device__ void smc_user_rhs(double t, const double *y, const double *theta, const double *cond, double *dydt) { dydt[0] = -theta[0] * y[0]; }
+__device__ double smc_user_obs(double t, const double *y, const double *theta, const double *cond) { return y[0]; }
+__device__ const int smc_user_root_dir[] = {-1};
+__device__ void smc_user_root(double t, const double *y, const double *theta, const double *cond, double *g) { g[0] = y[0] - cond[1]; }
+__device__ void smc_user_root_event(int k, double t, double *y, const double *theta, const double *cond) { y[0] += theta[1]; }
+"""
+
+SMC_USER_MAX_ROOTS, SMC_USER_MAX_ROOT_FIRES = 4, 256
+
+
+def brentq(f, a, b, xtol=4 * 2.220446049250313e-16, rtol=4 * 2.220446049250313e-16, maxiter=100, full_output=False):
+    """scipy.optimize.brentq(f, a, b, xtol, rtol, maxiter) restated in Python floats, statement by statement (Zeros/brentq.c) - the
+    text the kernels follow (csrc/user_root.h), with the tolerances solve_ivp's events use as defaults.  Returns the root, with
+    full_output (root, function calls, iterations): bit for bit SciPy's.  Raises ValueError where f(a) and f(b) have one sign or
+    f returns NaN, RuntimeError without convergence within maxiter iterations - where SciPy raises."""
+    import math
+
+    def call(x):
+        v = float(f(x))
+        if math.isnan(v):
+            raise ValueError(f"brentq: the function value at x={x} is NaN; solver cannot continue")
+        return v
+
+    def done(x, calls, it):
+        return (x, calls, it) if full_output else x
+
+    sign = lambda v: math.copysign(1.0, v) < 0
+    xpre, xcur = float(a), float(b)
+    xblk = fblk = spre = scur = 0.0
+    fpre, fcur = call(xpre), call(xcur)
+    calls = 2
+    if fpre == 0:
+        return done(xpre, calls, 0)
+    if fcur == 0:
+        return done(xcur, calls, 0)
+    if sign(fpre) == sign(fcur):
+        raise ValueError("brentq: f(a) and f(b) must have different signs")
+    for it in range(1, int(maxiter) + 1):
+        if fpre != 0 and fcur != 0 and sign(fpre) != sign(fcur):
+            xblk, fblk = xpre, fpre
+            spre = scur = xcur - xpre
+        if abs(fblk) < abs(fcur):
+            xpre, xcur = xcur, xblk
+            xblk = xpre
+            fpre, fcur = fcur, fblk
+            fblk = fpre
+        delta = (xtol + rtol * abs(xcur)) / 2
+        sbis = (xblk - xcur) / 2
+        if fcur == 0 or abs(sbis) < delta:
+            return done(xcur, calls, it)
+        if abs(spre) > delta and abs(fcur) < abs(fpre):
+            if xpre == xblk:      # interpolate
+                stry = -fcur * (xcur - xpre) / (fcur - fpre)
+            else:                 # extrapolate
+                dpre = (fpre - fcur) / (xpre - xcur)
+                dblk = (fblk - fcur) / (xblk - xcur)
+                stry = -fcur * (fblk * dblk - fpre * dpre) / (dblk * dpre * (fblk - fpre))
+            if 2 * abs(stry) < min(abs(spre), 3 * abs(sbis) - delta):      # good short step
+                spre, scur = scur, stry
+            else:                 # bisect
+                spre = scur = sbis
+        else:                     # bisect
+            spre = scur = sbis
+        xpre, fpre = xcur, fcur
+        if abs(scur) > delta:
+            xcur += scur
+        else:
+            xcur += delta if sbis > 0 else -delta
+        fcur = call(xcur)
+        calls += 1
+    raise RuntimeError(f"brentq: failed to converge after {maxiter} iterations")
+
+
+def root_chain(rhs, y0, t_row, root, root_dir, root_event, method="RK45", rtol=1e-3, atol=1e-6, jac=None, scheduled=()):
+    """A solve of a model with state-triggered events (include/smc_hip.h) as the chain of solve_ivp calls a SciPy user writes - the
+    reference the kernels are held to.  rhs(t, y); y0 (ns,); t_row: the row's data times, strictly increasing, t_row[0] the
+    initial time (NaN past the row's end is dropped); root(t, y) -> (n_root,) the event functions, root_dir their directions
+    (-1 falling, 0 either, +1 rising), root_event(k, t, y) -> the state after the jump of event k; scheduled: [(tau, jump)],
+    scheduled events with jump(t, y) -> y, of which those strictly inside the row fire.
+    Every call is solve_ivp(rhs, (a, b), y, method, events = the event functions, all terminal, dense_output=True, rtol, atol[,
+    jac]) with b the next scheduled time or the row's end.  The data times in (a, t_stop] (the first call: [t0, t_stop]) are read
+    from the call's dense output, so a data time equal to a fire time holds the state before the jump.  A call that ends at an
+    event (status 1) is followed by root_event on its end state - the earliest root, on a tie the lowest k - and the next call
+    starts from (t*, y); a root at b meets the scheduled jump after the triggered one.  The rules a chain written by hand
+    leaves open: a root at the start of its own call (the jump left the state on a firing surface; the chain would not move
+    again) raises RuntimeError, and so does fire number SMC_USER_MAX_ROOT_FIRES + 1.
+    Returns {"y": (len, ns) states at the row's times, "fires": [(k, t*)], "steps", "nlu", "njev": totals over the calls}."""
+    import numpy as np
+    from scipy.integrate import solve_ivp
+    tt = np.asarray(t_row, dtype=np.float64)
+    tt = tt[~np.isnan(tt)]
+    t0, t_end = tt[0], tt[-1]
+    ns = np.asarray(y0).size
+    n_root = len(root_dir)
+    events = []
+    for k in range(n_root):
+        ev = (lambda k: lambda t, y: float(np.asarray(root(t, y))[k]))(k)
+        ev.terminal, ev.direction = True, float(root_dir[k])
+        events.append(ev)
+    out = np.full((tt.size, ns), np.nan)
+    y = np.array(y0, dtype=np.float64)
+    fires, steps, nlu, njev = [], 0, 0, 0
+    if t_end == t0:
+        out[0] = y
+        return {"y": out, "fires": fires, "steps": 0, "nlu": 0, "njev": 0}
+    bounds = [(tau, jump) for tau, jump in scheduled if t0 < tau < t_end] + [(t_end, None)]
+    a, first = t0, True
+    for b, jump in bounds:
+        while True:
+            kw = {"jac": jac} if (jac is not None and method != "RK45") else {}
+            sol = solve_ivp(rhs, (a, b), y, method=method, events=events, dense_output=True, rtol=rtol, atol=atol, **kw)
+            if sol.status < 0:
+                raise RuntimeError(f"root_chain: {sol.message}")
+            t_stop = sol.t[-1]
+            steps += sol.t.size - 1
+            nlu += sol.nlu
+            njev += sol.njev
+            take = ((tt > a) | (first & (tt == a))) & (tt <= t_stop)
+            if take.any():
+                out[take] = sol.sol(tt[take]).T
+            first = False
+            y = sol.y[:, -1].copy()
+            if sol.status == 1:
+                k = next(k for k in range(n_root) if sol.t_events[k].size)
+                if t_stop == a:
+                    raise RuntimeError(f"root_chain: event {k} fires at t = {a!r}, the start of its own segment")
+                y = np.array(root_event(k, t_stop, y), dtype=np.float64)
+                fires.append((k, float(t_stop)))
+                if len(fires) > SMC_USER_MAX_ROOT_FIRES:
+                    raise RuntimeError(f"root_chain: more than {SMC_USER_MAX_ROOT_FIRES} fires in one solve")
+            a = t_stop
+            if t_stop == b:
+                break
+        if jump is not None:
+            y = np.array(jump(b, y), dtype=np.float64)
+    return {"y": out, "fires": fires, "steps": steps, "nlu": nlu, "njev": njev}
+
 
 def obs_layout(t, obs, obs_scale=None):
     """The data rules of smc_set_model_user3 (include/smc_hip.h), in NumPy: t (n_ex, n_t); obs (n_ex, n_t, n_obs) with NaN for a
