@@ -327,6 +327,35 @@ typedef struct smc_user_model_spec {
      * In a source spec censor != 0 is the source compiled with SMC_USER_CENSOR (it needs noise = 1 or 2); a dump then also writes
      * user_censor.h. */
     const signed char *censor;
+    /* COUNT OBSERVATIONS (no field: the contract lives in the source, as state-triggered events do): epidemic case counts, colony
+     * counts, read counts, detector events.  A multi-output source (n_obs >= 1) that contains the name smc_user_obs_family defines
+     *     __device__ const int smc_user_obs_family[] = {0, 2, 1};   // one entry per output
+     * 0: a Gaussian output (everything above), 1: Poisson, 2: negative binomial.  The library reads the integer literals behind the
+     * first "smc_user_obs_family[" of the text (a comment or a use of the name is passed over) and hands them to the kernel as
+     * compile-time constants.  Another length than n_obs, an entry that is none of 0, 1, 2, or the name in a one-output source
+     * (n_obs = 0) is refused (check_spec: does not compile) with the rule.  An all-zero list is a model without counts: its earlier
+     * path and bits.
+     *   For a count output the model output f is the MEAN mu and the variance is mu + (b_k mu)^2, b_k the output's proportional
+     * entry (prop_index[k] / prop_fixed[k]): negative binomial b_k > 0, size phi_k = 1 / b_k^2 - b_k is the coefficient of variation
+     * of the extra-Poisson scatter -; Poisson: no prop_index, or prop_index[k] = -1 with prop_fixed[k] = 0.  The additive entry of a
+     * count output is not used and must be fixed at 1, its obs_scale 1; a censor flag on a count is refused.
+     *   A model with a count output takes the noise path, never the sigma rule's: add_index == NULL forms the specification with the
+     * Gaussian outputs from est_sigma / sigma_fixed and the count outputs fixed at 1 (so a negative-binomial output, which needs its
+     * b_k, is refused there, and so is est_sigma != 0 without a Gaussian output).
+     *   Data: a finite value of a count output is a non-negative integer <= 2^53; NaN is "not measured" as ever.
+     *   Likelihood (user_models.count_loglik is the definition in NumPy; y = obs, mu = f):
+     *     Poisson   log p = -c(y) - x,  c(y) = lgamma(y + 1) - y log y + y (the saturated model: a data constant, summed per experiment
+     *               on the host as C_e),  x = y (d - log1p(d)), d = (mu - y) / y  (d < -1/2: log mu - log y for log1p(d));  x = mu for y = 0
+     *     neg. binomial  u = b^2 mu, phi = 1 / b^2:  x = -log p = -[lgamma(y + phi) - lgamma(phi) - lgamma(y + 1) - phi log1p(u) + y log u - y log1p(u)]
+     *   x is clamped at >= 0; mu NaN gives NaN (a failed output's route); mu < 0, mu = +inf, or mu = 0 with y > 0 give logL = -inf;
+     *   mu = 0 with y = 0 gives x = 0; any b_k < 0, or b_k <= 0 on a negative-binomial output: logL = -inf.  m_e, m_ek count Gaussian
+     *   quantified values only:   lk = sum_e [ (-m_e / 2) log(2 pi) - sum_k m_ek log(a_k s_k) - C_e - X_e ].
+     * The Poisson form needs no lgamma on the device and does not cancel at large counts.  Below b around 1e-4 the lgamma difference
+     * of the negative binomial loses digits: declare the output Poisson, or keep the prior off 0.  Early rejection stays exact (the
+     * floors do not depend on the solve); the LDS table does not grow.  smc_user_predict returns lk under this
+     * likelihood, designs give the mean; smc_user_predict_summary with noise = 1 is refused (no Poisson / gamma sampler).
+     * smc_user_obs_family and smc_user_count_check below apply the rules without a GPU.  A dump of such a source also writes
+     * user_count.h. */
 } smc_user_model_spec;
 /* DISPATCH, one rule over the fields (an absent feature takes the earlier path, and its bits with it):
  *   n_obs == 0                        the one-output model; obs_scale, a noise array, inputs, events or censor given: refused;
@@ -356,6 +385,17 @@ int smc_user_input_check(const double *in_t, const double *in_u, int n_ex, int n
 int smc_user_event_check(const double *t, const double *ev_t, const double *ev_v, int n_ex, int n_t, int n_ev, int n_val);
 int smc_user_censor_check(const double *t, const double *obs, const signed char *censor, int n_ex, int n_t, int n_obs, int c_n_ex,
                           int c_n_t, int c_n_obs);
+/* count observations: the family list of a source - the number of entries (the first min(n, cap) of them in family, as written:
+ * whether an entry is 0, 1 or 2 is smc_user_count_check's rule), 0 for a source without the name smc_user_obs_family, -1 for a
+ * list that is not written as one (the reason in smc_last_error(NULL)) ... */
+int smc_user_obs_family(const char *source, int *family, int cap);
+/* ... and the rules of a model with that list (n_family entries): the list against n_obs (0: the one-output model), then - for
+ * t n_ex x n_t and obs n_ex x n_t x n_obs - the data rules, the flags' rules (censor NULL: none), and the rules of COUNT
+ * OBSERVATIONS over obs_scale (NULL: ones), est_sigma and the noise arrays (NULL: absent) and the values.  n_family = 0: nothing
+ * to check. */
+int smc_user_count_check(const int *family, int n_family, const double *t, const double *obs, const signed char *censor,
+                         const double *obs_scale, int n_ex, int n_t, int n_obs, int est_sigma, const int *add_index,
+                         const double *add_fixed, const int *prop_index, const double *prop_fixed);
 int smc_user_set_design_inputs(smc_ctx *ctx, const double *in_t_new, const double *in_u_new, int n_ex_new, int n_knot_new);
 int smc_user_set_design_events(smc_ctx *ctx, const double *ev_t_new, const double *ev_v_new, int n_ex_new, int n_ev_new);
 /* EARLIER ENTRY POINTS, kept with their signatures, return codes and messages: each fills the fields named by its arguments and

@@ -119,6 +119,8 @@ SIGNATURES = {
     "smc_set_model_user7": (cint, [c_ctx, ctypes.c_char_p, cint, cint, c_dp, c_dp, c_dp, c_dp, cint, cint, cint, c_ip, c_dp, c_ip, c_dp,
                                     f64, f64, cint, cint, f64, c_dp, c_dp, cint, cint, c_dp, c_dp, cint, cint, c_i8p]),
     "smc_user_censor_check": (cint, [c_dp, c_dp, c_i8p, cint, cint, cint, cint, cint, cint]),
+    "smc_user_obs_family": (cint, [ctypes.c_char_p, c_ip, cint]),
+    "smc_user_count_check": (cint, [c_ip, cint, c_dp, c_dp, c_i8p, c_dp, cint, cint, cint, cint, c_ip, c_dp, c_ip, c_dp]),
     "smc_user_model_check7": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, ctypes.c_char_p,
                                       cint]),
     "smc_user_model_dump_source7": (cint, [ctypes.c_char_p, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint, cint,

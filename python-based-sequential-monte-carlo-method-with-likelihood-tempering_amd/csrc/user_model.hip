@@ -27,6 +27,7 @@
 #include "solve_sched.h"   // kChunk: the grid is sized in chunks of the shared scheduler
 #include "stage_kernels.h" // launch_aos_to_soa (smc_user_predict)
 #include "user_censor.h"   // censored observations (smc_set_model_user7)
+#include "user_count.h"    // count observations (smc_user_obs_family)
 #include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
 #include "predictive_kernels.h"   // smc_user_predict_summary's kernels
 
@@ -106,7 +107,10 @@ __global__ void __launch_bounds__(256)
 user_finish_noise_kernel(const double *__restrict__ theta, int64_t stride, int64_t n, uint8_t *__restrict__ p0mask,
                          const double *__restrict__ sum_x, const int *__restrict__ info, int n_ex, int n_obs,
                          const double *__restrict__ me, const double *__restrict__ mek, const UserNoise nz,
-                         double *__restrict__ lk_out, SweepCounters *__restrict__ counters) {
+                         double *__restrict__ lk_out, SweepCounters *__restrict__ counters, const double *__restrict__ ce = nullptr,
+                         unsigned negbin = 0) {
+    // ce, negbin: a model with count outputs (user_count.h; nullptr and 0 without) - ce[e] = C_e, the experiment's sum of the
+    // Poisson floors c(y), leaves the bracket after the Gaussian floors; bit k of negbin: output k is negative binomial, b_k > 0
     unsigned long long attempts = 0, failed = 0;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
         const bool masked = p0mask && p0mask[p] == 0;
@@ -116,7 +120,7 @@ user_finish_noise_kernel(const double *__restrict__ theta, int64_t stride, int64
         for (int k = 0; k < n_obs; ++k) {
             const double a = nz.add_index[k] >= 0 ? theta[(int64_t)nz.add_index[k] * stride + p] : nz.add_fixed[k];
             const double b = !nz.prop ? 0.0 : (nz.prop_index[k] >= 0 ? theta[(int64_t)nz.prop_index[k] * stride + p] : nz.prop_fixed[k]);
-            ok = ok && a > 0.0 && b >= 0.0;
+            ok = ok && a > 0.0 && b >= 0.0 && !(((negbin >> k) & 1u) && !(b > 0.0));
             la[k] = log(a * nz.scale[k]);
         }
         if (!ok) {
@@ -131,6 +135,7 @@ user_finish_noise_kernel(const double *__restrict__ theta, int64_t stride, int64
                 const double term = mek[8 * e + k] * la[k];
                 c0 = c0 - term;
             }
+            if (ce) c0 = c0 - ce[e];
             lk += c0 - sum_x[(int64_t)e * n + p];
             const int fl = info[(int64_t)e * n + p];
             attempts += (unsigned)(fl & 0x1fffffff);
@@ -242,6 +247,9 @@ struct UserModel {
     // smc_set_model_user4: the noise model (user_obs_args.h); d_const then holds m_e, sum log s_k and m_ek [8 n_ex]
     bool noise = false;
     UserNoise nz{};
+    // count outputs (user_count.h; the source's smc_user_obs_family): d_const's second n_ex words then hold C_e
+    bool count = false;
+    unsigned negbin = 0;      // bit k: output k is negative binomial
     // smc_set_model_user5: time-varying inputs (user_input.h).  The table lies behind each experiment's cond row, so d_cond holds
     // rows of spec.geom.row_words() doubles; h_rows keeps the data's rows and design_* the inputs of an explicit design
     // smc_set_model_user6: scheduled events (user_event.h).  Their table follows in the same rows; design_ev_* are the events of
@@ -303,6 +311,69 @@ static std::string root_dir_error(const char *user_source) {
     }
     return "";
 }
+// Count observations (user_count.h): the families of a source's outputs, read from its text as the directions above - the integer
+// literals of the initialiser list behind the first "smc_user_obs_family" that is followed by '['.  Returns the number of entries
+// (in fam, any integer: what an entry may be is obs_family_error's rule), 0 for a source without the name, -1 with `how` for a
+// list that is not written so.
+static const char *const kFamilyName = "smc_user_obs_family";
+static int obs_family_list(const char *user_source, std::vector<int> &fam, std::string &how) {
+    fam.clear();
+    if (!user_source || !mentions(user_source, kFamilyName)) return 0;
+    const char *p = user_source;
+    for (;;) {
+        p = strstr(p, kFamilyName);
+        if (!p) break;
+        const char *q = p + strlen(kFamilyName);
+        while (*q == ' ' || *q == '\t') ++q;
+        if (*q == '[') break;
+        p = q;
+    }
+    const char *open = p ? strchr(p, '{') : nullptr, *semi = p ? strchr(p, ';') : nullptr;
+    const char *close = open ? strchr(open, '}') : nullptr;
+    how = "smc_user_obs_family: the families are written as a list of the integers 0 (Gaussian), 1 (Poisson) or 2 (negative binomial) "
+          "behind the first smc_user_obs_family[ of the source";
+    if (!open || !close || (semi && semi < open)) return -1;
+    for (const char *q = open + 1; q < close;) {
+        while (q < close && (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')) ++q;
+        if (q == close) break;
+        char *end = nullptr;
+        const long v = strtol(q, &end, 10);
+        if (end == q || end > close) return -1;
+        fam.push_back((int)(v < -1000 ? -1000 : v > 1000 ? 1000 : v));
+        q = end;
+        while (q < close && (*q == ' ' || *q == '\t' || *q == '\n' || *q == '\r')) ++q;
+        if (q < close && *q != ',') return -1;
+        if (q < close) ++q;
+    }
+    if (fam.empty()) return -1;
+    how.clear();
+    return (int)fam.size();
+}
+// the rules of a family list for a source of n_obs outputs (n_obs = 0: the one-output source); "" = valid
+static std::string obs_family_error(const int *fam, int n_fam, int n_obs) {
+    if (n_fam == 0) return "";
+    if (n_fam < 0 || !fam) return "smc_user_obs_family: the list is malformed";
+    if (n_obs == 0) return "smc_user_obs_family: the name in a one-output source (n_obs = 0) - count outputs need the multi-output source (smc_user_obs_vec, n_obs >= 1)";
+    if (n_fam != n_obs)
+        return "smc_user_obs_family: " + std::to_string(n_fam) + " entries for n_obs = " + std::to_string(n_obs) + " outputs (one entry per output)";
+    for (int k = 0; k < n_fam; ++k)
+        if (fam[k] < 0 || fam[k] > 2)
+            return "smc_user_obs_family: entry " + std::to_string(fam[k]) + " of output " + std::to_string(k) +
+                   " is none of 0 (Gaussian), 1 (Poisson), 2 (negative binomial)";
+    return "";
+}
+// The families of a source for n_obs outputs: fam[k] (0 past n_obs); true if any output is a count.  bad: the refusal, if any.
+static bool source_families(const char *user_source, int n_obs, int fam[kUserMaxObs], std::string &bad) {
+    std::vector<int> list;
+    std::fill_n(fam, kUserMaxObs, 0);
+    const int n = obs_family_list(user_source, list, bad);
+    if (n == 0) return false;
+    if (n > 0) bad = obs_family_error(list.data(), n, n_obs);
+    if (!bad.empty()) return false;
+    bool any = false;
+    for (int k = 0; k < n_obs; ++k) fam[k] = list[k], any = any || list[k] != 0;
+    return any;
+}
 static std::string build_source(const char *user_source, const UserSourceSpec &sp) {
     const UserInputGeom &geom = sp.geom;
     const int n_obs = sp.n_obs, noise = sp.noise;
@@ -340,6 +411,25 @@ static std::string build_source(const char *user_source, const UserSourceSpec &s
     // smc_set_model_user4: the SMC_USER_NOISE blocks of the kernel files and of user_obs_args.h (noise = 2: with log1p and the division)
     // smc_set_model_user7: SMC_USER_CENSOR, user_censor.h in front and user_obs_args.h with its SMC_USER_CENSOR blocks (a noise model always)
     if (n_obs > 0 && noise > 0 && sp.censor) s += "#define SMC_USER_CENSOR 1\n#include \"user_censor.h\"\n";
+    // a source with the name smc_user_obs_family and a count among its outputs: SMC_USER_COUNT, the list as SMC_USER_FAMILY, user_count.h in
+    // front and user_obs_args.h with its SMC_USER_COUNT blocks (a noise model always).  An all-zero list changes nothing.
+    {
+        int fam[kUserMaxObs];
+        std::string bad;
+        if (source_families(user_source, n_obs, fam, bad)) {
+            bool negbin = false;
+            std::string list;
+            for (int k = 0; k < n_obs; ++k) list += (k ? ", " : "") + std::to_string(fam[k]), negbin = negbin || fam[k] == 2;
+            if (noise == 0)
+                s += "#error \"smc_user_obs_family: a model with a count output is compiled with a noise model (noise >= 1)\"\n";
+            else if (negbin && noise < 2)
+                s += "#error \"smc_user_obs_family: a negative-binomial output needs the proportional part (noise = 2): its b_k is the overdispersion\"\n";
+            else
+                s += "#define SMC_USER_COUNT 1\n#define SMC_USER_FAMILY {" + list + "}\n#include \"user_count.h\"\n";
+        } else if (!bad.empty()) {
+            s += "#error \"" + bad + "\"\n";
+        }
+    }
     if (n_obs > 0 && noise > 0) s += std::string("#define SMC_USER_NOISE 1\n#define SMC_USER_NOISE_PROP ") + (noise > 1 ? "1\n" : "0\n");
     if (mentions(user_source, "smc_user_cost")) s += "#define SMC_USER_HAS_COST 1\n#define SMC_USER_LIST_COST 220.0\n#define SMC_USER_SOLO_COST 3700.0\n";
     if (bdf && mentions(user_source, "smc_user_jac")) s += "#define SMC_USER_HAS_JAC 1\n";
@@ -360,24 +450,29 @@ static const struct { const char *name, *text; } kUserHeaders[] = {
     {"sweep_args.h", k_sweep_args_h}, {"philox.h", k_philox_h}, {"reject_bound.h", k_reject_bound_h}, {"solve_sched.h", k_solve_sched_h},
     {"rk45_math.h", k_rk45_math_h}, {"user_item_ops.h", k_user_item_ops_h}, {"user_obs_args.h", k_user_obs_args_h},
     {"user_input.h", k_user_input_h}, {"user_event.h", k_user_event_h}, {"user_censor.h", k_user_censor_h},
-    {"user_root.h", k_user_root_h}};
+    {"user_root.h", k_user_root_h}, {"user_count.h", k_user_count_h}};
 constexpr int kUserHeaderCount = sizeof(kUserHeaders) / sizeof(kUserHeaders[0]);
 // user_obs_args.h goes with a multi-output source only, user_input.h with a model that has inputs, user_event.h with one that
 // has events - and user_item_ops.h then with its SMC_USER_EVENTS blocks -, user_censor.h with one that has censored observations
 // - and user_obs_args.h then with its SMC_USER_CENSOR blocks -, user_root.h with a source that has state-triggered events - and
-// user_item_ops.h then as it is
+// user_item_ops.h then as it is, user_count.h with a source whose smc_user_obs_family holds a count - and user_obs_args.h then
+// with its SMC_USER_COUNT blocks (k_..._ct; with censoring as well the file as it is, k_..._cnct)
 static int user_headers(const char *user_source, const UserSourceSpec &sp, const char **texts, const char **names) {
     const UserInputGeom &geom = sp.geom;
     const bool roots = has_roots(user_source);
+    int fam[kUserMaxObs];
+    std::string bad;
+    const bool count = source_families(user_source, sp.n_obs, fam, bad) && sp.noise > 0;      // user_count.h, and user_obs_args.h with its SMC_USER_COUNT blocks
     int n = 0;
     for (const auto &h : kUserHeaders) {
         if ((h.text == k_user_obs_args_h && sp.n_obs <= 0) || (h.text == k_user_input_h && geom.n_in <= 0) ||
             (h.text == k_user_event_h && geom.n_ev <= 0) || (h.text == k_user_censor_h && !sp.censor) ||
-            (h.text == k_user_root_h && !roots))
+            (h.text == k_user_root_h && !roots) || (h.text == k_user_count_h && !count))
             continue;
         texts[n] = (h.text == k_user_item_ops_h && roots) ? k_user_item_ops_h_rt
                    : (h.text == k_user_item_ops_h && geom.n_ev > 0) ? k_user_item_ops_h_ev
-                   : (h.text == k_user_obs_args_h && sp.censor) ? k_user_obs_args_h_cn : h.text;
+                   : (h.text == k_user_obs_args_h && sp.censor) ? (count ? k_user_obs_args_h_cnct : k_user_obs_args_h_cn)
+                   : (h.text == k_user_obs_args_h && count) ? k_user_obs_args_h_ct : h.text;
         names[n++] = h.name;
     }
     return n;
@@ -544,7 +639,8 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     const int64_t g = (n + 255) / 256;
     if (u->noise)
         hipLaunchKernelGGL(user_finish_noise_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
-                           p0mask, u->d_sum, u->d_info, u->n_ex, u->n_obs, u->d_const, u->d_const + 2 * u->n_ex, u->nz, lk, c->d_counters);
+                           p0mask, u->d_sum, u->d_info, u->n_ex, u->n_obs, u->d_const, u->d_const + 2 * u->n_ex, u->nz, lk, c->d_counters,
+                           u->count ? u->d_const + u->n_ex : nullptr, u->negbin);
     else
         hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
                            c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
@@ -586,7 +682,8 @@ void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
 // censor (flags censor_layout_error has accepted, or nullptr): m_e and the sum count QUANTIFIED values only - a censored value
 // has no density term and its floor is 0.
 static std::string obs_layout(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
-                              std::vector<double> &me, std::vector<double> &ls, const signed char *censor = nullptr) {
+                              std::vector<double> &me, std::vector<double> &ls, const signed char *censor = nullptr,
+                              const int *family = nullptr) {      // family (nullptr: all Gaussian): a count output's values are left out too
     for (int k = 0; k < n_obs; ++k)
         if (scale && !(std::isfinite(scale[k]) && scale[k] > 0.0)) return "obs_scale must be finite and > 0";
     me.assign(n_ex, 0.0);
@@ -609,6 +706,7 @@ static std::string obs_layout(const double *t, const double *obs, const double *
                 if (std::isnan(v)) continue;
                 if (!std::isfinite(v)) return "obs holds an infinite value (NaN marks a value that was not measured)";
                 if (censor && censor[((size_t)e * n_t + i) * n_obs + k] != 0) continue;
+                if (family && family[k] != 0) continue;
                 me[e] += 1.0;
                 ls[e] += scale ? std::log(scale[k]) : 0.0;
             }
@@ -618,22 +716,44 @@ static std::string obs_layout(const double *t, const double *obs, const double *
 
 // the LDS image of user_obs_args.h for data obs_layout has accepted
 // m_ek [8 e + k]: the finite observations of output k at the finite times of experiment e (censor: the quantified ones)
-static std::vector<double> count_mek(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const signed char *censor = nullptr) {
+static std::vector<double> count_mek(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const signed char *censor = nullptr,
+                                     const int *family = nullptr) {      // ... and, of a model with count outputs, the Gaussian ones
     std::vector<double> mek(8 * (size_t)n_ex, 0.0);
     for (int e = 0; e < n_ex; ++e)
         for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
             for (int k = 0; k < n_obs; ++k) {
                 const size_t at = ((size_t)e * n_t + i) * n_obs + k;
-                if (!std::isnan(obs[at]) && !(censor && censor[at] != 0)) mek[8 * (size_t)e + k] += 1.0;
+                if (!std::isnan(obs[at]) && !(censor && censor[at] != 0) && !(family && family[k] != 0)) mek[8 * (size_t)e + k] += 1.0;
             }
     return mek;
+}
+
+// c(y) = lgamma(y + 1) - y log y + y, minus the log-probability of the saturated Poisson model at the count y (user_count.h;
+// user_models.count_floor is the same in NumPy): as written up to y = 32, where nothing cancels yet, and from there on by its
+// Stirling series 1/2 log(2 pi y) + 1/(12 y) - 1/(360 y^3) + 1/(1260 y^5) - 1/(1680 y^7), whose next term is below 1e-16 - the
+// three terms of the definition reach 1e7 at y = 1e6 and would leave c(y), a number below 10, with an error of 1e-9.
+static double count_floor(double y) {
+    if (y < 32.0) return y > 0.0 ? (std::lgamma(y + 1.0) - y * std::log(y)) + y : 0.0;
+    const double r = 1.0 / y, r2 = r * r;
+    return 0.5 * std::log(6.283185307179586 * y) + r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
+}
+// C_e: the sum of c(y) over the Poisson values of experiment e, for data the rules have accepted
+static std::vector<double> count_floor_sums(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const int *family) {
+    std::vector<double> ce((size_t)n_ex, 0.0);
+    for (int e = 0; e < n_ex; ++e)
+        for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
+            for (int k = 0; k < n_obs; ++k) {
+                const double v = obs[((size_t)e * n_t + i) * n_obs + k];
+                if (family[k] == 1 && !std::isnan(v)) ce[e] += count_floor(v);
+            }
+    return ce;
 }
 
 // flagged: the image of a model compiled with SMC_USER_CENSOR - records of obs_rec_words_censor(n_obs) words, the last one the
 // flags of the record's outputs (user_censor.h); censor: the flags (nullptr: none set, a design's image)
 static std::vector<double> build_obs_image(const double *t, const double *obs, const double *scale, int n_ex, int n_t, int n_obs,
                                            const std::vector<double> &me, const std::vector<double> &ls, const UserNoise *nz = nullptr,
-                                           bool flagged = false, const signed char *censor = nullptr) {
+                                           bool flagged = false, const signed char *censor = nullptr, const int *family = nullptr) {
     const int R = flagged ? obs_rec_words_censor(n_obs) : obs_rec_words(n_obs), at = obs_table_at(n_ex);
     std::vector<double> img((size_t)at + (size_t)n_ex * (n_t + 1) * R + (nz ? (size_t)obs_noise_words(n_ex) : 0), 0.0);
     if (nz) {      // the noise block (user_obs_args.h)
@@ -645,7 +765,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
             b[24 + k] = (k < n_obs && nz->prop) ? nz->prop_fixed[k] : 0.0;
             b[32 + k] = k < n_obs ? nz->scale[k] : 1.0;
         }
-        const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor);
+        const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor, family);
         std::copy(mek.begin(), mek.end(), b + kNoiseHdr);
     }
     for (int k = 0; k < kObsHdrMe; ++k) img[k] = (scale && k < n_obs) ? 1.0 / scale[k] : 1.0;
@@ -1124,6 +1244,74 @@ int smc_user_noise_check(int n_obs, int dim, const int *add_index, const double 
     return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_noise_check: " + bad).c_str());
 }
 
+// The rules of a model with count outputs (include/smc_hip.h: COUNT OBSERVATIONS; user_models.count_layout is the same in NumPy),
+// for t and obs that obs_layout accepts and flags that censor_layout_error accepts (nullptr: none): the family list (fam, n_fam
+// entries as obs_family_list returns them) against n_obs; per count output the scale (obs_scale nullptr: ones), the additive
+// entry (add_index nullptr: the sigma rule, under which a count output stands at fixed 1) and the proportional entry (prop_index
+// nullptr: none); est_sigma under the sigma rule; then the values and the flags, the first offence in row-major order.
+// "" = valid, else what is wrong.
+static std::string count_rules_error(const int *fam, int n_fam, const double *t, const double *obs, const signed char *censor,
+                                     const double *obs_scale, int n_ex, int n_t, int n_obs, int est_sigma, const int *add_index,
+                                     const double *add_fixed, const int *prop_index, const double *prop_fixed) {
+    const std::string bad = obs_family_error(fam, n_fam, n_obs);
+    if (!bad.empty() || n_fam == 0) return bad;
+    bool gaussian = false;
+    for (int k = 0; k < n_obs; ++k) {
+        gaussian = gaussian || fam[k] == 0;
+        if (fam[k] == 0) continue;
+        const std::string o = "output " + std::to_string(k) + ": ";
+        if (obs_scale && obs_scale[k] != 1.0) return o + "the obs_scale of a count output must be 1";
+        if (add_index && !(add_index[k] == -1 && add_fixed && add_fixed[k] == 1.0))
+            return o + "the additive entry of a count output must be fixed at 1 (it is not used)";
+        const bool has_b = prop_index && !(prop_index[k] == -1 && prop_fixed && prop_fixed[k] == 0.0);
+        if (fam[k] == 1 && has_b) return o + "a Poisson output takes no proportional entry (absent, or fixed at 0)";
+        if (fam[k] == 2 && !has_b)
+            return o + "a negative-binomial output needs a proportional entry (its b_k: a parameter, or fixed > 0)";
+    }
+    if (!add_index && est_sigma && !gaussian)
+        return "est_sigma without a noise model and no Gaussian output: the last parameter would be a noise level that nothing uses";
+    if (!t || !obs) return "NULL t or obs";
+    for (int e = 0; e < n_ex; ++e)
+        for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
+            for (int k = 0; k < n_obs; ++k) {
+                const size_t at = ((size_t)e * n_t + i) * n_obs + k;
+                const double v = obs[at];
+                if (fam[k] == 0 || std::isnan(v)) continue;
+                const std::string where = " at row " + std::to_string(e) + ", time " + std::to_string(i) + ", output " + std::to_string(k);
+                if (v < 0.0) return "obs holds a negative value on a count output" + where;
+                if (v > 9007199254740992.0) return "obs holds a value above 2^53 on a count output" + where;
+                if (v != std::floor(v)) return "obs holds a value that is not an integer on a count output" + where;
+                if (censor && censor[at] != 0) return "censor flags a value of a count output" + where + " (censored counts are not supported)";
+            }
+    return "";
+}
+int smc_user_obs_family(const char *source, int *family, int cap) {
+    std::vector<int> fam;
+    std::string how;
+    const int n = obs_family_list(source, fam, how);
+    if (n < 0) {
+        (void)smc_fail(nullptr, how.c_str());
+        return -1;
+    }
+    for (int k = 0; k < n && k < cap && family; ++k) family[k] = fam[k];
+    return n;
+}
+int smc_user_count_check(const int *family, int n_family, const double *t, const double *obs, const signed char *censor,
+                         const double *obs_scale, int n_ex, int n_t, int n_obs, int est_sigma, const int *add_index,
+                         const double *add_fixed, const int *prop_index, const double *prop_fixed) {
+    std::string bad = obs_family_error(family, n_family, n_obs);
+    if (bad.empty() && n_family > 0) {
+        std::vector<double> m, l;
+        if (n_ex < 1 || n_t < 1) bad = "bad data shape";
+        if (bad.empty()) bad = (t && obs) ? obs_layout(t, obs, nullptr, n_ex, n_t, n_obs, m, l) : std::string("NULL t or obs");
+        if (bad.empty() && censor) bad = censor_layout_error(t, obs, censor, n_ex, n_t, n_obs, n_ex, n_t, n_obs);
+        if (bad.empty())
+            bad = count_rules_error(family, n_family, t, obs, censor, obs_scale, n_ex, n_t, n_obs, est_sigma, add_index, add_fixed, prop_index,
+                                    prop_fixed);
+    }
+    return bad.empty() ? 0 : smc_fail(nullptr, ("smc_user_count_check: " + bad).c_str());
+}
+
 // What the device part needs of a smc_user_model_spec: user_model_plan forms it, the one place where the rules live by which an
 // absent feature takes the earlier path, and its bits with it.
 struct UserModelPlan {
@@ -1135,6 +1323,8 @@ struct UserModelPlan {
     double sigma_fixed = 0.0;
     bool in = false, ev = false;      // inputs, events: the spec's in_* and ev_* fields
     const signed char *censor = nullptr;      // flags with at least one set, which censor_layout_error has accepted
+    bool count = false;      // a count among the outputs (the source's smc_user_obs_family): the noise path always
+    int family[kUserMaxObs] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // The spec as a plan, or the failure.  Messages about the arguments' consistency carry `who`, the called function; who == nullptr:
@@ -1145,6 +1335,12 @@ static int user_model_plan(smc_ctx *c, const smc_user_model_spec &s, const char 
     const bool inputs = s.n_in != 0, events = s.n_ev != 0;
     const std::string gen = censored ? "smc_set_model_user7" : events ? "smc_set_model_user6" : "smc_set_model_user5";
     const std::string me = who ? who : gen;
+    std::vector<int> fam_list;      // count outputs: the families come with the source
+    std::string fam_bad;
+    const int n_fam = obs_family_list(s.source, fam_list, fam_bad);
+    if (fam_bad.empty()) fam_bad = obs_family_error(fam_list.data(), n_fam, s.n_obs == 0 ? 0 : user_obs_ok(s.n_obs) ? s.n_obs : n_fam);
+    if (!fam_bad.empty()) return smc_fail(c, (me + ": " + fam_bad).c_str());
+    const bool counted = std::any_of(fam_list.begin(), fam_list.end(), [](int f) { return f != 0; });
     if (s.n_obs == 0) {      // the one-output model: none of the later features
         if (s.obs_scale || s.add_index || s.add_fixed || s.prop_index || s.prop_fixed || inputs || s.in_t || s.in_u || events || s.ev_t || s.ev_v || s.censor)
             return smc_fail(c, (me + ": n_obs = 0 (the one-output model) with obs_scale, a noise model, inputs, events or censor given").c_str());
@@ -1160,6 +1356,16 @@ static int user_model_plan(smc_ctx *c, const smc_user_model_spec &s, const char 
         if (!bad.empty()) return smc_fail(c, ("smc_set_model_user7: " + bad).c_str());
         p.censor = s.censor;
     }
+    if (counted) {      // the data's own rules first, then those of the counts
+        std::vector<double> m, l;
+        std::string bad = (s.t && s.obs && s.n_ex >= 1 && s.n_t >= 1) ? obs_layout(s.t, s.obs, s.obs_scale, s.n_ex, s.n_t, s.n_obs, m, l) : std::string("NULL t or obs");
+        if (bad.empty())
+            bad = count_rules_error(fam_list.data(), n_fam, s.t, s.obs, p.censor, s.obs_scale, s.n_ex, s.n_t, s.n_obs, s.est_sigma, s.add_index,
+                                    s.add_fixed, s.prop_index, s.prop_fixed);
+        if (!bad.empty()) return smc_fail(c, (me + ": " + bad).c_str());
+        p.count = true;
+        std::copy(fam_list.begin(), fam_list.end(), p.family);
+    }
     if (!events && (s.ev_t || s.ev_v))
         return smc_fail(c, ((who ? who : censored ? gen : "smc_set_model_user6") + std::string(": n_ev = 0 with ev_t or ev_v given (both must be NULL)")).c_str());
     if (!inputs && (s.in_t || s.in_u)) return smc_fail(c, (me + ": n_in = 0 with in_t or in_u given (both must be NULL)").c_str());
@@ -1172,15 +1378,18 @@ static int user_model_plan(smc_ctx *c, const smc_user_model_spec &s, const char 
         if (s.add_fixed || s.prop_index || s.prop_fixed)
             return smc_fail(c, (me + ": add_index is NULL (the sigma rule) and another part of a noise model is given").c_str());
         p.est_sigma = s.est_sigma, p.sigma_fixed = s.sigma_fixed;
-        if (!censored) return 0;
-        if (!s.est_sigma && !(std::isfinite(s.sigma_fixed) && s.sigma_fixed > 0.0)) return smc_fail(c, (me + ": sigma_fixed must be finite and > 0").c_str());
+        if (!censored && !counted) return 0;
+        const bool gaussian = std::any_of(p.family, p.family + s.n_obs, [](int f) { return f == 0; });
+        if (gaussian && !s.est_sigma && !(std::isfinite(s.sigma_fixed) && s.sigma_fixed > 0.0)) return smc_fail(c, (me + ": sigma_fixed must be finite and > 0").c_str());
         std::fill_n(sigma_index, kUserMaxObs, s.est_sigma ? c->dim - 1 : -1);
         std::fill_n(sigma_value, kUserMaxObs, s.est_sigma ? 0.0 : s.sigma_fixed);
+        for (int k = 0; k < kUserMaxObs; ++k)
+            if (p.family[k] != 0) sigma_index[k] = -1, sigma_value[k] = 1.0;      // a count output: fixed 1, not used
         add_index = sigma_index, add_fixed = sigma_value;
     }
     const std::string bad = noise_spec_error(s.n_obs, c->dim, add_index, add_fixed, s.prop_index, s.prop_fixed);
     if (!bad.empty()) return smc_fail(c, ((who ? who : censored || events ? gen : inputs ? "smc_set_model_user5" : "smc_set_model_user4") + (": " + bad)).c_str());
-    if (!s.prop_index && !censored) {      // one sigma for every output: the sigma rule's path and its bits
+    if (!s.prop_index && !censored && !counted) {      // one sigma for every output: the sigma rule's path and its bits
         bool last = true, fixed = true;
         for (int k = 0; k < s.n_obs; ++k) {
             last = last && add_index[k] == c->dim - 1;
@@ -1213,6 +1422,7 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     const bool multi = plan.multi;
     const UserNoise *nz = plan.noise ? &plan.nz : nullptr;
     const signed char *censor = plan.censor;
+    const int *family = plan.count ? plan.family : nullptr;
     const UserInputs inputs{s.in_t, s.in_u, s.n_in, s.n_knot}, *in = plan.in ? &inputs : nullptr;
     const UserEvents events_{s.ev_t, s.ev_v, s.n_ev, s.n_val}, *ev = plan.ev ? &events_ : nullptr;
     if (!s.source) return smc_fail(c, "smc_set_model_user: NULL source");
@@ -1221,8 +1431,11 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     if (multi && !user_obs_ok(n_obs)) return smc_fail(c, "smc_set_model_user3: n_obs out of range (1 .. SMC_USER_MAX_OBS)");
     if (n_ex < 1 || n_t < 1 || n_cond < 0) return smc_fail(c, "smc_set_model_user: bad data shape");
     std::vector<double> me, ls;
-    std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, censor) : std::string("NULL t or obs");
+    std::string bad = (t && obs) ? obs_layout(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, censor, family) : std::string("NULL t or obs");
     if (multi && !bad.empty()) return smc_fail(c, ("smc_set_model_user3: " + bad).c_str());
+    // count outputs: the words that hold the sum of log s_k, which a noise model does not read, hold C_e (user_count.h) - in the
+    // image and in the constants of user_finish_noise_kernel alike.  The image does not grow.
+    if (family) ls = count_floor_sums(t, obs, n_ex, n_t, n_obs, family);
     if (multi && !nz && user_lds_bytes3(n_states, n_ex, n_t, n_obs) > kUserLdsCap)
         return smc_fail(c, "smc_set_model_user3: data set too large for the kernel's LDS table ((8 + 2 n_ex + n_ex (n_t + 1) "
                            "(n_obs + 2 rounded down to even)) x 8 B + pools > 150 KB)");
@@ -1299,7 +1512,7 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
             k[n_ex + e] = multi ? ls[e] : 0.0;
         }
         if (nz) {      // user_finish_noise_kernel: m_ek follows
-            const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor);
+            const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor, family);
             k.insert(k.end(), mek.begin(), mek.end());
         }
         ok = ok && hipMalloc(&u->d_const, k.size() * sizeof(double)) == hipSuccess &&
@@ -1309,7 +1522,7 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
                 if (me[e] != (double)n_t) bad = "a missing observation (NaN)";
         }
         if (bad.empty()) {
-            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz, censor != nullptr, censor);
+            const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz, censor != nullptr, censor, family);
             u->img_len = (int)img.size();
             ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
                  hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
@@ -1338,6 +1551,10 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     if (nz) {
         u->noise = true;
         u->nz = *nz;
+    }
+    if (family) {
+        u->count = true;
+        for (int k = 0; k < n_obs; ++k) u->negbin |= family[k] == 2 ? 1u << k : 0u;
     }
     {   // occupancy of the compiled kernel with its pool in LDS
         int nb = 0;
@@ -1718,6 +1935,9 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     for (int j = 0; j < n_probs; ++j)
         if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return smc_fail(c, "smc_user_predict_summary: a probability outside [0, 1]");
     if (!mean || !sd || !lower || !upper || !n_finite) return smc_fail(c, "smc_user_predict_summary: NULL result array");
+    if (noise != 0 && u->count)
+        return smc_fail(c, "smc_user_predict_summary: noise = 1 on a model with a count output: replicated count draws need a Poisson / gamma "
+                           "sampler on the Philox stream, which the library does not have (noise = 0 gives the bands of the mean)");
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     if (n_failed) *n_failed = 0;
     if (attempts) *attempts = 0;

@@ -114,6 +114,17 @@ __device__ __forceinline__ void emit(double &sr2, double *&pred, const double *y
 // proportional part (SMC_USER_NOISE_PROP 1), q_k = (b_k / (a_k s_k))^2; then u = q_k f^2 and x = 1/2 log1p(u) + r^2 w_k / (1 + u):
 // one log1p and one division per observed value.  Without it x = r^2 w_k and neither is compiled.
 constexpr int kProp = SMC_USER_NOISE_PROP;
+#ifdef SMC_USER_COUNT
+// Count observations (user_count.h): output k is Gaussian (family 0: everything as without counts), Poisson (1) or negative
+// binomial (2).  The list is the source's smc_user_obs_family, handed over by the library as SMC_USER_FAMILY: compile-time
+// constants, so that the unrolled loops over k below keep, per output, only its family's code.  A count output's additive entry
+// is fixed 1 and its scale 1: w_k is not used and q_k = b_k^2.
+__device__ constexpr int family_of(int k) {
+    constexpr int f[] = SMC_USER_FAMILY;
+    static_assert(sizeof(f) / sizeof(f[0]) == kObs, "smc_user_obs_family: one entry per output");
+    return f[k];
+}
+#endif  // SMC_USER_COUNT
 struct Noise {
     double w[kObs];
 #if SMC_USER_NOISE_PROP
@@ -147,6 +158,12 @@ __device__ __forceinline__ bool noise_valid(const double *th, int n_ex, int n_t)
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < kObs; ++k) ok = ok && noise_add(th, k, n_ex, n_t) > 0.0 && (!kProp || noise_prop(th, k, n_ex, n_t) >= 0.0);
+#ifdef SMC_USER_COUNT
+    // ... and b_k > 0 on a negative-binomial output (a source with one is compiled with the proportional part)
+#pragma unroll
+    for (int k = 0; k < kObs; ++k)
+        if (family_of(k) == smc_cnt::kNegBin) ok = ok && noise_prop(th, k, n_ex, n_t) > 0.0;
+#endif  // SMC_USER_COUNT
     return ok;
 }
 // the item's weights from its particle's parameters; zeros (no excess at all) for parameters that make logL -inf
@@ -221,6 +238,18 @@ __device__ __forceinline__ void emit_noise(double &sx, double *&pred, const Nois
             continue;
         }
 #endif  // SMC_USER_CENSOR
+#ifdef SMC_USER_COUNT
+        if (family_of(k) != smc_cnt::kGaussian) {      // a count: its excess over the floor, behind a call; no flag stands on it
+            if (obs[k] == obs[k]) {
+#if SMC_USER_NOISE_PROP
+                sx += family_of(k) == smc_cnt::kPoisson ? smc_cnt::poisson_excess(obs[k], m[k]) : smc_cnt::negbin_excess(obs[k], m[k], nz.q[k]);
+#else
+                sx += smc_cnt::poisson_excess(obs[k], m[k]);
+#endif
+            }
+            continue;
+        }
+#endif  // SMC_USER_COUNT
 #if SMC_USER_NOISE_PROP
         double x;
         if (FUSE) {
@@ -263,6 +292,9 @@ __device__ __forceinline__ double noise_floor_of(int e, const double *la, int n_
         const double term = mek(e, k, n_ex, n_t) * la[k];
         c0 = c0 - term;
     }
+#ifdef SMC_USER_COUNT
+    c0 = c0 - sum_log_scale(e, n_ex);      // C_e, the Poisson floors of the experiment (user_count.h: the words a noise model does not read)
+#endif  // SMC_USER_COUNT
     return c0;
 }
 #endif

@@ -214,7 +214,17 @@ class HipEngine:
         A censored value contributes log Phi(z) (user_models.censored_loglik is the likelihood, censor_layout the rules: ValueError
         for flags that break them, censor_data makes such data).  With a flag set the model takes the noise path; noise=None then
         stands for every output at the last parameter (est_sigma) or fixed at sigma_fixed.  Combines with everything above.
-        censor=None or all zeros leaves the model as it is without them.  Every feature is a group of fields of one
+        censor=None or all zeros leaves the model as it is without them.
+        Count observations (case counts, colony counts, read counts) need no argument either: a source that contains the name
+        smc_user_obs_family defines
+            __device__ const int smc_user_obs_family[] = {0, 2, 1};   // per output: 0 Gaussian, 1 Poisson, 2 negative binomial
+        For a count output the model output is the MEAN and the variance is mean + (b_k mean)^2, b_k the output's entry of
+        noise["proportional"] (negative binomial: a parameter or fixed > 0; Poisson: absent or ("fixed", 0.0)); its additive
+        entry must be ("fixed", 1.0) and its obs_scale 1 (they are not used), its finite values non-negative integers, and it
+        takes no censor flag.  The model takes the noise path; noise=None stands for the Gaussian outputs at est_sigma /
+        sigma_fixed and the counts at fixed 1.  user_models.count_loglik is the likelihood, count_layout the rules (ValueError
+        for what breaks them), obs_family reads the list; predictive_summary(noise=True) is refused for such a model.  An
+        all-zero list, or no such name, leaves the model as it is.  Every feature is a group of fields of one
         smc_user_model_spec, set by smc_set_model_user_spec; an absent feature takes the path, and gives the bits, it always had."""
         if method not in B.USER_METHODS:
             raise ValueError(f"set_model_user: method must be one of {sorted(B.USER_METHODS)}, not {method!r}")
@@ -254,6 +264,12 @@ class HipEngine:
         if events is not None:
             ev_t, ev_v, n_val = self._events("set_model_user", events, t)
             n_ev = ev_t.shape[1]
+        # count outputs: the families come with the source (smc_user_obs_family); the same checks as the library's
+        from .user_models import obs_family, count_layout
+        family = obs_family(source)
+        if family is not None:
+            count_layout(t, obs, family, noise, scale if multi else None, censor, bool(est_sigma), self.dim)
+        self.user_family = family
         # one description by field name (include/smc_hip.h: smc_user_model_spec); n_obs = 0: the one-output model.  `keep` holds the
         # arrays the struct points to until the call has returned
         keep = []

@@ -444,6 +444,226 @@ def censor_data(values, lower=None, upper=None):
     return obs, (above.astype(np.int8) - below.astype(np.int8))
 
 
+# Count observations (include/smc_hip.h: COUNT OBSERVATIONS).  An SIR epidemic with weekly case counts: theta = (beta, gamma, b),
+# cond = (N, I0); states S, I and the accumulator A of new infections, which a scheduled event resets at every report time - a data
+# time equal to an event time sees the state before the jump, i.e. the week's incidence.  The one output is negative binomial with
+# b = theta[2] estimated (noise={"additive": [("fixed", 1.0)], "proportional": [("param", 2)]}).
+SIR_WEEKLY_CASES = r"""
+__device__ const int smc_user_obs_family[] = {2};
+__device__ void smc_user_y0(const double *theta, const double *cond, double *y) { y[0] = cond[0] - cond[1]; y[1] = cond[1]; y[2] = 0.0; }
+__device__ void smc_user_rhs(double t, const double *y, const double *theta, const double *cond, double *dydt) {
+    const double inf = theta[0] * y[0] * y[1] / cond[0];
+    dydt[0] = -inf;
+    dydt[1] = inf - theta[1] * y[1];
+    dydt[2] = inf;
+}
+__device__ void smc_user_obs_vec(double t, const double *y, const double *theta, const double *cond, double *out) { out[0] = y[2]; }
+__device__ void smc_user_event(int j, double t, double *y, const double *theta, const double *cond) { y[2] = 0.0; }
+"""
+
+OBS_FAMILY_NAMES = {0: "Gaussian", 1: "Poisson", 2: "negative binomial"}
+
+
+def obs_family(source):
+    """The family list of a source (include/smc_hip.h: COUNT OBSERVATIONS), read as the library reads it (smc_user_obs_family):
+    the integer literals of the initialiser list behind the first "smc_user_obs_family" that is followed by "[" - a comment or a
+    use of the name is passed over.  Returns the entries as written (whether an entry is 0, 1 or 2 is count_layout's rule), None
+    for a source without the name; raises ValueError, in the library's words, for a list that is not written as one."""
+    import re
+    name = "smc_user_obs_family"
+    if name not in source:
+        return None
+    how = ("obs_family: smc_user_obs_family: the families are written as a list of the integers 0 (Gaussian), 1 (Poisson) or 2 "
+           "(negative binomial) behind the first smc_user_obs_family[ of the source")
+    m = re.search(name + r"[ \t]*\[", source)
+    rest = source[m.start():] if m else source[source.index(name):]
+    o, sc = rest.find("{"), rest.find(";")
+    c = rest.find("}", o) if o >= 0 else -1
+    if o < 0 or c < 0 or (0 <= sc < o):
+        raise ValueError(how)
+    body = rest[o + 1:c]
+    if not re.fullmatch(r"\s*[+-]?\d+\s*(,\s*[+-]?\d+\s*)*,?\s*", body):
+        raise ValueError(how)
+    return [max(-1000, min(1000, int(v))) for v in re.findall(r"[+-]?\d+", body)]
+
+
+def count_layout(t, obs, family, noise=None, obs_scale=None, censor=None, est_sigma=False, dim=None):
+    """The rules of a model with count outputs (include/smc_hip.h: COUNT OBSERVATIONS), in NumPy, for t (n_ex, n_t) and obs (n_ex,
+    n_t, n_obs) that obs_layout accepts (a 2-D obs: the one-output model, which has no count outputs) and flags that censor_layout
+    accepts: family (obs_family's list; None: nothing to check) has one entry 0, 1 or 2 per output; a count output has obs_scale
+    1, the additive entry ("fixed", 1.0), no proportional entry or ("fixed", 0.0) if Poisson and one (a parameter, or fixed > 0) if
+    negative binomial; noise=None with est_sigma needs a Gaussian output; a finite value of a count output is a non-negative integer
+    <= 2^53 and carries no censor flag.  Returns {"family": (n_obs,) int, "counts": (n_ex, n_obs) the values of the count outputs,
+    "floor": (n_ex,) C_e, the sum of count_floor over the Poisson values}; raises ValueError, in the library's words
+    (smc_user_count_check), for what the library refuses - the first offence in row-major order."""
+    import numpy as np
+    t = np.asarray(t, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    if family is None:
+        return None
+    fam = [int(v) for v in family]
+    n_fam = len(fam)
+    n_obs = obs.shape[2] if obs.ndim == 3 else 0
+    if n_obs == 0:
+        raise ValueError("count_layout: smc_user_obs_family: the name in a one-output source (n_obs = 0) - count outputs need the "
+                         "multi-output source (smc_user_obs_vec, n_obs >= 1)")
+    if n_fam != n_obs:
+        raise ValueError(f"count_layout: smc_user_obs_family: {n_fam} entries for n_obs = {n_obs} outputs (one entry per output)")
+    for k, f in enumerate(fam):
+        if f not in (0, 1, 2):
+            raise ValueError(f"count_layout: smc_user_obs_family: entry {f} of output {k} is none of 0 (Gaussian), 1 (Poisson), "
+                             "2 (negative binomial)")
+    n_t_e = obs_layout(t, obs)["n_t_e"]
+    if censor is not None:
+        censor_layout(t, obs, censor)
+    ai = af = pi = pf = None
+    if noise is not None:
+        ai, af, pi, pf = noise_layout(noise, n_obs, int(dim) if dim is not None else 1 << 30)
+    scale = None if obs_scale is None else np.asarray(obs_scale, dtype=np.float64).reshape(-1)
+    for k, f in enumerate(fam):
+        if f == 0:
+            continue
+        if scale is not None and scale[k] != 1.0:
+            raise ValueError(f"count_layout: output {k}: the obs_scale of a count output must be 1")
+        if ai is not None and not (ai[k] == -1 and af[k] == 1.0):
+            raise ValueError(f"count_layout: output {k}: the additive entry of a count output must be fixed at 1 (it is not used)")
+        has_b = pi is not None and not (pi[k] == -1 and pf[k] == 0.0)
+        if f == 1 and has_b:
+            raise ValueError(f"count_layout: output {k}: a Poisson output takes no proportional entry (absent, or fixed at 0)")
+        if f == 2 and not has_b:
+            raise ValueError(f"count_layout: output {k}: a negative-binomial output needs a proportional entry (its b_k: a "
+                             "parameter, or fixed > 0)")
+    if noise is None and est_sigma and 0 not in fam:
+        raise ValueError("count_layout: est_sigma without a noise model and no Gaussian output: the last parameter would be a noise "
+                         "level that nothing uses")
+    n_ex, n_t = t.shape
+    inside = (np.arange(n_t)[None, :] < n_t_e[:, None])[:, :, None]
+    is_count = (np.asarray(fam) != 0)[None, None, :]
+    seen = inside & is_count & ~np.isnan(obs)
+    v = np.where(seen, obs, 0.0)
+    neg, big, frac = seen & (v < 0), seen & (v > 2.0 ** 53), seen & (v != np.floor(v))
+    flag = seen & (np.asarray(censor) != 0) if censor is not None else np.zeros_like(seen)
+    bad = neg | big | frac | flag
+    if bad.any():
+        e, i, k = (int(x) for x in np.unravel_index(int(np.flatnonzero(bad)[0]), bad.shape))
+        where = f" at row {e}, time {i}, output {k}"
+        if neg[e, i, k]:
+            raise ValueError("count_layout: obs holds a negative value on a count output" + where)
+        if big[e, i, k]:
+            raise ValueError("count_layout: obs holds a value above 2^53 on a count output" + where)
+        if frac[e, i, k]:
+            raise ValueError("count_layout: obs holds a value that is not an integer on a count output" + where)
+        raise ValueError("count_layout: censor flags a value of a count output" + where + " (censored counts are not supported)")
+    pois = seen & (np.asarray(fam) == 1)[None, None, :]
+    return {"family": np.asarray(fam, dtype=np.int64), "counts": seen.sum(axis=1).astype(np.int64),
+            "floor": np.where(pois, count_floor(v), 0.0).sum(axis=(1, 2))}
+
+
+def count_floor(y):
+    """c(y) = gammaln(y + 1) - xlogy(y, y) + y: minus the log-probability of the saturated Poisson model at the count y, the floor
+    of a Poisson term (log p = -c(y) - count_excess).  As written below y = 32, where nothing cancels yet; from there on by its
+    Stirling series 1/2 log(2 pi y) + 1/(12 y) - 1/(360 y^3) + 1/(1260 y^5) - 1/(1680 y^7), whose next term is below 1e-16 - the
+    three terms of the definition reach 1e7 at y = 1e6 and would leave c(y), a number below 10, with an error of 1e-9.  The
+    library's host code (csrc/user_model.hip: count_floor) is the same."""
+    import numpy as np
+    from scipy.special import gammaln, xlogy
+    y = np.asarray(y, dtype=np.float64)
+    small = np.where(y < 32.0, y, 1.0)
+    large = np.where(y < 32.0, 32.0, y)
+    r = 1.0 / large
+    r2 = r * r
+    series = 0.5 * np.log(6.283185307179586 * large) + r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))))
+    return np.where(y < 32.0, (gammaln(small + 1.0) - xlogy(small, small)) + small, series)
+
+
+def count_excess(y, mu, b, family):
+    """x >= 0, the excess of a count term over its floor (include/smc_hip.h: COUNT OBSERVATIONS), as the kernels form it
+    (csrc/user_count.h), operation for operation.  y the count, mu the model's mean, b the overdispersion, family 1 (Poisson: log
+    p = -count_floor(y) - x, b is not used) or 2 (negative binomial: log p = -x).  Arrays broadcast; family is one number.
+      Poisson:  x = y (d - L), d = (mu - y) / y, L = log1p(d) for d >= -1/2 and log mu - log y below (the same number, without
+                losing a mu below y 2^-53);  x = mu for y = 0.
+      negative binomial, u = b^2 mu, phi = 1 / b^2:
+                x = -[gammaln(y + phi) - gammaln(phi) - gammaln(y + 1) - phi log1p(u) + y log u - y log1p(u)];  y = 0: phi log1p(u).
+    Both: clamped at >= 0; NaN for mu NaN; +inf for mu < 0, mu = +inf, or mu = 0 with y > 0; 0 for mu = 0 with y = 0.  A negative
+    binomial b that is not > 0 gives 0 (such parameters have logL = -inf, which count_loglik decides)."""
+    import numpy as np
+    from scipy.special import gammaln
+    family = int(family)
+    if family not in (1, 2):
+        raise ValueError(f"count_excess: family {family} is neither 1 (Poisson) nor 2 (negative binomial)")
+    y, mu, b = np.broadcast_arrays(np.asarray(y, dtype=np.float64), np.asarray(mu, dtype=np.float64), np.asarray(b, dtype=np.float64))
+    inf_case = (mu < 0) | (mu == np.inf) | ((mu == 0) & (y > 0))
+    safe_mu = np.where(inf_case | np.isnan(mu) | (mu == 0), 1.0, mu)
+    safe_y = np.where(y > 0, y, 1.0)
+    with np.errstate(all="ignore"):
+        if family == 1:
+            d = (safe_mu - safe_y) / safe_y
+            low = d < -0.5
+            l = np.where(low, np.log(safe_mu) - np.log(safe_y), np.log1p(np.where(low, 0.0, d)))
+            x = safe_y * (d - l)
+            x = np.where(y == 0, mu, x)
+        else:
+            ok_b = b > 0
+            b2 = np.where(ok_b, b * b, 1.0)
+            phi = 1.0 / b2
+            u = b2 * safe_mu
+            l1 = np.log1p(u)
+            pl = phi * l1
+            g = (gammaln(safe_y + phi) - gammaln(phi)) - gammaln(safe_y + 1.0)
+            x = -(((g - pl) + safe_y * np.log(u)) - safe_y * l1)
+            x = np.where(y == 0, np.where(mu == 0, 0.0, pl), x)
+        x = np.where(x < 0, 0.0, x)
+        x = np.where(inf_case, np.inf, x)
+        if family == 2:
+            x = np.where(ok_b, x, 0.0)
+            x = np.where(np.isnan(mu) & ok_b, np.nan, x)
+        else:
+            x = np.where(np.isnan(mu), np.nan, x)
+    return x
+
+
+def count_loglik(pred, t, obs, theta, family, noise, obs_scale=None, censor=None):
+    """The likelihood of a model with count outputs (include/smc_hip.h: COUNT OBSERVATIONS) applied to given model outputs - its
+    executable definition.  Arguments as censored_loglik's (censor None: no flags) and family, one entry per output: 0 a Gaussian
+    output with its terms of noise_loglik / censored_loglik, 1 Poisson, 2 negative binomial with the output's proportional entry
+    b_k as overdispersion (variance mu + (b_k mu)^2).  With mu = pred:
+        logL = [the Gaussian outputs' logL] - sum over Poisson values [count_floor(y) + count_excess(y, mu, 0, 1)]
+               - sum over negative-binomial values count_excess(y, mu, b_k, 2);
+    -inf where any a_k <= 0, any b_k < 0, or b_k <= 0 on a negative-binomial output.  noise=None is not accepted here: give the
+    specification the library forms (count outputs ("fixed", 1.0)).  Returns (n,).  With every family 0 it is censored_loglik's
+    (noise_loglik's without flags) array exactly."""
+    import numpy as np
+    obs = np.asarray(obs, dtype=np.float64)
+    pred = np.asarray(pred, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64)
+    n_obs = obs.shape[2]
+    fam = np.asarray([int(v) for v in family], dtype=np.int64)
+    gauss = lambda o: (noise_loglik(pred, t, o, theta, noise, obs_scale) if censor is None
+                       else censored_loglik(pred, t, o, censor, theta, noise, obs_scale))
+    if not np.any(fam != 0):
+        if fam.shape != (n_obs,):
+            raise ValueError(f"count_loglik: smc_user_obs_family: {fam.size} entries for n_obs = {n_obs} outputs (one entry per output)")
+        return gauss(obs)
+    count_layout(t, obs, fam, noise, obs_scale, censor, dim=theta.shape[1])
+    lk = gauss(np.where((fam != 0)[None, None, :], np.nan, obs))       # a_k > 0 and b_k >= 0 are decided here
+    ai, af, pi, pf = noise_layout(noise, n_obs, theta.shape[1])
+    b = np.zeros((theta.shape[0], n_obs)) if pi is None else np.where(pi >= 0, theta[:, np.maximum(pi, 0)], pf[None, :])
+    seen = ~np.isnan(obs) & ~np.isnan(np.asarray(t, dtype=np.float64))[:, :, None]
+    valid = np.ones(theta.shape[0], dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for k in np.flatnonzero(fam != 0):
+            s = seen[:, :, k]
+            y = np.where(s, obs[:, :, k], 0.0)
+            mu = np.where(s[None], pred[:, :, :, k], 0.0)
+            x = count_excess(y[None], mu, b[:, k][:, None, None], int(fam[k]))
+            if fam[k] == 1:
+                x = x + count_floor(y)[None]
+            else:
+                valid &= b[:, k] > 0
+            lk = lk - np.where(s[None], x, 0.0).sum(axis=(1, 2))
+    return np.where(valid, lk, -np.inf)
+
+
 def input_layout(in_t, in_u, n_ex):
     """The data rules of a model's time-varying inputs (include/smc_hip.h: smc_set_model_user5), in NumPy: in_t (n_ex, n_knot) knot
     times, a row by the row rules of obs_layout's t - a strictly increasing finite run of at least one knot, possibly followed by
