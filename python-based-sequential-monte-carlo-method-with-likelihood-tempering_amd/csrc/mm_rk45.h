@@ -379,6 +379,26 @@ __device__ __forceinline__ int mm_item_attempt(MMItem &it, const double2 *s_tp, 
 // same fused multiply-adds the compiler forms for rk_attempt_core (first two terms of a stage sum: fma(k0, a_i1, rn(k1 *
 // a_i2)), the others fused in order; (sum) * h + y fused) - tests/test_gpu_parity.py runs stiff populations with the block
 // on and off (smc_set_fast_tail) and demands equal bits, so a compiler that changes its mind is noticed.
+// What paces the block (tools/fp64_chain_probe.hip on one wave with one live lane, profiles/lone_chain_probe.json; the wave
+// runs at 2.40 GHz): every instruction costs its ISSUE time whether or not it depends on the one before - v_fma_f64 4.4 cycles
+// in one dependent chain and in eight interleaved ones, v_add/v_mul_f64 4.3, a scalar instruction or s_nop 4.2, v_log/exp_f32
+// 8.2, v_rcp_f64 16.5 during which nothing else issues (three independent instructions behind it hide none of it).  So the
+// ORDER of the arithmetic is worth nothing and is left as the compiler has it for rk_attempt_core.  A conditional branch is
+// what is dear: in the probe's stream of independent FMAs ~20 cycles not taken, ~29 taken, ~37 directly behind the vector
+// compare that writes its condition - upper bounds from a synthetic stream: in this block a branch turned out to cost about
+// half of that (below).  The block therefore takes ONE not-taken conditional branch per accepted attempt for all of its ways out (h_abs < min_step, an
+// output due, error_norm < 2^-64; rejected and error_norm >= 2^64 are told apart behind it), with the masks gathered into one
+// scalar pair far from the branch - the kernels have no scalar registers to spare, so the off-path code computes two masks
+// again instead of keeping them -, one for the first step after a rejection (its v_min out of line) and the back edge:
+// 129 instructions and 3 branches on the accepted path where there were 133 and 7, the compares in the two slots behind
+// v_log_f32 / v_exp_f32 that held s_nop.  Measured (tools/tail_latency.py, six alternations, profiles/ab_lone_chain.log):
+// 0.3040 us per attempt against 0.3315 before, 728 against 794 cycles: the four branches and four instructions fewer saved
+// 66 cycles where the probe's branch costs give 152 (tools/lone_chain_model.py: 0.296 and 0.359 us predicted; why a branch
+// is cheaper among the block's instructions than among the probe's has not been found).  The arithmetic alone is ~640
+// cycles = 0.27 us by its issue costs; below that only fewer instructions help.  tests/test_fast_block_dataflow.py
+// value-numbers the asm text against the block it replaced (tests/golden/fast_block_parent.txt): same operations, operands
+// and order of roundings on every path, nothing committed before an exit; tests/test_gpu_fast_block_exits.py runs every way
+// out on the device with the block on and off.
 // Hazards the assembler does not see inside an asm block (gfx940 rules of LLVM's hazard recogniser): one independent
 // instruction or s_nop between a transcendental (v_rcp_f64, v_log_f32, v_exp_f32) and the first use of its result.
 // Returns 1 when the next attempt needs mm_item_attempt() (state untouched by it), 0 when `budget` ran out.
@@ -397,19 +417,20 @@ __device__ __forceinline__ int mm_fast_uniform_attempts(MMItem &it, double rtol,
     budget = __builtin_amdgcn_readfirstlane(budget);
     double tnew, h, k1, k2, k3, k4, k5, k6, acc, den, num, r, e, q;   // k1 doubles as y_new (b2 = e2 = 0), acc as the factor
     float w;
-    unsigned long long accm;
+    unsigned long long mexit;
     asm volatile(
         "s_mov_b32 %[code], 1\n"
         ".Lfast_loop_%=:\n"
-        "v_cmp_lt_f64 vcc, %[habs], %[minstep]\n"             // rk.py:133-134: left to mm_item_attempt
-        "s_cbranch_vccnz .Lfast_end_%=\n"
+        "v_cmp_lt_f64 %[mexit], %[habs], %[minstep]\n"       // rk.py:133-134: left to mm_item_attempt (tested below)
         "v_add_f64 %[tnew], %[t], %[habs]\n"
         "v_min_f64 %[tnew], %[tnew], %[tb]\n"
         "v_add_f64 %[h], %[tnew], -%[t]\n"
+        "v_cmp_le_f64 vcc, %[tstop], %[tnew]\n"              // an output is due if this step is accepted
         // stage 1
         "v_mul_f64 %[acc], %[k0], %[a21]\n"
         "v_fma_f64 %[acc], %[acc], %[h], %[y]\n"
         "v_add_f64 %[den], %[km], %[acc]\n"
+        "s_or_b64 %[mexit], %[mexit], vcc\n"                  // mexit: what sends an ACCEPTED step to mm_item_attempt
         "v_rcp_f64 %[r], %[den]\n"
         "v_mul_f64 %[num], %[nvm], %[acc]\n"
         "v_fma_f64 %[e], -%[den], %[r], 1.0\n"
@@ -504,32 +525,27 @@ __device__ __forceinline__ int mm_fast_uniform_attempts(MMItem &it, double rtol,
         "v_fma_f64 %[q], %[e], %[r], %[q]\n"                  // error_norm = |q|
         // 0.9 * error_norm ** -0.2: pow_minus_fifth_core<false> (rk45_math.h)
         "v_cvt_f32_f64 %[w], |%[q]|\n"
-        "v_cmp_lt_f64 %[accm], |%[q]|, 1.0\n"                 // accept (rk.py:149)
         "v_log_f32 %[w], %[w]\n"
-        "s_nop 0\n"
+        "v_cmp_nge_f64 vcc, |%[q]|, %[clo]\n"                 // error_norm < 2^-64, in the slot after the transcendental
         "v_mul_f32 %[w], 0xbe4ccccd, %[w]\n"
         "v_exp_f32 %[w], %[w]\n"
-        "s_nop 0\n"
+        "s_or_b64 %[mexit], %[mexit], vcc\n"                  // in the slot after the transcendental
         "v_cvt_f64_f32 %[r], %[w]\n"                          // y
+        "v_cmp_lt_f64 vcc, |%[q]|, 1.0\n"                     // accept (rk.py:149)
         "v_mul_f64 %[e], %[r], %[r]\n"
         "v_mul_f64 %[e], %[e], %[e]\n"
         "v_mul_f64 %[e], %[e], %[r]\n"                        // y^5
         "v_fma_f64 %[e], -|%[q]|, %[e], 1.0\n"                // rho
+        "s_andn2_b64 vcc, vcc, %[mexit]\n"                    // accepted and nothing else to do: the one branch of that path
         "v_mul_f64 %[acc], %[e], %[r]\n"                      // y * rho
         "v_fma_f64 %[e], %[c012], %[e], %[c02]\n"             // 0.2 + 0.12 rho
         "v_fma_f64 %[r], %[acc], %[e], %[r]\n"
         "v_mul_f64 %[acc], %[r], %[c09]\n"
-        "s_and_b64 vcc, exec, %[accm]\n"
-        "s_cbranch_vccz .Lfast_reject_%=\n"
-        // ---- accepted: no output may be due (tstop = min(t_next, t_bound)) and error_norm >= 2^-64
-        "v_cmp_le_f64 vcc, %[tstop], %[tnew]\n"
-        "s_cbranch_vccnz .Lfast_end_%=\n"
-        "v_cmp_nge_f64 vcc, |%[q]|, %[clo]\n"
-        "s_cbranch_vccnz .Lfast_end_%=\n"
+        "s_cbranch_vccz .Lfast_other_%=\n"
+        // ---- accepted, no output due (tstop = min(t_next, t_bound)), error_norm >= 2^-64, step size above its minimum
         "v_min_f64 %[acc], %[acc], %[c10]\n"                    // min(MAX_FACTOR, .)
         "s_cmp_eq_u32 %[rejected], 0\n"
-        "s_cbranch_scc1 .Lfast_first_%=\n"
-        "v_min_f64 %[acc], %[acc], 1.0\n"                       // rk.py:158-159
+        "s_cbranch_scc0 .Lfast_after_reject_%=\n"
         ".Lfast_first_%=:\n"
         "v_mul_f64 %[habs], |%[h]|, %[acc]\n"
         "v_mov_b64 %[t], %[tnew]\n"
@@ -540,25 +556,34 @@ __device__ __forceinline__ int mm_fast_uniform_attempts(MMItem &it, double rtol,
         "v_add_f64 %[e], %[e], -%[tnew]\n"
         "v_mul_f64 %[minstep], |%[e]|, %[c10]\n"
         "v_max_f64 %[habs], %[habs], %[minstep]\n"            // rk.py:122-127
-        "s_branch .Lfast_next_%=\n"
-        ".Lfast_reject_%=:\n"
-        "v_cmp_nlt_f64 vcc, |%[q]|, %[chi]\n"                 // error_norm >= 2^64, inf or NaN: left to mm_item_attempt
-        "s_cbranch_vccnz .Lfast_end_%=\n"
-        "v_max_f64 %[acc], %[acc], %[c02]\n"                    // max(MIN_FACTOR, .)
-        "v_mul_f64 %[habs], |%[h]|, %[acc]\n"
-        "s_mov_b32 %[rejected], 1\n"
         ".Lfast_next_%=:\n"
         "s_add_i32 %[attempts], %[attempts], 1\n"
         "s_sub_i32 %[budget], %[budget], 1\n"
         "s_cmp_gt_i32 %[budget], 0\n"
         "s_cbranch_scc1 .Lfast_loop_%=\n"
         "s_mov_b32 %[code], 0\n"
+        "s_branch .Lfast_end_%=\n"
+        // ---- off the accepted path
+        ".Lfast_after_reject_%=:\n"
+        "v_min_f64 %[acc], %[acc], 1.0\n"                       // rk.py:158-159
+        "s_branch .Lfast_first_%=\n"
+        ".Lfast_other_%=:\n"
+        "v_cmp_lt_f64 vcc, |%[q]|, 1.0\n"                     // the masks again, apart (no scalar pair to keep them in)
+        "v_cmp_lt_f64 %[mexit], %[habs], %[minstep]\n"
+        "s_cbranch_vccnz .Lfast_end_%=\n"                     // accepted, but an output is due or error_norm < 2^-64 or h_abs <
+        "v_cmp_nlt_f64 vcc, |%[q]|, %[chi]\n"                 // min_step.  error_norm >= 2^64, inf or NaN: left to mm_item_attempt
+        "s_or_b64 vcc, vcc, %[mexit]\n"
+        "s_cbranch_vccnz .Lfast_end_%=\n"                     // nothing has been committed
+        "v_max_f64 %[acc], %[acc], %[c02]\n"                    // rejected: max(MIN_FACTOR, .)
+        "v_mul_f64 %[habs], |%[h]|, %[acc]\n"
+        "s_mov_b32 %[rejected], 1\n"
+        "s_branch .Lfast_next_%=\n"
         ".Lfast_end_%=:\n"
         : [t] "+v"(t), [y] "+v"(y), [k0] "+v"(k0), [habs] "+v"(habs), [minstep] "+v"(minstep), [attempts] "+s"(attempts),
           [rejected] "+s"(rejected), [budget] "+s"(budget), [code] "=&s"(code), [tnew] "=&v"(tnew), [h] "=&v"(h), [k1] "=&v"(k1),
           [k2] "=&v"(k2), [k3] "=&v"(k3), [k4] "=&v"(k4), [k5] "=&v"(k5), [k6] "=&v"(k6), [acc] "=&v"(acc),
           [den] "=&v"(den), [num] "=&v"(num), [r] "=&v"(r), [e] "=&v"(e), [q] "=&v"(q), [w] "=&v"(w),
-          [accm] "=&s"(accm)
+          [mexit] "=&s"(mexit)
         : [nvm] "s"(nvm), [km] "s"(km), [tb] "s"(tb), [tstop] "s"(tstop), [rtol] "v"(rtol), [atol] "s"(atol), [c02] "v"(0.2),
           [a21] "s"(A21), [a31] "s"(A31), [a32] "s"(A32), [a41] "s"(A41), [a42] "s"(A42), [a43] "s"(A43), [a51] "s"(A51),
           [a52] "s"(A52), [a53] "s"(A53), [a54] "s"(A54), [a61] "s"(A61), [a62] "s"(A62), [a63] "s"(A63), [a64] "s"(A64),

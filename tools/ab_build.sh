@@ -7,7 +7,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 src="$root/python-based-sequential-monte-carlo-method-with-likelihood-tempering_amd/csrc"
 out="$root/build/ab/$name"
 mkdir -p "$out/csrc"
-cp "$src"/*.hip "$src"/*.h "$src"/Makefile "$out/csrc/"
+cp "$src"/*.hip "$src"/*.h "$src"/*.awk "$src"/Makefile "$out/csrc/"
 mkdir -p "$out/../../../include" 2>/dev/null || true
 # the sources include ../../include/smc_hip.h relative to csrc
 mkdir -p "$out/../include"; cp "$root/include/smc_hip.h" "$out/../include/"

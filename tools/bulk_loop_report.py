@@ -10,8 +10,9 @@ subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx9
                 "-DSMC_ENABLE_DEBUG_API=1", "-DSMC_ISA_MARKS", *sys.argv[1:], "-S", "--cuda-device-only", "-o", asm,
                 os.path.join(CSRC, "mm_kernels.hip")], check=True, stderr=subprocess.DEVNULL)
 lines = open(asm).read().split("\n")
-for inst in ("ILb0ELb0ELb1", "ILb0ELb0ELb0", "ILb0ELb1ELb0"):
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN3smc15mm_solve_kernel" + inst))
+for kern, inst in (("15mm_solve_kernel", "ILb0ELb0ELb1"), ("15mm_solve_kernel", "ILb0ELb0ELb0"), ("15mm_solve_kernel", "ILb0ELb1ELb0"),
+                   ("21mm_solve_share_kernel", "ILb0ELb0ELb1"), ("21mm_solve_share_kernel", "ILb0ELb0ELb0")):
+    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN3smc" + kern + inst))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     mk = next(i for i in range(start, end) if "MARK bulk_attempt" in lines[i])
     lab = next((i, re.match(r"^(\.LBB\d+_\d+):", lines[i]).group(1)) for i in range(mk, start, -1) if re.match(r"^\.LBB\d+_\d+:", lines[i]))
@@ -34,9 +35,9 @@ for inst in ("ILb0ELb0ELb1", "ILb0ELb0ELb0", "ILb0ELb1ELb0"):
         cur["salu"] += op.startswith("s_")
         cur["spill"] += op in ("v_readlane_b32", "v_writelane_b32")
     meta = "\n".join(lines)
-    k = meta.index(".name:           _ZN3smc15mm_solve_kernel" + inst)
-    regs = {key: int(re.search(r"\." + key + r":\s+(\d+)", meta[k:]).group(1)) for key in ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count")}
-    print(f"mm_solve_kernel<{inst}>: {regs}; bulk loop {back - lab[0]} lines")
+    k = meta.index(".name:           _ZN3smc" + kern + inst)
+    regs = {key: int(re.search(r"\." + key + r":\s+(\d+)", meta[k:]).group(1)) for key in ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")}
+    print(f"{kern[2:]}<{inst}>: {regs}; bulk loop {back - lab[0]} lines")
     for r in rows:
         for key in tot:
             tot[key] += r[key]
