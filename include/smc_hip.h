@@ -500,6 +500,36 @@ int smc_user_predict_summary(smc_ctx *ctx, int set, const double *t_new, const d
                              const double *probs, int n_probs, int noise, uint64_t seed, int64_t global_offset,
                              size_t max_staging_bytes, double *mean, double *sd, double *lower, double *upper, int64_t *n_finite,
                              int64_t *n_failed, int64_t *attempts, double *kernel_ms);
+/* POINTWISE LOG-LIKELIHOOD of a user model (any set function; RK45 or BDF), on the data's design - there are no observations
+ * elsewhere.  A cell is (experiment e, time i, output k), index c = (e * n_t + i) * n_obs + k (a one-output model: n_obs = 1); it
+ * is OBSERVED when obs is finite at a finite time of its row (a censored value is observed).  The term l of an observed cell for
+ * a particle with prediction f, a_k, b_k its output's noise parameters (the sigma rule: a_k = sigma, b_k = 0), s_k its scale:
+ *   Gaussian, quantified   -1/2 log(2 pi) - 1/2 log sd^2 - r^2 / (2 sd^2),  sd^2 = (a_k s_k)^2 + (b_k f)^2,  r = obs - f
+ *   censored               log Phi(z), z = r / sd (at or below obs) or -r / sd (at or above obs)
+ *   Poisson                log of the Poisson probability of the count obs under the mean f
+ *   negative binomial      ... of the negative-binomial one with mean f and variance f + (b_k f)^2
+ * NaN where the cell is not observed or f is NaN (a failed solve, or the model's own NaN); -inf in every other observed cell of a
+ * particle whose parameters make logL -inf (an a_k <= 0, a b_k < 0, b_k <= 0 on a negative-binomial output).  The sum of a
+ * particle's terms is its logL (smc_user_predict's lk) up to the order of the sum.  user_models.pointwise_loglik is the
+ * definition in NumPy.
+ * smc_user_pointwise: n host particles (n x dim, AoS; any n, in chunks of n_local) -> ll[p * cells + c].  Own staging; the sets and
+ * their lk are not touched; n_failed / attempts as smc_user_predict. */
+int smc_user_pointwise(smc_ctx *ctx, const double *particle, int64_t n, double *ll, int64_t *n_failed, int64_t *attempts);
+/* ... and its per-cell STATISTICS over a resident particle set, formed on the device - what lppd / WAIC and a PIT histogram are made
+ * of; replaces downloading the set, smc_user_predict of it and the family terms on the host.  set: SMC_SET_PRED or SMC_SET_FILT,
+ * its n_local particles equally weighted.  Per cell c, over the particles whose term is not NaN (-inf counts): n[c], max[c],
+ * sum_exp[c] = sum exp(l - max), mean[c] = sum l / n, m2[c] = sum (l - mean)^2 (two-pass) - raw, so that the statistics of several
+ * ranks' blocks merge (user_models.pointwise_merge): lpd = max + log(sum_exp / n), var = m2 / (n - 1).  n = 0: NaN in all but n.
+ * pit[c], for an observed quantified Gaussian cell: the mean of Phi((obs - f) / sd) over the particles with a finite f and valid
+ * noise parameters; NaN elsewhere (censored and count cells: there is no CDF on the device).  Every sum runs per thread in index
+ * order and then through a fixed tree (no atomics): a repeated call returns the same bits, and so does any max_staging_bytes.
+ * Staging as smc_user_predict_summary's (predictions plus terms, 2 x n_local x n_t x n_obs x 8 B per experiment) plus 1/32 of it
+ * for the PIT partials, within max_staging_bytes (0: most of the free device memory) by running groups of experiments; a single
+ * experiment that does not fit is refused with the bytes needed.  cells x 6 numbers and the counters come back in one
+ * synchronisation.  The particle sets, their lk, the accept flags and smc_work_totals stay as they were.  kernel_ms (may be
+ * NULL): [0] the prediction sweeps, [1] the pointwise kernels, from events.  Several ranks: THIS rank's block only. */
+int smc_user_pointwise_summary(smc_ctx *ctx, int set, size_t max_staging_bytes, int64_t *n, double *max, double *sum_exp, double *mean,
+                               double *m2, double *pit, int64_t *n_failed, int64_t *attempts, double *kernel_ms);
 /* BDF user model: device-counted work of the LAST smc_loglik / smc_mh_step_* sweep, in the manner of
  * smc_meth_sweep_counters: out = {accepted BDF steps, Newton iterations, LU factorisations, Jacobian evaluations} summed over
  * the sweep's solves (masked proposals left out).  Fails with a message for an RK45 model. */

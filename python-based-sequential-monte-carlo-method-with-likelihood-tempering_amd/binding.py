@@ -129,6 +129,8 @@ SIGNATURES = {
     "smc_user_predict_at": (cint, [c_ctx, c_dp, i64, c_dp, c_dp, cint, cint, c_dp, c_i64p, c_i64p]),
     "smc_user_predict_summary": (cint, [c_ctx, cint, c_dp, c_dp, cint, cint, c_dp, cint, cint, u64, i64, ctypes.c_size_t, c_dp, c_dp,
                                          c_dp, c_dp, c_i64p, c_i64p, c_i64p, c_dp]),
+    "smc_user_pointwise": (cint, [c_ctx, c_dp, i64, c_dp, c_i64p, c_i64p]),
+    "smc_user_pointwise_summary": (cint, [c_ctx, cint, ctypes.c_size_t, c_i64p, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p, c_i64p, c_dp]),
     "smc_user_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_check": (cint, [c_ctx, c_i64p]),

@@ -30,6 +30,7 @@
 #include "user_count.h"    // count observations (smc_user_obs_family)
 #include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
 #include "predictive_kernels.h"   // smc_user_predict_summary's kernels
+#include "pointwise_kernels.h"    // smc_user_pointwise, smc_user_pointwise_summary
 
 namespace smc {
 
@@ -241,6 +242,12 @@ struct UserModel {
     int blocks_per_cu_pred = 4;
     double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;   // smc_user_predict's staging: parameters (AoS + SoA), lk, pred
     int64_t p_cap = 0;
+    // smc_user_pointwise / smc_user_pointwise_summary (pointwise_kernels.h): per cell of the data's design its value, what it is and
+    // count_floor of a Poisson value, built once with the image; the families; the staging of the host-particle entry point
+    double *d_cell_obs = nullptr, *d_cell_floor = nullptr, *d_pll = nullptr;
+    int *d_cell_code = nullptr;
+    int family[kUserMaxObs] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t pll_cap = 0;
     // what a design other than the data's needs again on the host (smc_user_predict_at, smc_user_predict_summary)
     std::vector<double> h_t, h_cond;
     double scale[kUserMaxObs] = {1, 1, 1, 1, 1, 1, 1, 1};
@@ -526,6 +533,10 @@ void user_model_release(smc_ctx *c) {
     (void)hipFree(u->d_pt);
     (void)hipFree(u->d_plk);
     (void)hipFree(u->d_ppred);
+    (void)hipFree(u->d_cell_obs);
+    (void)hipFree(u->d_cell_floor);
+    (void)hipFree(u->d_cell_code);
+    (void)hipFree(u->d_pll);
     if (u->module_pred) (void)hipModuleUnload(u->module_pred);
     if (u->module) (void)hipModuleUnload(u->module);
     delete u;
@@ -747,6 +758,27 @@ static std::vector<double> count_floor_sums(const double *t, const double *obs, 
                 if (family[k] == 1 && !std::isnan(v)) ce[e] += count_floor(v);
             }
     return ce;
+}
+
+// The per-cell tables of the pointwise kernels (pointwise_kernels.h) for data obs_layout has accepted: a cell (e, i, k) is observed
+// when obs is finite at a finite time of its row; a censored value is observed.
+static void build_cell_tables(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const signed char *censor, const int *family,
+                              std::vector<double> &value, std::vector<int> &code, std::vector<double> &floor_y) {
+    const size_t cells = (size_t)n_ex * n_t * n_obs;
+    value.assign(cells, std::nan(""));
+    code.assign(cells, 0);
+    floor_y.assign(cells, 0.0);
+    for (int e = 0; e < n_ex; ++e)
+        for (int i = 0; i < n_t && !std::isnan(t[(size_t)e * n_t + i]); ++i)
+            for (int k = 0; k < n_obs; ++k) {
+                const size_t at = ((size_t)e * n_t + i) * n_obs + k;
+                if (std::isnan(obs[at])) continue;
+                const int fam = family ? family[k] : 0;
+                const signed char f = censor ? censor[at] : 0;
+                value[at] = obs[at];
+                code[at] = kCellObserved | ((f < 0 ? kCensorLeft : f > 0 ? kCensorRight : kCensorNone) << kCellFlagShift) | (fam << kCellFamilyShift);
+                if (fam == 1) floor_y[at] = count_floor(obs[at]);
+            }
 }
 
 // flagged: the image of a model compiled with SMC_USER_CENSOR - records of obs_rec_words_censor(n_obs) words, the last one the
@@ -1526,6 +1558,15 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
             u->img_len = (int)img.size();
             ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
                  hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+            std::vector<double> cv, cf;      // the pointwise kernels' tables
+            std::vector<int> cc;
+            build_cell_tables(t, obs, n_ex, n_t, n_obs, censor, family, cv, cc, cf);
+            ok = ok && hipMalloc(&u->d_cell_obs, cv.size() * sizeof(double)) == hipSuccess &&
+                 hipMalloc(&u->d_cell_floor, cf.size() * sizeof(double)) == hipSuccess &&
+                 hipMalloc(&u->d_cell_code, cc.size() * sizeof(int)) == hipSuccess &&
+                 hipMemcpy(u->d_cell_obs, cv.data(), cv.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(u->d_cell_floor, cf.data(), cf.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(u->d_cell_code, cc.data(), cc.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
         } else {
             u->img_error = "smc_user_predict: the data of this model (set through smc_set_model_user / smc_set_model_user2) cannot be "
                            "predicted: " + bad + "; set it through smc_set_model_user3";
@@ -1555,6 +1596,7 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     if (family) {
         u->count = true;
         for (int k = 0; k < n_obs; ++k) u->negbin |= family[k] == 2 ? 1u << k : 0u;
+        for (int k = 0; k < n_obs; ++k) u->family[k] = family[k];
     }
     {   // occupancy of the compiled kernel with its pool in LDS
         int nb = 0;
@@ -1720,11 +1762,36 @@ int smc_user_set_design_inputs(smc_ctx *c, const double *in_t_new, const double 
     return 0;
 }
 
-int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts) {
+// the noise of every output as the pointwise kernels take it: the model's noise model, or the sigma rule written as one
+static PointwiseArgs pointwise_args_of(const smc_ctx *c, const UserModel *u) {
+    PointwiseArgs a{};
+    if (u->noise) {
+        a.nz = u->nz;
+    } else {
+        for (int k = 0; k < kUserMaxObs; ++k) {
+            a.nz.add_index[k] = u->est_sigma ? c->dim - 1 : -1;
+            a.nz.add_fixed[k] = u->sigma_fixed;
+            a.nz.prop_index[k] = -1;
+            a.nz.prop_fixed[k] = 0.0;
+            a.nz.scale[k] = u->scale[k];
+        }
+        a.nz.prop = 0;
+    }
+    for (int k = 0; k < kUserMaxObs; ++k) a.family[k] = u->family[k];
+    a.n_obs = u->n_obs;
+    a.cell_obs = u->d_cell_obs;
+    a.cell_code = u->d_cell_code;
+    a.cell_floor = u->d_cell_floor;
+    return a;
+}
+
+// smc_user_predict, and with ll != nullptr smc_user_pointwise: the terms of every chunk's predictions, particle-major like pred
+static int user_predict_impl(smc_ctx *c, const char *who, const double *particle, int64_t n, double *lk, double *pred, double *ll,
+                             int64_t *n_failed, int64_t *attempts) {
     if (!c) return smc_fail(nullptr, "NULL context");
     UserModel *u = (UserModel *)c->user;
-    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_predict: no user model has been set");
-    if (n < 0 || (n > 0 && (!particle || !lk))) return smc_fail(c, "smc_user_predict: bad arguments");
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, (std::string(who) + ": no user model has been set").c_str());
+    if (n < 0 || (n > 0 && (!particle || !lk))) return smc_fail(c, (std::string(who) + ": bad arguments").c_str());
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     if (n_failed) *n_failed = 0;
     if (attempts) *attempts = 0;
@@ -1762,6 +1829,13 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
             return smc_fail(c, "smc_user_predict: device allocation failed");
         u->p_cap = chunk;
     }
+    if (ll && chunk > u->pll_cap) {
+        (void)hipFree(u->d_pll);
+        u->d_pll = nullptr;
+        u->pll_cap = 0;
+        if (hipMalloc(&u->d_pll, (size_t)chunk * per * sizeof(double)) != hipSuccess) return smc_fail(c, (std::string(who) + ": device allocation failed").c_str());
+        u->pll_cap = chunk;
+    }
     double *aos = u->d_pt, *soa = u->d_pt + (size_t)u->p_cap * dim;
     if (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
         (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess))
@@ -1776,6 +1850,19 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
             c->launch_failed = false;
             return 1;
         }
+        if (ll) {
+            PointwiseArgs a = pointwise_args_of(c, u);
+            a.pred = u->d_ppred;
+            a.ll = u->d_pll;
+            a.n = m;
+            a.cells = (int)per;
+            a.cells_total = (int64_t)per;
+            a.theta = soa;
+            a.stride = m;
+            launch_pointwise(c, a);
+            if (hipMemcpyAsync(ll + (size_t)off * per, u->d_pll, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+                return smc_fail(c, (std::string(who) + ": download failed").c_str());
+        }
         if (hipMemcpyAsync(lk + off, u->d_plk, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             (pred && hipMemcpyAsync(pred + (size_t)off * per, u->d_ppred, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost,
                                     c->stream) != hipSuccess))
@@ -1787,6 +1874,15 @@ int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, 
     if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
     if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
     return 0;
+}
+int smc_user_predict(smc_ctx *c, const double *particle, int64_t n, double *lk, double *pred, int64_t *n_failed, int64_t *attempts) {
+    return user_predict_impl(c, "smc_user_predict", particle, n, lk, pred, nullptr, n_failed, attempts);
+}
+int smc_user_pointwise(smc_ctx *c, const double *particle, int64_t n, double *ll, int64_t *n_failed, int64_t *attempts) {
+    if (!c) return smc_fail(nullptr, "NULL context");
+    if (n > 0 && !ll) return smc_fail(c, "smc_user_pointwise: NULL result array");
+    std::vector<double> lk((size_t)(n > 0 ? n : 0) + 1);
+    return user_predict_impl(c, "smc_user_pointwise", particle, n, lk.data(), nullptr, ll, n_failed, attempts);
 }
 // the design of a call: (t_new, cond_new) checked by the rules of smc_set_model_user3, or the data's own
 // A model with inputs: cond becomes whole rows (cond_stride words, the table behind the numbers) - the data's own, or in `rows`
@@ -2061,6 +2157,131 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     (void)hipFree(d_plk);
     (void)hipFree(d_ppred);
     (void)hipFree(d_keys);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, int64_t *n_terms, double *max, double *sum_exp, double *mean,
+                               double *m2, double *pit, int64_t *n_failed, int64_t *attempts, double *kernel_ms) {
+    const char *who = "smc_user_pointwise_summary";
+    if (!c) return smc_fail(nullptr, "NULL context");
+    UserModel *u = (UserModel *)c->user;
+    if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_pointwise_summary: no user model has been set");
+    if (set != SMC_SET_PRED && set != SMC_SET_FILT) return smc_fail(c, "smc_user_pointwise_summary: set must be SMC_SET_PRED or SMC_SET_FILT");
+    if (!n_terms || !max || !sum_exp || !mean || !m2 || !pit) return smc_fail(c, "smc_user_pointwise_summary: NULL result array");
+    if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
+    if (n_failed) *n_failed = 0;
+    if (attempts) *attempts = 0;
+    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
+    const double *t = nullptr, *cond = nullptr;      // the data's design: there are no observations elsewhere
+    int n_ex = 0, n_t = 0;
+    std::vector<double> design_rows;
+    if (resolve_design(c, u, who, t, cond, n_ex, n_t, design_rows) != 0) return 1;
+    const int64_t n = c->n_local;
+    const int g_lds = design_lds_group(u, n_ex, n_t);
+    if (g_lds < 1) return design_too_large(c, u, who, n_t);
+    // staging: per experiment the predictions and their terms (n x n_t x n_obs words each), the PIT partials (2 words per 32
+    // particles and cell: 1/32 of the two) and the per-item words of a launch; once, the likelihoods the finish kernel writes and
+    // the results
+    const size_t row = (size_t)n_t * u->n_obs;
+    const int64_t cells_total = (int64_t)n_ex * (int64_t)row;
+    const size_t out_words = (size_t)cells_total * kPwOutWords;
+    const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pointwise_terms_bytes(n, (int)row) + pointwise_pit_bytes(n, (int)row);
+    const size_t fixed = (size_t)n * sizeof(double) + out_words * sizeof(double);
+    size_t budget = max_staging_bytes;
+    if (budget == 0) {      // default: most of what is free
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return smc_fail(c, "smc_user_pointwise_summary: hipMemGetInfo failed");
+        budget = free_b / 10 * 8;
+    }
+    if (budget < fixed + per_ex)
+        return smc_fail(c, (std::string(who) + ": one experiment of the design needs " + std::to_string(fixed + per_ex) +
+                            " B of staging (predictions and terms of " + std::to_string(n) + " particles), max_staging_bytes allows " +
+                            std::to_string(budget) + " B").c_str());
+    int g_max = (int)std::min<size_t>((budget - fixed) / per_ex, (size_t)g_lds);
+    if (g_max > n_ex) g_max = n_ex;
+    if (ensure_pred_kernel(c, u, who) != 0 || raise_pred_lds(c, u, who) != 0) return 1;
+
+    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
+    std::vector<hipEvent_t> ev(3 * groups.size(), nullptr);
+    DesignItems items;
+    double *d_plk = nullptr, *d_ppred = nullptr, *d_out = nullptr, *d_terms = nullptr, *d_pit = nullptr;
+    std::vector<double> h_out(out_words);
+    int rc = 0;
+    bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_ppred, (size_t)n * g_max * row * sizeof(double)) == hipSuccess &&
+              hipMalloc(&d_terms, pointwise_terms_bytes(n, (int)(g_max * row))) == hipSuccess &&
+              hipMalloc(&d_pit, pointwise_pit_bytes(n, (int)(g_max * row))) == hipSuccess &&
+              hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess;
+    for (size_t k = 0; ok && k < groups.size(); ++k) {
+        const int e0 = (int)k * g_max;
+        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
+    }
+    for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
+    if (!ok) rc = smc_fail(c, "smc_user_pointwise_summary: device allocation / upload failed");
+    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
+                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
+        rc = smc_fail(c, "smc_user_pointwise_summary: clearing the counters failed");
+    const ParticleSet &P = c->set[set];
+    for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
+        const DesignGroup &dg = groups[k];
+        (void)hipEventRecord(ev[3 * k], c->stream);
+        {
+            DesignScope scope(u, dg, items);
+            launch_user_kernel(c, P.theta, P.stride, n, nullptr, d_plk, false, d_ppred);
+        }
+        if (c->launch_failed) {
+            c->launch_failed = false;
+            rc = 1;
+            break;
+        }
+        (void)hipEventRecord(ev[3 * k + 1], c->stream);
+        PointwiseArgs a = pointwise_args_of(c, u);
+        a.pred = d_ppred;
+        a.terms = d_terms;
+        a.pit_part = d_pit;
+        a.n = n;
+        a.cells = (int)(dg.n_ex * row);
+        a.cell_base = (int64_t)dg.e0 * (int64_t)row;
+        a.cells_total = cells_total;
+        a.theta = P.theta;
+        a.stride = P.stride;
+        a.out = d_out;
+        launch_pointwise(c, a);
+        (void)hipEventRecord(ev[3 * k + 2], c->stream);
+    }
+    // the one synchronisation: results and counters
+    if (rc == 0 && (hipMemcpyAsync(h_out.data(), d_out, out_words * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipStreamSynchronize(c->stream) != hipSuccess))
+        rc = smc_fail(c, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+    if (rc != 0) (void)hipStreamSynchronize(c->stream);
+    if (rc == 0) {
+        const size_t ct = (size_t)cells_total;
+        for (size_t i = 0; i < ct; ++i) {
+            n_terms[i] = (int64_t)h_out[i];
+            max[i] = h_out[ct + i];
+            sum_exp[i] = h_out[2 * ct + i];
+            mean[i] = h_out[3 * ct + i];
+            m2[i] = h_out[4 * ct + i];
+            pit[i] = h_out[5 * ct + i];
+        }
+        if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
+        if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
+        for (size_t k = 0; kernel_ms && k < groups.size(); ++k) {
+            float a_ms = 0.f, b_ms = 0.f;
+            if (hipEventElapsedTime(&a_ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) kernel_ms[0] += a_ms;
+            if (hipEventElapsedTime(&b_ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) kernel_ms[1] += b_ms;
+        }
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (DesignGroup &dg : groups) dg.release();
+    items.release();
+    (void)hipFree(d_plk);
+    (void)hipFree(d_ppred);
+    (void)hipFree(d_terms);
+    (void)hipFree(d_pit);
     (void)hipFree(d_out);
     return rc;
 }

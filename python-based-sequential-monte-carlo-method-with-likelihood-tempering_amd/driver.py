@@ -334,9 +334,30 @@ def _rng_state_from_json(j):
     return (j[0], np.array(j[1], dtype=np.uint32), j[2], j[3], j[4])
 
 
+def _pointwise_all_ranks(engine, comm, kwargs):
+    """HipEngine.pointwise_summary of this rank's block; with several ranks the blocks' raw statistics allgathered and merged in
+    rank order, so that every rank holds the statistics of the whole population."""
+    from .user_models import pointwise_merge, waic
+    mine = engine.pointwise_summary(**kwargs)
+    if comm.size == 1:
+        return mine
+    keys = ("n", "max", "sum_exp", "mean", "m2", "pit")
+    shape = mine["n"].shape
+    flat = np.concatenate([np.asarray(mine[k], dtype=np.float64).reshape(-1) for k in keys]
+                          + [np.array([mine["n_failed"], mine["rk_attempts"]], dtype=np.float64)])
+    parts = np.asarray(comm.allgather(flat)).reshape(comm.size, -1)      # n, failures and attempts are integers below 2^53: exact
+    cells = mine["n"].size
+    blocks = [{k: (p[j * cells:(j + 1) * cells].reshape(shape).astype(np.int64) if k == "n" else p[j * cells:(j + 1) * cells].reshape(shape))
+               for j, k in enumerate(keys)} for p in parts]
+    out = pointwise_merge(blocks)
+    out.update({"n_failed": int(parts[:, -2].sum()), "rk_attempts": int(parts[:, -1].sum()), "kernel_ms": mine["kernel_ms"]})
+    out["waic"] = waic(out)
+    return out
+
+
 def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy", verbose: bool = True,
             p_pred0=None, seed_device: int | None = None, log=print, dump_dir: str | None = None,
-            resume_from: tuple | None = None, predictive: dict | None = None):
+            resume_from: tuple | None = None, predictive: dict | None = None, pointwise: bool | dict | None = None):
     """Run the tempering loop (main:95-262).  The engine must already hold the model and the prior.
 
     dump_dir: per-step dumps in the reference's formats plus a small state file per step.
@@ -351,8 +372,16 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     global_offset defaults to the block's start rank * n_local, as in every other device-RNG call of the run, so the ranks' bands
     are independent draws and do not depend on how the particles are sharded; a "global_offset" in the dict wins.
 
+    pointwise: True, or keyword arguments of HipEngine.pointwise_summary (user models only; `which` defaults to the final
+    posterior, SMC_SET_PRED): per observation the statistics of its log-likelihood term over the posterior - lppd, WAIC and the
+    PIT - formed on the device before returning and stored as out["pointwise"].  With several ranks each rank's block statistics
+    are allgathered (comm.allgather) and merged in rank order (user_models.pointwise_merge), so every rank returns the whole
+    population's statistics; "n_failed" and "rk_attempts" are then summed over the ranks and "kernel_ms" stays this rank's.
+
     Returns a dict: final particles (this rank's block), lk, schedule records, logZ, counters.
     """
+    if pointwise is not None and pointwise is not False and (getattr(engine, "model", None) is None or engine.model[0] != "user"):
+        raise ValueError("run_smc: pointwise= applies to a user model (HipEngine.set_model_user) only")
     if predictive is not None and (getattr(engine, "model", None) is None or engine.model[0] != "user"):
         raise ValueError("run_smc: predictive= applies to a user model (HipEngine.set_model_user) only")
     s = s or SMCSettings()
@@ -593,4 +622,6 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
            "wall_s": time.perf_counter() - start_time}
     if predictive is not None:                    # this rank's block, its noise drawn under the block's global particle numbers
         out["predictive"] = engine.predictive_summary(**{"which": SMC_SET_PRED, "global_offset": lo, **predictive})
+    if pointwise is not None and pointwise is not False:
+        out["pointwise"] = _pointwise_all_ranks(engine, comm, {"which": SMC_SET_PRED, **(pointwise if isinstance(pointwise, dict) else {})})
     return out

@@ -662,6 +662,46 @@ class HipEngine:
         return {"mean": mean, "sd": sd, "n_finite": nfin, "lower": lower, "upper": upper, "quantile": quantile,
                 "n_failed": nf.value, "rk_attempts": att.value, "kernel_ms": {"predict": float(ms[0]), "summary": float(ms[1])}}
 
+    def pointwise_loglik(self, particles):
+        """The log-likelihood term of every observation for host particles (n, dim) (include/smc_hip.h: smc_user_pointwise;
+        user_models.pointwise_loglik is its definition): returns ll (n, n_ex, n_t, n_obs) - NaN where a cell is not observed or
+        the prediction is NaN, -inf for parameters that make logL -inf - and {"n_failed", "rk_attempts"} as predict_user's.  The
+        (draws x observations) matrix ArviZ / loo take.  Leaves the particle sets and their lk untouched."""
+        if self.model is None or self.model[0] != "user":
+            raise SmcError("pointwise_loglik: no user model has been set")
+        particles = _f64(particles)
+        if particles.ndim != 2 or particles.shape[1] != self.dim:
+            raise ValueError(f"pointwise_loglik: particles must be (n, {self.dim}), got {particles.shape}")
+        n = particles.shape[0]
+        ll = np.empty((n, self.model[1], self.model[2], self.user_n_obs))
+        nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._ck(self.L.smc_user_pointwise(self.ctx, _dp(particles), n, _dp(ll), ctypes.byref(nf), ctypes.byref(att)),
+                 "smc_user_pointwise")
+        return ll, {"n_failed": nf.value, "rk_attempts": att.value}
+
+    def pointwise_summary(self, which=SMC_SET_FILT, max_staging_bytes=0):
+        """Per observation the statistics of its log-likelihood term over a resident particle set, formed on the device
+        (include/smc_hip.h: smc_user_pointwise_summary).  Returns the dict of user_models.pointwise_stats - "n", "max", "sum_exp",
+        "mean", "m2", "lpd", "var", each (n_ex, n_t, n_obs) - plus "pit" (quantified Gaussian cells; NaN on censored and count
+        cells, for which the device has no CDF), "n_failed", "rk_attempts", "kernel_ms": {"predict", "pointwise"} and "waic"
+        (user_models.waic of it).  Only the statistics cross the bus; the sets, their lk and the accept flags are untouched.
+        With several ranks each rank describes its own block; user_models.pointwise_merge joins them (run_smc(pointwise=) does)."""
+        if self.model is None or self.model[0] != "user":
+            raise SmcError("pointwise_summary: no user model has been set")
+        cells = (self.model[1], self.model[2], self.user_n_obs)
+        n = np.empty(cells, dtype=np.int64)
+        mx, se, mean, m2, pit = (np.empty(cells) for _ in range(5))
+        nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
+        ms = np.zeros(2)
+        self._ck(self.L.smc_user_pointwise_summary(self.ctx, int(which), int(max_staging_bytes), n.ctypes.data_as(B.c_i64p), _dp(mx),
+                                                   _dp(se), _dp(mean), _dp(m2), _dp(pit), ctypes.byref(nf), ctypes.byref(att),
+                                                   _dp(ms)), "smc_user_pointwise_summary")
+        from .user_models import pointwise_finish, waic
+        out = pointwise_finish({"n": n, "max": mx, "sum_exp": se, "mean": mean, "m2": m2, "pit": pit})
+        out.update({"n_failed": nf.value, "rk_attempts": att.value, "kernel_ms": {"predict": float(ms[0]), "pointwise": float(ms[1])}})
+        out["waic"] = waic(out)
+        return out
+
     # ---- weights / ESS -------------------------------------------------------------------------
     def max_lk_local(self):
         v = ctypes.c_double(0)

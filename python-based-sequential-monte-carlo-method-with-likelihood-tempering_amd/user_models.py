@@ -842,3 +842,182 @@ def linear_quantile(lower, upper, frac):
         q = np.where(frac >= 0.5, upper - d * (1.0 - frac), lower + d * frac)
         q = np.where(upper == lower, lower, q)
         return np.minimum(np.maximum(q, lower), upper)       # rounding cannot leave the bracket
+
+
+# ---- pointwise log-likelihood, WAIC and PIT (include/smc_hip.h: smc_user_pointwise, smc_user_pointwise_summary) --------------------
+def _pointwise_parts(pred, t, obs, theta, noise, obs_scale, censor, family):
+    """What pointwise_loglik and pointwise_pit share: (pred, obs, seen, a, b, scale, flag, fam, valid) with a, b (n, n_obs) the
+    particles' noise parameters and valid (n,) whether they allow a likelihood at all."""
+    import numpy as np
+    pred = np.asarray(pred, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    if obs.ndim == 2:                                   # the one-output model: one cell per time
+        obs = obs[:, :, None]
+    if pred.ndim == 3:
+        pred = pred[:, :, :, None]
+    n_obs = obs.shape[2]
+    if pred.shape[1:] != obs.shape or pred.shape[0] != theta.shape[0]:
+        raise ValueError(f"pointwise_loglik: pred must be (n, n_ex, n_t, n_obs) = {(theta.shape[0],) + obs.shape}, got {pred.shape}")
+    ai, af, pi, pf = noise_layout(noise, n_obs, theta.shape[1])
+    scale = np.ones(n_obs) if obs_scale is None else np.asarray(obs_scale, dtype=np.float64).reshape(n_obs)
+    fam = np.zeros(n_obs, dtype=np.int64) if family is None else np.asarray([int(v) for v in family], dtype=np.int64)
+    flag = np.zeros(obs.shape, dtype=np.int8) if censor is None else np.asarray(censor)
+    if censor is not None:
+        censor_layout(t, obs, flag)
+    if np.any(fam != 0):
+        count_layout(t, obs, fam, noise, obs_scale, censor, dim=theta.shape[1])
+    a = np.where(ai >= 0, theta[:, np.maximum(ai, 0)], af[None, :])
+    b = np.zeros_like(a) if pi is None else np.where(pi >= 0, theta[:, np.maximum(pi, 0)], pf[None, :])
+    seen = ~np.isnan(obs) & ~np.isnan(np.asarray(t, dtype=np.float64))[:, :, None]
+    with np.errstate(invalid="ignore"):
+        valid = np.all(a > 0, axis=1) & np.all(b >= 0, axis=1) & np.all((b > 0) | (fam != 2)[None, :], axis=1)
+    return pred, obs, seen, a, b, scale, flag, fam, valid
+
+
+def pointwise_loglik(pred, t, obs, theta, noise, obs_scale=None, censor=None, family=None):
+    """The log-likelihood term of every cell (experiment e, time i, output k) for every particle - the executable definition of
+    smc_user_pointwise (include/smc_hip.h), written with the functions that define the sums (noise_layout, censor_excess,
+    count_floor, count_excess), operation for operation as the kernels form it (csrc/pointwise_kernels.hip: pw_term).  Arguments as
+    count_loglik's: pred (n, n_ex, n_t, n_obs) model outputs f, t (n_ex, n_t), obs (n_ex, n_t, n_obs), theta (n, dim), noise the
+    specification (the sigma rule is {"additive": [("param", dim - 1)] * n_obs}, or ("fixed", sigma)), censor and family optional.
+    A 2-D obs with a 3-D pred is the one-output model.  A cell is observed when obs is finite at a finite time of its row; censored
+    values are observed.  With sd^2 = (a_k s_k)^2 + (b_k f)^2 and r = obs - f the term l is
+        Gaussian, quantified   -1/2 log(2 pi) - 1/2 log sd^2 - r^2 / (2 sd^2)
+        censored (flag -1, +1) -censor_excess(z),  z = r / sd and -r / sd
+        Poisson                -(count_floor(y) + count_excess(y, f, 0, 1))
+        negative binomial      -count_excess(y, f, b_k, 2)
+    NaN where the cell is not observed or f is NaN (a failed solve, or the model's own NaN); -inf in every other observed cell of a
+    particle whose parameters make logL -inf (any a_k <= 0, any b_k < 0, b_k <= 0 on a negative-binomial output).  Returns
+    (n, n_ex, n_t, n_obs); its nansum over the cells is noise_loglik / censored_loglik / count_loglik up to the order of the sum."""
+    import numpy as np
+    pred, obs, seen, a, b, scale, flag, fam, valid = _pointwise_parts(pred, t, obs, theta, noise, obs_scale, censor, family)
+    f = np.where(seen[None], pred, 0.0)
+    y = np.where(seen, obs, 0.0)
+    with np.errstate(all="ignore"):
+        sd2 = (a * scale)[:, None, None, :] ** 2 + (b[:, None, None, :] * f) ** 2
+        r = y[None] - f
+        ll = -0.5 * np.log(2 * np.pi) - 0.5 * np.log(sd2) - r * r / (2 * sd2)
+        cens = (flag != 0)[None]
+        z = np.where((flag < 0)[None], r, -r) / np.sqrt(sd2)
+        ll = np.where(cens, -censor_excess(np.where(cens, z, 0.0)), ll)
+        for k in np.flatnonzero(fam != 0):
+            yk, fk = y[None, :, :, k], f[:, :, :, k]
+            if fam[k] == 1:
+                ll[..., k] = -(count_floor(yk) + count_excess(yk, fk, 0.0, 1))
+            else:
+                ll[..., k] = -count_excess(yk, fk, np.where(valid, b[:, k], 1.0)[:, None, None], 2)
+    ll = np.where(valid[:, None, None, None], ll, -np.inf)
+    return np.where(seen[None] & ~np.isnan(pred), ll, np.nan)
+
+
+def pointwise_pit(pred, t, obs, theta, noise, obs_scale=None, censor=None, family=None):
+    """The probability integral transform of every quantified Gaussian value under the equally weighted particles - the definition
+    of smc_user_pointwise_summary's pit: per observed cell with flag 0 on a Gaussian output
+        pit = sum Phi((obs - f) / sd) / n_pit,   Phi(z) = erfc(-z / sqrt 2) / 2,
+    over the n_pit particles with a finite f and valid noise parameters (n_pit = 0: NaN); NaN on every other cell - the PIT of a
+    censored or count value is not formed (there is no CDF on the device).  Arguments as pointwise_loglik's; returns
+    (n_ex, n_t, n_obs).  A calibrated model has PIT values uniform on (0, 1) over the cells."""
+    import numpy as np
+    from scipy.special import erfc
+    pred, obs, seen, a, b, scale, flag, fam, valid = _pointwise_parts(pred, t, obs, theta, noise, obs_scale, censor, family)
+    cell = seen & (flag == 0) & (fam == 0)[None, None, :]
+    use = cell[None] & np.isfinite(pred) & valid[:, None, None, None]
+    f = np.where(use, pred, 0.0)
+    with np.errstate(all="ignore"):
+        sd2 = (a * scale)[:, None, None, :] ** 2 + (b[:, None, None, :] * f) ** 2
+        z = (np.where(seen, obs, 0.0)[None] - f) / np.sqrt(sd2)
+        phi = np.where(use, 0.5 * erfc(-z / np.sqrt(2.0)), 0.0)
+        pit = phi.sum(axis=0) / use.sum(axis=0)
+    return np.where(cell, pit, np.nan)
+
+
+def pointwise_finish(stats):
+    """lpd = max + log(sum_exp / n) and var = m2 / (n - 1) added to raw statistics {"n", "max", "sum_exp", "mean", "m2"[, "pit"]}:
+    n = 0 gives NaN in both, n = 1 var NaN, max = -inf lpd -inf; everything else is what the expressions give."""
+    import numpy as np
+    out = dict(stats)
+    n = np.asarray(out["n"], dtype=np.int64)
+    nf = n.astype(np.float64)
+    with np.errstate(all="ignore"):
+        lpd = out["max"] + np.log(out["sum_exp"] / nf)
+        lpd = np.where(np.isneginf(out["max"]), -np.inf, lpd)
+        out["lpd"] = np.where(n == 0, np.nan, lpd)
+        out["var"] = np.where(n >= 2, out["m2"] / (nf - 1.0), np.nan)
+    return out
+
+
+def pointwise_stats(ll):
+    """Per cell the statistics of the terms ll (n, ...) over the particles whose term is not NaN (-inf counts) - what
+    smc_user_pointwise_summary forms on the device: {"n", "max", "sum_exp" = sum exp(l - max), "mean" = sum l / n, "m2" = sum
+    (l - mean)^2 (two-pass), "lpd" = max + log(sum_exp / n), "var" = m2 / (n - 1)}, each of ll's shape without the first axis.
+    n = 0: NaN everywhere except n; n = 1: var NaN; max = -inf: lpd -inf; everything else is whatever these expressions give
+    under errstate(all="ignore") (a -inf term next to finite ones: mean -inf, m2 NaN)."""
+    import numpy as np
+    ll = np.asarray(ll, dtype=np.float64)
+    ok = ~np.isnan(ll)
+    n = ok.sum(axis=0).astype(np.int64)
+    nf = n.astype(np.float64)
+    with np.errstate(all="ignore"):
+        mx = np.where(n > 0, np.max(np.where(ok, ll, -np.inf), axis=0), np.nan)
+        sum_exp = np.where(n > 0, np.sum(np.where(ok, np.exp(ll - mx[None]), 0.0), axis=0), np.nan)
+        mean = np.where(n > 0, np.sum(np.where(ok, ll, 0.0), axis=0) / nf, np.nan)
+        d = np.where(ok, ll - mean[None], 0.0)
+        m2 = np.where(n > 0, np.sum(d * d, axis=0), np.nan)
+    return pointwise_finish({"n": n, "max": mx, "sum_exp": sum_exp, "mean": mean, "m2": m2})
+
+
+def pointwise_merge(blocks):
+    """The statistics of disjoint blocks of particles (dicts of pointwise_stats / HipEngine.pointwise_summary) merged in list order
+    into those of all of them - what a run over several ranks returns (csrc/pointwise_reduce.h: merge is the same in C++): n adds
+    and max is the larger; sum_exp is rescaled to the common max (a block whose max is -inf under a finite one adds 0); mean and
+    m2 by Chan's update, delta = mean_b - mean_a: mean = mean_a + delta n_b / n, m2 = m2_a + m2_b + delta^2 n_a n_b / n (a -inf
+    mean on either side: mean -inf, m2 NaN, as the expressions of the whole give); "pit", where the blocks carry it, weighted by
+    n.  A block with n = 0 in a cell changes nothing there.  lpd and var are formed anew (pointwise_finish)."""
+    import numpy as np
+    blocks = list(blocks)
+    if not blocks:
+        raise ValueError("pointwise_merge: no block")
+    with_pit = all("pit" in b for b in blocks)
+    acc = {k: np.array(blocks[0][k], dtype=np.int64 if k == "n" else np.float64) for k in ("n", "max", "sum_exp", "mean", "m2")}
+    if with_pit:
+        acc["pit"] = np.array(blocks[0]["pit"], dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for blk in blocks[1:]:
+            na, nb = acc["n"].astype(np.float64), np.asarray(blk["n"], dtype=np.float64)
+            n = na + nb
+            ma, mb = acc["max"], np.asarray(blk["max"], dtype=np.float64)
+            mx = np.where(mb > ma, mb, ma)
+
+            def rescaled(s, m):
+                return np.where(m == mx, s, np.where(np.isneginf(m), 0.0, s * np.exp(m - mx)))
+            sum_exp = rescaled(acc["sum_exp"], ma) + rescaled(np.asarray(blk["sum_exp"], dtype=np.float64), mb)
+            mean_a, mean_b = acc["mean"], np.asarray(blk["mean"], dtype=np.float64)
+            delta = mean_b - mean_a
+            mean = mean_a + delta * (nb / n)
+            m2 = (acc["m2"] + np.asarray(blk["m2"], dtype=np.float64)) + (delta * delta) * (na * nb / n)
+            low = np.isneginf(mean_a) | np.isneginf(mean_b)
+            mean, m2 = np.where(low, -np.inf, mean), np.where(low, np.nan, m2)
+            new = {"max": mx, "sum_exp": sum_exp, "mean": mean, "m2": m2}
+            if with_pit:
+                new["pit"] = (acc["pit"] * na + np.asarray(blk["pit"], dtype=np.float64) * nb) / n
+            for k, v in new.items():      # an empty block changes nothing
+                acc[k] = np.where(nb == 0, acc[k], np.where(na == 0, np.asarray(blk[k], dtype=np.float64), v))
+            acc["n"] = acc["n"] + np.asarray(blk["n"], dtype=np.int64)
+    return pointwise_finish(acc)
+
+
+def waic(stats):
+    """WAIC (Watanabe; Vehtari, Gelman & Gabry 2017) from per-cell statistics, over the C cells with n >= 2 terms: lppd = sum lpd,
+    p_waic = sum var, elpd_waic = lppd - p_waic, se = sqrt(C var_c(lpd_c - var_c, ddof=1)).  Returns {"lppd", "p_waic",
+    "elpd_waic", "se", "n_cells", "pointwise": lpd - var per cell, NaN where the cell does not count}."""
+    import numpy as np
+    n = np.asarray(stats["n"])
+    use = n >= 2
+    lpd, var = np.asarray(stats["lpd"], dtype=np.float64), np.asarray(stats["var"], dtype=np.float64)
+    with np.errstate(all="ignore"):
+        point = np.where(use, lpd - var, np.nan)
+        c = int(use.sum())
+        lppd, p_waic = float(np.sum(lpd[use])), float(np.sum(var[use]))
+        se = float(np.sqrt(c * np.var(point[use], ddof=1))) if c >= 2 else float("nan")
+    return {"lppd": lppd, "p_waic": p_waic, "elpd_waic": lppd - p_waic, "se": se, "n_cells": c, "pointwise": point}
