@@ -6,8 +6,11 @@ A accumulates the new infections; a scheduled event sets it back to 0 at every r
 time sees the state before the jump - so the model output at a report time is that week's incidence.  The source declares its
 one output negative binomial (smc_user_obs_family[] = {2}): the output is the MEAN of the count, the variance is
 mean + (b mean)^2 with the overdispersion b = theta[2] estimated beside beta and gamma (the output's proportional entry; its
-additive entry is fixed at 1 and not used).  user_models.count_loglik is the likelihood.  Ends with bands of the mean
-(predictive_summary(noise=False): replicated counts would need a Poisson / gamma sampler, which the library has not got).
+additive entry is fixed at 1 and not used).  user_models.count_loglik is the likelihood.  Ends with two bands per week - of the
+mean incidence (predictive_summary(noise=False)) and of replicated case counts (noise="family": a negative-binomial draw per
+particle on the device, csrc/count_draw.h), with the share of the data inside each: the first is too narrow to hold them, the
+second should hold 90 % - and with the PIT histogram of the counts (pointwise_summary(count_pit=True), user_models.pit_histogram),
+which is flat when the model is calibrated.
 
     python examples/epidemic_run.py [n_particle]"""
 import os
@@ -46,8 +49,16 @@ with pkg.HipEngine(n, 3, device=0) as eng:
         print(f"{nm:6s} = {m[j]:.4f} +- {s[j]:.4f}   (generated with {truth[j]})")
     print(f"R0 = beta / gamma = {np.mean(out['p_pred'][:, 0] / out['p_pred'][:, 1]):.3f} (generated with {truth[0] / truth[1]:.3f}); logZ = {out.get('logZ', float('nan')):.3f}")
     band = eng.predictive_summary(pkg.SMC_SET_PRED, probs=(0.05, 0.5, 0.95))          # bands of the MEAN weekly incidence
+    repl = eng.predictive_summary(pkg.SMC_SET_PRED, probs=(0.05, 0.5, 0.95), noise="family", seed=1)      # ... of replicated case counts
     for e in range(2):
-        print(f"town {e}: week, cases, 5 % / median / 95 % of the mean")
+        print(f"town {e}: week, cases, 5 % / median / 95 % of the mean, 5 % / median / 95 % of replicated counts")
         for i in range(1, weeks.size):
-            q = band["quantile"][:, e, i, 0]
-            print(f"   {int(weeks[i]):2d}  {int(cases[e, i, 0]):5d}   {q[0]:8.1f} {q[1]:8.1f} {q[2]:8.1f}")
+            q, r = band["quantile"][:, e, i, 0], repl["quantile"][:, e, i, 0]
+            print(f"   {int(weeks[i]):2d}  {int(cases[e, i, 0]):5d}   {q[0]:8.1f} {q[1]:8.1f} {q[2]:8.1f}   {r[0]:8.1f} {r[1]:8.1f} {r[2]:8.1f}")
+    seen = np.isfinite(cases)
+    for name, b in (("mean", band), ("replicated counts", repl)):
+        inside = (cases >= b["lower"][0]) & (cases <= b["upper"][2]) & seen
+        print(f"share of the {int(seen.sum())} observed counts inside the 5 % - 95 % band of the {name}: {inside.sum() / seen.sum():.2f}")
+    pw = eng.pointwise_summary(pkg.SMC_SET_PRED, count_pit=True, seed=1)
+    hist = pkg.user_models.pit_histogram(pw["pit_lower"][seen], pw["pit_upper"][seen], bins=5)
+    print("PIT histogram of the counts (5 bins, flat = 0.2 each):", np.round(hist, 3), f"; elpd_waic {pw['waic']['elpd_waic']:.1f}")

@@ -353,7 +353,8 @@ typedef struct smc_user_model_spec {
      * The Poisson form needs no lgamma on the device and does not cancel at large counts.  Below b around 1e-4 the lgamma difference
      * of the negative binomial loses digits: declare the output Poisson, or keep the prior off 0.  Early rejection stays exact (the
      * floors do not depend on the solve); the LDS table does not grow.  smc_user_predict returns lk under this
-     * likelihood, designs give the mean; smc_user_predict_summary with noise = 1 is refused (no Poisson / gamma sampler).
+     * likelihood, designs give the mean; smc_user_predict_summary with noise = 1 is refused (it draws Gaussian noise only), noise = 2
+     * draws replicated counts, and smc_user_pointwise_summary_opt ranks the observed counts among them (the PIT).
      * smc_user_obs_family and smc_user_count_check below apply the rules without a GPU.  A dump of such a source also writes
      * user_count.h. */
 } smc_user_model_spec;
@@ -489,13 +490,23 @@ int smc_user_predict_at(smc_ctx *ctx, const double *particle, int64_t n, const d
  * method "lower" / "higher"; exact (a radix select), no sketch.  m = 0: NaN in all of them.
  * noise != 0: the summaries are of replicated observations pred + sigma_p s_k z - sigma_p the particle's last parameter (est_sigma)
  * or sigma_fixed, s_k the model's obs_scale, z a standard normal (Philox4x32-10, Box-Muller) keyed by (seed, global_offset + p,
- * c): independent of the staging groups.  noise == 0 draws nothing.
+ * c): independent of the staging groups.  noise == 0 draws nothing.  noise = 1 (SMC_PRED_NOISE_GAUSSIAN) on a model with a count
+ * output is refused: it calls no count sampler.
+ * noise = 2 (SMC_PRED_NOISE_FAMILY): replicated observations of EVERY family.  A Gaussian output gets noise = 1's value, bit for bit
+ * (block 0 of the cell's Philox stream); a count output's value is a count drawn with the prediction as its mean - Poisson, or
+ * negative binomial with the particle's b_k (mean mu, variance mu + (b_k mu)^2: Poisson(mu b_k^2 G), G ~ Gamma(1 / b_k^2, 1)) - from
+ * blocks 1, 2, .. of the same stream: inversion below a mean of 10, Hoermann's PTRS from there on, Marsaglia-Tsang for the gamma
+ * (csrc/count_draw.h; tests/count_draw_reference.py is the same in NumPy).  The draw is NaN, and leaves n_finite like a failed
+ * solve, for a mean that is NaN, negative, infinite or >= 2^52 and for a b_k that is not finite and > 0 on a negative-binomial
+ * output.  On a model without count outputs noise = 2 is noise = 1.
  * Staging: predictions plus keys, 2 x n_local x n_t_new x n_obs x 8 B per experiment, stay within max_staging_bytes (0: most of the
  * free device memory) by running groups of experiments; a single experiment that does not fit is refused with the bytes needed.
  * Nothing with a particle axis leaves the device: cells x (3 + 2 n_probs) numbers and the counters come back in one
  * synchronisation.  The particle sets, their lk, the accept flags and smc_work_totals stay as they were.  n_failed / attempts as
  * smc_user_predict_at.  kernel_ms (may be NULL): [0] the prediction sweeps, [1] the summary kernels, from events.
  * Several ranks: the summary describes THIS rank's block of particles only; merging order statistics across ranks is not done. */
+#define SMC_PRED_NOISE_GAUSSIAN 1
+#define SMC_PRED_NOISE_FAMILY 2
 int smc_user_predict_summary(smc_ctx *ctx, int set, const double *t_new, const double *cond_new, int n_ex_new, int n_t_new,
                              const double *probs, int n_probs, int noise, uint64_t seed, int64_t global_offset,
                              size_t max_staging_bytes, double *mean, double *sd, double *lower, double *upper, int64_t *n_finite,
@@ -521,7 +532,8 @@ int smc_user_pointwise(smc_ctx *ctx, const double *particle, int64_t n, double *
  * sum_exp[c] = sum exp(l - max), mean[c] = sum l / n, m2[c] = sum (l - mean)^2 (two-pass) - raw, so that the statistics of several
  * ranks' blocks merge (user_models.pointwise_merge): lpd = max + log(sum_exp / n), var = m2 / (n - 1).  n = 0: NaN in all but n.
  * pit[c], for an observed quantified Gaussian cell: the mean of Phi((obs - f) / sd) over the particles with a finite f and valid
- * noise parameters; NaN elsewhere (censored and count cells: there is no CDF on the device).  Every sum runs per thread in index
+ * noise parameters; NaN elsewhere (a censored cell has none; a count cell's is formed from replicated draws by
+ * smc_user_pointwise_summary_opt below, and stays NaN here).  Every sum runs per thread in index
  * order and then through a fixed tree (no atomics): a repeated call returns the same bits, and so does any max_staging_bytes.
  * Staging as smc_user_predict_summary's (predictions plus terms, 2 x n_local x n_t x n_obs x 8 B per experiment) plus 1/32 of it
  * for the PIT partials, within max_staging_bytes (0: most of the free device memory) by running groups of experiments; a single
@@ -530,6 +542,24 @@ int smc_user_pointwise(smc_ctx *ctx, const double *particle, int64_t n, double *
  * NULL): [0] the prediction sweeps, [1] the pointwise kernels, from events.  Several ranks: THIS rank's block only. */
 int smc_user_pointwise_summary(smc_ctx *ctx, int set, size_t max_staging_bytes, int64_t *n, double *max, double *sum_exp, double *mean,
                                double *m2, double *pit, int64_t *n_failed, int64_t *attempts, double *kernel_ms);
+/* ... with options; opts == NULL is smc_user_pointwise_summary, bit for bit (which is this call with NULL).
+ * count_pit != 0: the PIT of COUNT cells, without a CDF.  For every observed count cell c with observation y, over the particles with
+ * a finite prediction f and valid noise parameters - their number is pit_n[c] - a replicated count is drawn with mean f (Poisson, or
+ * negative binomial with the particle's b_k; the sampler of smc_user_predict_summary's noise = 2) from the Philox stream keyed by
+ * (seed, global_offset + p, tag 0x504954, c); pit_below[c] counts the draws < y and pit_equal[c] those == y (a NaN draw, f < 0 or
+ * >= 2^52, is neither).  below / n estimates F(y - 1) and equal / n the mass at y: user_models.count_pit and pit_histogram make the
+ * randomised PIT and the non-randomised histogram of them.  Integer counts: blocks of particles and ranks merge by addition, and
+ * staging groups cannot change them.  All three are 0 on every other cell, and on a model without count outputs.  pit stays NaN
+ * on count cells; every other result is the one of a call without options.  Staging grows by 4 B per 32 particles and cell. */
+typedef struct smc_pointwise_opts {
+    int count_pit;
+    uint64_t seed;
+    int64_t global_offset;
+    int64_t *pit_below, *pit_equal, *pit_n;      /* cells each; needed with count_pit != 0 */
+} smc_pointwise_opts;
+int smc_user_pointwise_summary_opt(smc_ctx *ctx, int set, size_t max_staging_bytes, const smc_pointwise_opts *opts, int64_t *n,
+                                   double *max, double *sum_exp, double *mean, double *m2, double *pit, int64_t *n_failed,
+                                   int64_t *attempts, double *kernel_ms);
 /* BDF user model: device-counted work of the LAST smc_loglik / smc_mh_step_* sweep, in the manner of
  * smc_meth_sweep_counters: out = {accepted BDF steps, Newton iterations, LU factorisations, Jacobian evaluations} summed over
  * the sweep's solves (masked proposals left out).  Fails with a message for an RK45 model. */

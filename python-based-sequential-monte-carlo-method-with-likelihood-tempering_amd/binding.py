@@ -27,6 +27,7 @@ PRIOR_MODES = {"mask": 0, "ratio_mask": 1, "ratio": 2}
 RESAMPLING = {"residual_systematic": 0, "systematic": 1, "multinomial": 2}
 SMC_MAX_ESS_CAND = 16
 SMC_PRED_MAX_PROBS = 16
+SMC_PRED_NOISE_GAUSSIAN, SMC_PRED_NOISE_FAMILY = 1, 2      # smc_user_predict_summary's noise
 SMC_ABI_VERSION = 3
 SMC_SWEEP_COUNTER_WORDS = 14
 SWEEP_COUNTER_NAMES = ("n_failed", "rk_attempts", "accepted_now", "accepted_ever", "newton_iters", "factorisations", "failed_solves",
@@ -72,6 +73,13 @@ class UserModelSpec(ctypes.Structure):
 
     def __init__(self, **fields):
         super().__init__(struct_size=ctypes.sizeof(type(self)), **fields)
+
+
+class PointwiseOpts(ctypes.Structure):
+    """smc_pointwise_opts (include/smc_hip.h): the options of smc_user_pointwise_summary_opt.  Pointers only: whoever fills it keeps
+    the three count arrays alive until the call has returned."""
+    _fields_ = [("count_pit", cint), ("seed", u64), ("global_offset", i64), ("pit_below", c_i64p), ("pit_equal", c_i64p),
+                ("pit_n", c_i64p)]
 
 
 # name -> (restype, argtypes); one entry per function of include/smc_hip.h
@@ -131,6 +139,8 @@ SIGNATURES = {
                                          c_dp, c_dp, c_i64p, c_i64p, c_i64p, c_dp]),
     "smc_user_pointwise": (cint, [c_ctx, c_dp, i64, c_dp, c_i64p, c_i64p]),
     "smc_user_pointwise_summary": (cint, [c_ctx, cint, ctypes.c_size_t, c_i64p, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p, c_i64p, c_dp]),
+    "smc_user_pointwise_summary_opt": (cint, [c_ctx, cint, ctypes.c_size_t, ctypes.POINTER(PointwiseOpts), c_i64p, c_dp, c_dp, c_dp, c_dp,
+                                               c_dp, c_i64p, c_i64p, c_dp]),
     "smc_user_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_counters": (cint, [c_ctx, c_i64p]),
     "smc_meth_sweep_check": (cint, [c_ctx, c_i64p]),

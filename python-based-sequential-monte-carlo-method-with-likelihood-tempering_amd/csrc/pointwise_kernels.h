@@ -17,6 +17,7 @@ namespace smc {
 constexpr int kCellObserved = 1, kCellFlagShift = 1, kCellFamilyShift = 3;
 constexpr int kPwTile = 32;          // particles (and cells) per tile of the terms kernel
 constexpr int kPwOutWords = 6;       // results per cell: n, max, sum_exp, mean, m2, pit
+constexpr int kPwCountWords = 3;     // ... and with the PIT of count cells (pit_cnt != nullptr): pit_below, pit_equal, pit_n
 
 // One group of experiments: `pred` as PredSummaryArgs' (pred[p * cells + c]).
 struct PointwiseArgs {
@@ -39,10 +40,19 @@ struct PointwiseArgs {
     const int *cell_code;
     const double *cell_floor;
     double *out;                   // [n | max | sum_exp | mean | m2 | pit] x cells_total
+    // The PIT of count cells (smc_user_pointwise_summary_opt with count_pit; nullptr: not formed, and the terms kernel without the
+    // sampler runs): per observed count cell, over the particles with a finite prediction and valid noise parameters, how many
+    // replicated counts (count_draw.h, tag 0x504954, seed, global_offset + p, the global cell) lie below the observation and how
+    // many equal it.  pit_cnt [cells][tiles]: one word per tile of kPwTile particles, below | equal << 8 | n << 16 (each <= 32);
+    // out then has kPwCountWords more rows, [pit_below | pit_equal | pit_n], integers held in doubles.
+    unsigned *pit_cnt;
+    uint64_t seed;
+    int64_t global_offset;
 };
 
 size_t pointwise_terms_bytes(int64_t n, int cells);
 size_t pointwise_pit_bytes(int64_t n, int cells);
+size_t pointwise_pit_count_bytes(int64_t n, int cells);
 // the terms of a group on ctx->stream; with a.terms also the per-cell reduction
 void launch_pointwise(smc_ctx *ctx, const PointwiseArgs &a);
 

@@ -16,6 +16,7 @@
 #include "user_censor.h"
 #include "user_count.h"
 
+#include "count_draw.h"
 #include "pointwise_kernels.h"
 #include "pointwise_reduce.h"
 #include "smc_internal.h"
@@ -50,8 +51,12 @@ __device__ __forceinline__ double pw_term(int code, double y, double floor_y, do
     return (-0.9189385332046727 - 0.5 * log(sd2)) - (r * r) / (2.0 * sd2);
 }
 
-__global__ void __launch_bounds__(256) pw_terms_kernel(const PointwiseArgs a) {
+// kCountPit: the PIT counts of count cells are formed too (PointwiseArgs::pit_cnt) - the instantiation that holds the sampler,
+// pw_terms_count_kernel; without, pw_terms_kernel is what it was before there was one
+template <bool kCountPit>
+__device__ __forceinline__ void pw_terms_body(const PointwiseArgs &a) {
     __shared__ double tile[kPwTile][kPwTile + 1], phis[kPwTile][kPwTile + 1];
+    __shared__ unsigned cnts[kCountPit ? kPwTile : 1][kPwTile + 1];
     __shared__ double s_a[kPwTile][kUserMaxObs], s_b[kPwTile][kUserMaxObs];
     __shared__ int s_valid[kPwTile];
     const int tx = threadIdx.x % kPwTile, ty = threadIdx.x / kPwTile;      // 32 x 8
@@ -81,15 +86,25 @@ __global__ void __launch_bounds__(256) pw_terms_kernel(const PointwiseArgs a) {
         const int64_t p = p0 + r;
         const int c = c0 + tx;
         double l = nan, phi = nan;
+        unsigned cnt = 0u;
         if (p < a.n && c < a.cells) {
             const int64_t cell = a.cell_base + c;
             const int k = c % a.n_obs;
-            l = pw_term(a.cell_code[cell], a.cell_obs[cell], a.cell_floor[cell], a.pred[p * a.cells + c], s_a[r][k], s_b[r][k], a.nz.scale[k],
-                        s_valid[r] != 0, phi);
+            const int code = a.cell_code[cell];
+            const double y = a.cell_obs[cell], f = a.pred[p * a.cells + c];
+            l = pw_term(code, y, a.cell_floor[cell], f, s_a[r][k], s_b[r][k], a.nz.scale[k], s_valid[r] != 0, phi);
             if (!a.terms) a.ll[p * a.cells + c] = l;
+            if (kCountPit) {      // the replicated count of this particle against the observation
+                const int family = (code >> kCellFamilyShift) & 3;
+                if ((code & kCellObserved) && family != smc_cnt::kGaussian && s_valid[r] != 0 && fabs(f) < __builtin_huge_val()) {
+                    const double yr = smc_draw::count_draw(family, f, s_b[r][k], a.seed, (uint64_t)(a.global_offset + p), smc_draw::kTagPit, (uint64_t)cell);
+                    cnt = (1u << 16) | (yr == y ? 1u << 8 : 0u) | (yr < y ? 1u : 0u);      // a NaN draw is neither
+                }
+            }
         }
         tile[r][tx] = l;
         phis[r][tx] = phi;
+        if (kCountPit) cnts[r][tx] = cnt;
     }
     if (!a.terms) return;
     __syncthreads();
@@ -111,8 +126,16 @@ __global__ void __launch_bounds__(256) pw_terms_kernel(const PointwiseArgs a) {
         double *part = a.pit_part + ((int64_t)(c0 + tx) * (int64_t)gridDim.x + blockIdx.x) * 2;
         part[0] = sum;
         part[1] = cnt;
+        if (kCountPit) {      // three counts of at most 32 each: the fields cannot carry
+            unsigned w = 0u;
+            for (int r = 0; r < kPwTile; ++r) w += cnts[r][tx];
+            a.pit_cnt[(int64_t)(c0 + tx) * (int64_t)gridDim.x + blockIdx.x] = w;
+        }
     }
 }
+
+__global__ void __launch_bounds__(256) pw_terms_kernel(const PointwiseArgs a) { pw_terms_body<false>(a); }
+__global__ void __launch_bounds__(256) pw_terms_count_kernel(const PointwiseArgs a) { pw_terms_body<true>(a); }
 
 // the fixed tree of pointwise_reduce.h over the block's partials
 template <class T, class Join>
@@ -146,10 +169,12 @@ __global__ void __launch_bounds__(smc_pw::kPwThreads) pw_cell_kernel(const Point
         smc_pw::pass1_add(p1, x.y);
     }
     p1 = pw_block_tree(p1, s1, smc_pw::pass1_join);
-    if (p1.n == 0.0) {      // no particle has a term here
+    if (p1.n == 0.0) {      // no particle has a term here (and none a finite prediction: the PIT counts are 0)
         if (tid == 0) {
             a.out[cell] = 0.0;
             for (int j = 1; j < kPwOutWords; ++j) a.out[(int64_t)j * ct + cell] = nan;
+            if (a.pit_cnt)
+                for (int j = 0; j < kPwCountWords; ++j) a.out[(int64_t)(kPwOutWords + j) * ct + cell] = 0.0;
         }
         return;
     }
@@ -176,6 +201,25 @@ __global__ void __launch_bounds__(smc_pw::kPwThreads) pw_cell_kernel(const Point
         q = pw_block_tree(q, s2, smc_pw::pass2_join);
         pit = q.sum_exp / q.m2;      // no term: 0 / 0
     }
+    // the PIT counts of a count cell: the tiles' words in the same fixed order; integers below 2^53, exact in any order.
+    // Pass1 carries them: n = below, max = equal, sum = n.
+    if (a.pit_cnt) {
+        const int64_t tiles = pw_tiles(a.n);
+        const unsigned *w = a.pit_cnt + (int64_t)c * tiles;
+        smc_pw::Pass1 q{0.0, 0.0, 0.0};
+        for (int64_t i = tid; i < tiles; i += smc_pw::kPwThreads) {
+            const unsigned x = w[i];
+            q.n += (double)(x & 0xFFu);
+            q.max += (double)((x >> 8) & 0xFFu);
+            q.sum += (double)(x >> 16);
+        }
+        q = pw_block_tree(q, s1, [](const smc_pw::Pass1 &x, const smc_pw::Pass1 &y) { return smc_pw::Pass1{x.n + y.n, x.max + y.max, x.sum + y.sum}; });
+        if (tid == 0) {
+            a.out[(int64_t)kPwOutWords * ct + cell] = q.n;
+            a.out[(int64_t)(kPwOutWords + 1) * ct + cell] = q.max;
+            a.out[(int64_t)(kPwOutWords + 2) * ct + cell] = q.sum;
+        }
+    }
     if (tid == 0) {
         const smc_pw::Stats st = smc_pw::finish(p1, p2);
         a.out[cell] = st.n;
@@ -189,12 +233,16 @@ __global__ void __launch_bounds__(smc_pw::kPwThreads) pw_cell_kernel(const Point
 
 size_t pointwise_terms_bytes(int64_t n, int cells) { return (size_t)pw_stride(n) * (size_t)cells * sizeof(double); }
 size_t pointwise_pit_bytes(int64_t n, int cells) { return (size_t)pw_tiles(n) * (size_t)cells * 2 * sizeof(double); }
+size_t pointwise_pit_count_bytes(int64_t n, int cells) { return (size_t)pw_tiles(n) * (size_t)cells * sizeof(unsigned); }
 
 void launch_pointwise(smc_ctx *c, const PointwiseArgs &a) {
     if (a.n <= 0 || a.cells <= 0) return;
     const int64_t np = a.terms ? pw_stride(a.n) : a.n;
     const dim3 g((unsigned)((np + kPwTile - 1) / kPwTile), (unsigned)((a.cells + kPwTile - 1) / kPwTile));
-    hipLaunchKernelGGL(pw_terms_kernel, g, dim3(256), 0, c->stream, a);
+    if (a.terms && a.pit_cnt)
+        hipLaunchKernelGGL(pw_terms_count_kernel, g, dim3(256), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL(pw_terms_kernel, g, dim3(256), 0, c->stream, a);
     if (a.terms) hipLaunchKernelGGL(pw_cell_kernel, dim3((unsigned)a.cells), dim3(smc_pw::kPwThreads), 0, c->stream, a);
 }
 

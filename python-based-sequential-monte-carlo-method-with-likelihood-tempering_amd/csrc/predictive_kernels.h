@@ -22,6 +22,9 @@ struct PredSummaryArgs {
     int n_obs;
     // replicated observations (noise != 0): value = pred + sigma_p * scale[k] * z(seed, global_offset + p, cell_base + c)
     int noise;
+    // ... of every family (noise = 2 on a model with a count output): family[k] != 0 makes the value of output k the count
+    // count_draw.h draws with mean pred and the particle's proportional entry b_k; a Gaussian output keeps the line above
+    int family[8];
     const double *theta;           // SoA, theta[c * stride + p]
     int64_t stride;
     int dim, est_sigma;
@@ -40,7 +43,8 @@ struct PredSummaryArgs {
 };
 
 size_t pred_summary_key_bytes(int64_t n, int cells);
-// the two launches of a group, on ctx->stream: transpose into keys (adding the noise), then one block per cell
+// the two launches of a group, on ctx->stream: transpose into keys (adding the noise), then one block per cell; a model
+// without count outputs (every family 0) launches the keys kernel that holds no sampler
 void launch_pred_summary(smc_ctx *ctx, const PredSummaryArgs &a);
 
 }  // namespace smc

@@ -9,6 +9,7 @@
 // All sums run in an order fixed by the block size, so a repeated call returns the same bits.
 #include <hip/hip_runtime.h>
 
+#include "count_draw.h"
 #include "philox.h"
 #include "predictive_kernels.h"
 #include "smc_internal.h"
@@ -23,6 +24,9 @@ constexpr int kSelBatch = 2;          // 16-byte loads (two keys each) a thread 
 // a cell's keys start on a 16-byte boundary: the stride is n rounded up to even, the odd one out holds kNanKey
 __host__ __device__ inline int64_t key_stride(int64_t n) { return (n + 1) & ~(int64_t)1; }
 
+// kCounts: some output of the model is a count (PredSummaryArgs::family) - the instantiation that holds the sampler; without,
+// the kernel is what it was before there was one
+template <bool kCounts>
 __global__ void __launch_bounds__(256) pred_keys_kernel(const PredSummaryArgs a) {
     __shared__ u64 tile[kTile][kTile + 1];
     const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;      // 32 x 8
@@ -34,7 +38,12 @@ __global__ void __launch_bounds__(256) pred_keys_kernel(const PredSummaryArgs a)
         u64 key = smc_sel::kNanKey;
         if (p < a.n && c < a.cells) {
             double v = a.pred[p * a.cells + c];
-            if (a.noise) {
+            const int fam = kCounts ? a.family[c % a.n_obs] : 0;
+            if (kCounts && a.noise && fam != 0) {      // a replicated count: mean v, the particle's b_k (count_draw.h)
+                const int k = c % a.n_obs;
+                const double bk = !a.nz.prop ? 0.0 : (a.nz.prop_index[k] >= 0 ? a.theta[(int64_t)a.nz.prop_index[k] * a.stride + p] : a.nz.prop_fixed[k]);
+                v = smc_draw::count_draw(fam, v, bk, a.seed, (uint64_t)(a.global_offset + p), smc_draw::kTagPredict, (uint64_t)(a.cell_base + c));
+            } else if (a.noise) {
                 const int64_t cell = a.cell_base + c;
                 const double sigma = a.est_sigma ? a.theta[(int64_t)(a.dim - 1) * a.stride + p] : a.sigma_fixed;
                 const u32x4 q = philox_block(a.seed, (uint64_t)(a.global_offset + p), (0x505245ull << 32) | (uint64_t)cell, 0);
@@ -207,7 +216,12 @@ size_t pred_summary_key_bytes(int64_t n, int cells) { return (size_t)key_stride(
 void launch_pred_summary(smc_ctx *c, const PredSummaryArgs &a) {
     if (a.n <= 0 || a.cells <= 0) return;
     const dim3 g((unsigned)((key_stride(a.n) + kTile - 1) / kTile), (unsigned)((a.cells + kTile - 1) / kTile));
-    hipLaunchKernelGGL(pred_keys_kernel, g, dim3(256), 0, c->stream, a);
+    bool counts = false;
+    for (int k = 0; k < a.n_obs; ++k) counts = counts || a.family[k] != 0;
+    if (counts)
+        hipLaunchKernelGGL(pred_keys_kernel<true>, g, dim3(256), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL(pred_keys_kernel<false>, g, dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(pred_select_kernel, dim3((unsigned)a.cells), dim3(kSelThreads), 0, c->stream, a);
 }
 

@@ -2031,9 +2031,12 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     for (int j = 0; j < n_probs; ++j)
         if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return smc_fail(c, "smc_user_predict_summary: a probability outside [0, 1]");
     if (!mean || !sd || !lower || !upper || !n_finite) return smc_fail(c, "smc_user_predict_summary: NULL result array");
-    if (noise != 0 && u->count)
+    if (noise != 0 && noise != SMC_PRED_NOISE_GAUSSIAN && noise != SMC_PRED_NOISE_FAMILY)
+        return smc_fail(c, "smc_user_predict_summary: noise must be 0, 1 (SMC_PRED_NOISE_GAUSSIAN) or 2 (SMC_PRED_NOISE_FAMILY)");
+    if (noise == SMC_PRED_NOISE_GAUSSIAN && u->count)
         return smc_fail(c, "smc_user_predict_summary: noise = 1 on a model with a count output: replicated count draws need a Poisson / gamma "
-                           "sampler on the Philox stream, which the library does not have (noise = 0 gives the bands of the mean)");
+                           "sampler on the Philox stream, which noise = 1 does not call: noise = 2 (SMC_PRED_NOISE_FAMILY) draws every "
+                           "output under its family (noise = 0 gives the bands of the mean)");
     if (hipSetDevice(c->device) != hipSuccess) return smc_fail(c, "hipSetDevice failed");
     if (n_failed) *n_failed = 0;
     if (attempts) *attempts = 0;
@@ -2109,6 +2112,7 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
         a.cells_total = cells_total;
         a.n_obs = u->n_obs;
         a.noise = noise != 0;
+        for (int j = 0; j < kUserMaxObs; ++j) a.family[j] = (noise == SMC_PRED_NOISE_FAMILY && u->count) ? u->family[j] : 0;
         a.theta = P.theta;
         a.stride = P.stride;
         a.dim = c->dim;
@@ -2163,8 +2167,17 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
 
 int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, int64_t *n_terms, double *max, double *sum_exp, double *mean,
                                double *m2, double *pit, int64_t *n_failed, int64_t *attempts, double *kernel_ms) {
+    return smc_user_pointwise_summary_opt(c, set, max_staging_bytes, nullptr, n_terms, max, sum_exp, mean, m2, pit, n_failed, attempts, kernel_ms);
+}
+
+int smc_user_pointwise_summary_opt(smc_ctx *c, int set, size_t max_staging_bytes, const smc_pointwise_opts *opts, int64_t *n_terms, double *max,
+                                   double *sum_exp, double *mean, double *m2, double *pit, int64_t *n_failed, int64_t *attempts,
+                                   double *kernel_ms) {
     const char *who = "smc_user_pointwise_summary";
     if (!c) return smc_fail(nullptr, "NULL context");
+    const bool count_pit = opts && opts->count_pit != 0;
+    if (count_pit && (!opts->pit_below || !opts->pit_equal || !opts->pit_n))
+        return smc_fail(c, "smc_user_pointwise_summary_opt: count_pit with a NULL pit_below, pit_equal or pit_n");
     UserModel *u = (UserModel *)c->user;
     if (c->model_kind != 3 || !u || !c->have_model) return smc_fail(c, "smc_user_pointwise_summary: no user model has been set");
     if (set != SMC_SET_PRED && set != SMC_SET_FILT) return smc_fail(c, "smc_user_pointwise_summary: set must be SMC_SET_PRED or SMC_SET_FILT");
@@ -2185,8 +2198,12 @@ int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, in
     // the results
     const size_t row = (size_t)n_t * u->n_obs;
     const int64_t cells_total = (int64_t)n_ex * (int64_t)row;
-    const size_t out_words = (size_t)cells_total * kPwOutWords;
-    const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pointwise_terms_bytes(n, (int)row) + pointwise_pit_bytes(n, (int)row);
+    // the PIT of count cells: three more result rows and one word per 32 particles and cell; a model without count outputs has no
+    // such cell - the counts are 0 and the kernels are the ones of a call without options
+    const bool draw = count_pit && u->count;
+    const size_t out_words = (size_t)cells_total * (kPwOutWords + (draw ? kPwCountWords : 0));
+    const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pointwise_terms_bytes(n, (int)row) + pointwise_pit_bytes(n, (int)row) +
+                          (draw ? pointwise_pit_count_bytes(n, (int)row) : 0);
     const size_t fixed = (size_t)n * sizeof(double) + out_words * sizeof(double);
     size_t budget = max_staging_bytes;
     if (budget == 0) {      // default: most of what is free
@@ -2206,12 +2223,14 @@ int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, in
     std::vector<hipEvent_t> ev(3 * groups.size(), nullptr);
     DesignItems items;
     double *d_plk = nullptr, *d_ppred = nullptr, *d_out = nullptr, *d_terms = nullptr, *d_pit = nullptr;
+    unsigned *d_cnt = nullptr;
     std::vector<double> h_out(out_words);
     int rc = 0;
     bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
               hipMalloc(&d_ppred, (size_t)n * g_max * row * sizeof(double)) == hipSuccess &&
               hipMalloc(&d_terms, pointwise_terms_bytes(n, (int)(g_max * row))) == hipSuccess &&
               hipMalloc(&d_pit, pointwise_pit_bytes(n, (int)(g_max * row))) == hipSuccess &&
+              (!draw || hipMalloc(&d_cnt, pointwise_pit_count_bytes(n, (int)(g_max * row))) == hipSuccess) &&
               hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess;
     for (size_t k = 0; ok && k < groups.size(); ++k) {
         const int e0 = (int)k * g_max;
@@ -2240,6 +2259,9 @@ int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, in
         a.pred = d_ppred;
         a.terms = d_terms;
         a.pit_part = d_pit;
+        a.pit_cnt = d_cnt;
+        a.seed = draw ? opts->seed : 0;
+        a.global_offset = draw ? opts->global_offset : 0;
         a.n = n;
         a.cells = (int)(dg.n_ex * row);
         a.cell_base = (int64_t)dg.e0 * (int64_t)row;
@@ -2266,6 +2288,11 @@ int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, in
             m2[i] = h_out[4 * ct + i];
             pit[i] = h_out[5 * ct + i];
         }
+        for (size_t i = 0; count_pit && i < ct; ++i) {
+            opts->pit_below[i] = draw ? (int64_t)h_out[(kPwOutWords + 0) * ct + i] : 0;
+            opts->pit_equal[i] = draw ? (int64_t)h_out[(kPwOutWords + 1) * ct + i] : 0;
+            opts->pit_n[i] = draw ? (int64_t)h_out[(kPwOutWords + 2) * ct + i] : 0;
+        }
         if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
         if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
         for (size_t k = 0; kernel_ms && k < groups.size(); ++k) {
@@ -2282,6 +2309,7 @@ int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, in
     (void)hipFree(d_ppred);
     (void)hipFree(d_terms);
     (void)hipFree(d_pit);
+    (void)hipFree(d_cnt);
     (void)hipFree(d_out);
     return rc;
 }

@@ -337,19 +337,25 @@ def _rng_state_from_json(j):
 def _pointwise_all_ranks(engine, comm, kwargs):
     """HipEngine.pointwise_summary of this rank's block; with several ranks the blocks' raw statistics allgathered and merged in
     rank order, so that every rank holds the statistics of the whole population."""
-    from .user_models import pointwise_merge, waic
+    from .user_models import count_pit_fill, pointwise_merge, waic
     mine = engine.pointwise_summary(**kwargs)
     if comm.size == 1:
         return mine
-    keys = ("n", "max", "sum_exp", "mean", "m2", "pit")
+    # with count_pit the three integer arrays travel beside the statistics (below 2^53: exact as doubles) and add
+    with_counts = bool(kwargs.get("count_pit"))
+    keys = ("n", "max", "sum_exp", "mean", "m2", "pit") + (("pit_below", "pit_equal", "pit_n") if with_counts else ())
+    whole = ("n", "pit_below", "pit_equal", "pit_n")
     shape = mine["n"].shape
     flat = np.concatenate([np.asarray(mine[k], dtype=np.float64).reshape(-1) for k in keys]
                           + [np.array([mine["n_failed"], mine["rk_attempts"]], dtype=np.float64)])
     parts = np.asarray(comm.allgather(flat)).reshape(comm.size, -1)      # n, failures and attempts are integers below 2^53: exact
     cells = mine["n"].size
-    blocks = [{k: (p[j * cells:(j + 1) * cells].reshape(shape).astype(np.int64) if k == "n" else p[j * cells:(j + 1) * cells].reshape(shape))
+    blocks = [{k: (p[j * cells:(j + 1) * cells].reshape(shape).astype(np.int64) if k in whole else p[j * cells:(j + 1) * cells].reshape(shape))
                for j, k in enumerate(keys)} for p in parts]
     out = pointwise_merge(blocks)
+    if with_counts:      # pit on count cells from the merged counts, not from the blocks' own randomised values
+        out.update(count_pit_fill(out["pit"], out["pit_below"], out["pit_equal"], out["pit_n"], getattr(engine, "user_family", None),
+                                  kwargs.get("seed", 0)))
     out.update({"n_failed": int(parts[:, -2].sum()), "rk_attempts": int(parts[:, -1].sum()), "kernel_ms": mine["kernel_ms"]})
     out["waic"] = waic(out)
     return out
@@ -377,6 +383,10 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     PIT - formed on the device before returning and stored as out["pointwise"].  With several ranks each rank's block statistics
     are allgathered (comm.allgather) and merged in rank order (user_models.pointwise_merge), so every rank returns the whole
     population's statistics; "n_failed" and "rk_attempts" are then summed over the ranks and "kernel_ms" stays this rank's.
+    With "count_pit": True the PIT of count cells is formed from replicated counts: global_offset defaults to the block's start as
+    for predictive=, the ranks' integer counts are allgathered beside the statistics and added, and "pit" on count cells comes
+    from the merged counts (user_models.count_pit_fill).  predictive={"noise": "family"} gives the bands of replicated
+    observations of every family.
 
     Returns a dict: final particles (this rank's block), lk, schedule records, logZ, counters.
     """
@@ -623,5 +633,8 @@ def run_smc(engine, s: SMCSettings | None = None, comm=None, rng: str = "numpy",
     if predictive is not None:                    # this rank's block, its noise drawn under the block's global particle numbers
         out["predictive"] = engine.predictive_summary(**{"which": SMC_SET_PRED, "global_offset": lo, **predictive})
     if pointwise is not None and pointwise is not False:
-        out["pointwise"] = _pointwise_all_ranks(engine, comm, {"which": SMC_SET_PRED, **(pointwise if isinstance(pointwise, dict) else {})})
+        pw = {"which": SMC_SET_PRED, **(pointwise if isinstance(pointwise, dict) else {})}
+        if pw.get("count_pit"):                   # the replicated counts are drawn under the block's global particle numbers
+            pw = {"global_offset": lo, **pw}
+        out["pointwise"] = _pointwise_all_ranks(engine, comm, pw)
     return out

@@ -223,7 +223,8 @@ class HipEngine:
         entry must be ("fixed", 1.0) and its obs_scale 1 (they are not used), its finite values non-negative integers, and it
         takes no censor flag.  The model takes the noise path; noise=None stands for the Gaussian outputs at est_sigma /
         sigma_fixed and the counts at fixed 1.  user_models.count_loglik is the likelihood, count_layout the rules (ValueError
-        for what breaks them), obs_family reads the list; predictive_summary(noise=True) is refused for such a model.  An
+        for what breaks them), obs_family reads the list; predictive_summary(noise=True) is refused for such a model, noise="family"
+        draws replicated counts and pointwise_summary(count_pit=True) ranks the observed counts among them.  An
         all-zero list, or no such name, leaves the model as it is.  Every feature is a group of fields of one
         smc_user_model_spec, set by smc_set_model_user_spec; an absent feature takes the path, and gives the bits, it always had."""
         if method not in B.USER_METHODS:
@@ -636,7 +637,10 @@ class HipEngine:
         (n_probs, n_ex, n_t, n_obs) - the order statistics np.nanquantile picks with method "lower" / "higher" and the linear
         value between them (user_models.quantile_ranks, linear_quantile); "n_failed", "rk_attempts"; "kernel_ms":
         {"predict", "summary"}}.  noise=True: of replicated observations pred + sigma s_k z (Philox keyed by seed,
-        global_offset + particle, cell).  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
+        global_offset + particle, cell); refused on a model with a count output.  noise="family": replicated observations of every
+        family - a Gaussian output as under noise=True, bit for bit, a count output a Poisson / negative-binomial count drawn with
+        the prediction as its mean (csrc/count_draw.h; NaN draws, e.g. of a negative mean, leave n_finite): the band that
+        should hold the data.  On a model without count outputs it is noise=True.  Only the summaries cross the bus; the sets, their lk and the accept flags are untouched.
         With several ranks each rank summarises its own block only, and the caller passes the block's start as global_offset so
         that the noise is drawn under the particles' global numbers - run_smc(predictive=...) does; with the default 0 every rank
         would draw the noise of particles 0 .. n_local - 1 and the ranks' bands would be correlated copies.
@@ -646,6 +650,12 @@ class HipEngine:
         q = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))
         if not 1 <= q.size <= B.SMC_PRED_MAX_PROBS or not np.all((q >= 0) & (q <= 1)):
             raise ValueError(f"predictive_summary: 1 .. {B.SMC_PRED_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
+        if isinstance(noise, str):
+            if noise != "family":
+                raise ValueError(f"predictive_summary: noise must be False, True or \"family\", got {noise!r}")
+            noise_code = B.SMC_PRED_NOISE_FAMILY
+        else:
+            noise_code = B.SMC_PRED_NOISE_GAUSSIAN if noise else 0
         t, cbuf, cargs, shape = self._design("predictive_summary", t, cond, inputs, events)
         cells = (shape[0], shape[1], self.user_n_obs)
         mean, sd = np.empty(cells), np.empty(cells)
@@ -653,7 +663,7 @@ class HipEngine:
         nfin = np.empty(cells, dtype=np.int64)
         nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
         ms = np.zeros(2)
-        self._ck(self.L.smc_user_predict_summary(self.ctx, int(which), *cargs, _dp(q), q.size, int(bool(noise)), int(seed),
+        self._ck(self.L.smc_user_predict_summary(self.ctx, int(which), *cargs, _dp(q), q.size, noise_code, int(seed),
                                                  int(global_offset), int(max_staging_bytes), _dp(mean), _dp(sd), _dp(lower),
                                                  _dp(upper), nfin.ctypes.data_as(B.c_i64p), ctypes.byref(nf), ctypes.byref(att),
                                                  _dp(ms)), "smc_user_predict_summary")
@@ -679,13 +689,19 @@ class HipEngine:
                  "smc_user_pointwise")
         return ll, {"n_failed": nf.value, "rk_attempts": att.value}
 
-    def pointwise_summary(self, which=SMC_SET_FILT, max_staging_bytes=0):
+    def pointwise_summary(self, which=SMC_SET_FILT, max_staging_bytes=0, count_pit=False, seed=0, global_offset=0):
         """Per observation the statistics of its log-likelihood term over a resident particle set, formed on the device
         (include/smc_hip.h: smc_user_pointwise_summary).  Returns the dict of user_models.pointwise_stats - "n", "max", "sum_exp",
         "mean", "m2", "lpd", "var", each (n_ex, n_t, n_obs) - plus "pit" (quantified Gaussian cells; NaN on censored and count
-        cells, for which the device has no CDF), "n_failed", "rk_attempts", "kernel_ms": {"predict", "pointwise"} and "waic"
+        cells; count_pit=True below fills the count cells), "n_failed", "rk_attempts", "kernel_ms": {"predict", "pointwise"} and "waic"
         (user_models.waic of it).  Only the statistics cross the bus; the sets, their lk and the accept flags are untouched.
-        With several ranks each rank describes its own block; user_models.pointwise_merge joins them (run_smc(pointwise=) does)."""
+        With several ranks each rank describes its own block; user_models.pointwise_merge joins them (run_smc(pointwise=) does).
+        count_pit=True (smc_user_pointwise_summary_opt): the PIT of count cells from replicated draws (Philox keyed by seed,
+        global_offset + particle, cell - pass the block's start as global_offset on several ranks, as for predictive_summary).  The
+        result gains "pit_below", "pit_equal", "pit_n" (int64: the particles' replicated counts below and at the observation, and
+        how many particles count; 0 off the count cells), "pit_lower" = below / n and "pit_upper" = (below + equal) / n - the
+        estimates of F(y - 1) and F(y), what user_models.pit_histogram takes; a Gaussian cell enters with both = pit - and "pit"
+        on count cells becomes the randomised PIT user_models.count_pit(below, equal, n, seed).  Everything else is unchanged."""
         if self.model is None or self.model[0] != "user":
             raise SmcError("pointwise_summary: no user model has been set")
         cells = (self.model[1], self.model[2], self.user_n_obs)
@@ -693,11 +709,21 @@ class HipEngine:
         mx, se, mean, m2, pit = (np.empty(cells) for _ in range(5))
         nf, att = ctypes.c_int64(0), ctypes.c_int64(0)
         ms = np.zeros(2)
-        self._ck(self.L.smc_user_pointwise_summary(self.ctx, int(which), int(max_staging_bytes), n.ctypes.data_as(B.c_i64p), _dp(mx),
-                                                   _dp(se), _dp(mean), _dp(m2), _dp(pit), ctypes.byref(nf), ctypes.byref(att),
-                                                   _dp(ms)), "smc_user_pointwise_summary")
-        from .user_models import pointwise_finish, waic
+        if count_pit:
+            below, equal, pn = (np.zeros(cells, dtype=np.int64) for _ in range(3))
+            opts = B.PointwiseOpts(count_pit=1, seed=int(seed), global_offset=int(global_offset), pit_below=below.ctypes.data_as(B.c_i64p),
+                                   pit_equal=equal.ctypes.data_as(B.c_i64p), pit_n=pn.ctypes.data_as(B.c_i64p))
+            self._ck(self.L.smc_user_pointwise_summary_opt(self.ctx, int(which), int(max_staging_bytes), ctypes.byref(opts),
+                                                           n.ctypes.data_as(B.c_i64p), _dp(mx), _dp(se), _dp(mean), _dp(m2), _dp(pit),
+                                                           ctypes.byref(nf), ctypes.byref(att), _dp(ms)), "smc_user_pointwise_summary_opt")
+        else:
+            self._ck(self.L.smc_user_pointwise_summary(self.ctx, int(which), int(max_staging_bytes), n.ctypes.data_as(B.c_i64p), _dp(mx),
+                                                       _dp(se), _dp(mean), _dp(m2), _dp(pit), ctypes.byref(nf), ctypes.byref(att),
+                                                       _dp(ms)), "smc_user_pointwise_summary")
+        from .user_models import count_pit_fill, pointwise_finish, waic
         out = pointwise_finish({"n": n, "max": mx, "sum_exp": se, "mean": mean, "m2": m2, "pit": pit})
+        if count_pit:
+            out.update(count_pit_fill(pit, below, equal, pn, getattr(self, "user_family", None), seed))
         out.update({"n_failed": nf.value, "rk_attempts": att.value, "kernel_ms": {"predict": float(ms[0]), "pointwise": float(ms[1])}})
         out["waic"] = waic(out)
         return out

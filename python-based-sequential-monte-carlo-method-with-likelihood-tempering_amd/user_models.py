@@ -916,7 +916,7 @@ def pointwise_pit(pred, t, obs, theta, noise, obs_scale=None, censor=None, famil
     of smc_user_pointwise_summary's pit: per observed cell with flag 0 on a Gaussian output
         pit = sum Phi((obs - f) / sd) / n_pit,   Phi(z) = erfc(-z / sqrt 2) / 2,
     over the n_pit particles with a finite f and valid noise parameters (n_pit = 0: NaN); NaN on every other cell - the PIT of a
-    censored or count value is not formed (there is no CDF on the device).  Arguments as pointwise_loglik's; returns
+    censored value is not formed, that of a count comes from replicated draws instead of a CDF (count_pit).  Arguments as pointwise_loglik's; returns
     (n_ex, n_t, n_obs).  A calibrated model has PIT values uniform on (0, 1) over the cells."""
     import numpy as np
     from scipy.special import erfc
@@ -930,6 +930,61 @@ def pointwise_pit(pred, t, obs, theta, noise, obs_scale=None, censor=None, famil
         phi = np.where(use, 0.5 * erfc(-z / np.sqrt(2.0)), 0.0)
         pit = phi.sum(axis=0) / use.sum(axis=0)
     return np.where(cell, pit, np.nan)
+
+
+COUNT_PIT_TAG = 0x504954      # the Philox tag of the PIT's replicated counts (csrc/count_draw.h) and the second word of count_pit's generator
+
+
+def count_pit(below, equal, n, seed=0):
+    """The randomised PIT of count observations from the counts of HipEngine.pointwise_summary(count_pit=True): per cell
+        (below + v_c equal) / n,   v_c uniform on [0, 1), one per cell from np.random.default_rng([seed, 0x504954]).random(shape),
+    with below = #{replicated counts < y}, equal = #{= y} over the n particles that count; n = 0 gives NaN.  below / n estimates
+    F(y - 1) and equal / n the mass at y, so this is the value u = F(y - 1) + v (F(y) - F(y - 1)) that is uniform on (0, 1) under a
+    calibrated model (Smith 1985; Czado, Gneiting & Held 2009) - the mid-point v = 1/2 is not, for small counts."""
+    import numpy as np
+    below, equal, n = (np.asarray(x) for x in (below, equal, n))
+    v = np.random.default_rng([int(seed), COUNT_PIT_TAG]).random(np.shape(n))
+    with np.errstate(all="ignore"):
+        u = (below.astype(np.float64) + v * equal.astype(np.float64)) / n.astype(np.float64)
+    return np.where(n > 0, u, np.nan)
+
+
+def count_pit_fill(pit, below, equal, n, family, seed=0):
+    """What count_pit=True adds to a pointwise summary, from the Gaussian cells' pit (..., n_obs) and the counts: {"pit_below",
+    "pit_equal", "pit_n", "pit_lower" = below / n, "pit_upper" = (below + equal) / n, "pit"}.  On the outputs whose family is a
+    count, pit is count_pit(...) and lower / upper the two estimates (NaN where n = 0); on every other output pit stays and
+    lower = upper = pit.  family: the list of the source (obs_family), None: no count output."""
+    import numpy as np
+    pit = np.asarray(pit, dtype=np.float64)
+    below, equal, n = (np.asarray(x, dtype=np.int64) for x in (below, equal, n))
+    is_count = np.zeros(pit.shape, dtype=bool)
+    if family is not None:
+        is_count[..., np.asarray(family) != 0] = True
+    with np.errstate(all="ignore"):
+        nf = n.astype(np.float64)
+        lower = np.where(n > 0, below / nf, np.nan)
+        upper = np.where(n > 0, (below + equal) / nf, np.nan)
+    return {"pit_below": below, "pit_equal": equal, "pit_n": n, "pit_lower": np.where(is_count, lower, pit),
+            "pit_upper": np.where(is_count, upper, pit), "pit": np.where(is_count, count_pit(below, equal, n, seed), pit)}
+
+
+def pit_histogram(lower, upper, bins=10):
+    """The non-randomised PIT histogram of Czado, Gneiting & Held (2009) for counts, and the ordinary one for continuous values:
+    per cell F_c(u) = 0 for u <= lower, (u - lower) / (upper - lower) in between, 1 for u >= upper (lower = upper: the step at that
+    value, a continuous observation's PIT); the result is the mean of F_c over the cells with finite lower and upper, differenced
+    over the `bins` equal bins of [0, 1]: heights that sum to 1, each 1 / bins under a calibrated model.  No cell: NaN."""
+    import numpy as np
+    lower, upper = np.asarray(lower, dtype=np.float64).reshape(-1), np.asarray(upper, dtype=np.float64).reshape(-1)
+    use = np.isfinite(lower) & np.isfinite(upper)
+    lo, up = lower[use][:, None], upper[use][:, None]
+    if lo.size == 0:
+        return np.full(int(bins), np.nan)
+    edges = np.linspace(0.0, 1.0, int(bins) + 1)[None, :]
+    with np.errstate(all="ignore"):
+        ramp = np.clip((edges - lo) / (up - lo), 0.0, 1.0)
+    F = np.where(up > lo, ramp, (edges >= lo).astype(np.float64))
+    F[:, 0], F[:, -1] = 0.0, 1.0      # the whole mass lies in [0, 1]: a step at 0 belongs to the first bin
+    return np.diff(F.mean(axis=0))
 
 
 def pointwise_finish(stats):
@@ -973,7 +1028,10 @@ def pointwise_merge(blocks):
     and max is the larger; sum_exp is rescaled to the common max (a block whose max is -inf under a finite one adds 0); mean and
     m2 by Chan's update, delta = mean_b - mean_a: mean = mean_a + delta n_b / n, m2 = m2_a + m2_b + delta^2 n_a n_b / n (a -inf
     mean on either side: mean -inf, m2 NaN, as the expressions of the whole give); "pit", where the blocks carry it, weighted by
-    n.  A block with n = 0 in a cell changes nothing there.  lpd and var are formed anew (pointwise_finish)."""
+    n.  A block with n = 0 in a cell changes nothing there.  lpd and var are formed anew (pointwise_finish).  Where every block
+    carries the count PIT's "pit_below", "pit_equal" and "pit_n" they add (integers: exact in any order); "pit" on count cells,
+    "pit_lower" and "pit_upper" are then formed from the sums by count_pit_fill, which the caller applies (it knows the families
+    and the seed; run_smc(pointwise={"count_pit": True}) does)."""
     import numpy as np
     blocks = list(blocks)
     if not blocks:
@@ -1004,7 +1062,12 @@ def pointwise_merge(blocks):
             for k, v in new.items():      # an empty block changes nothing
                 acc[k] = np.where(nb == 0, acc[k], np.where(na == 0, np.asarray(blk[k], dtype=np.float64), v))
             acc["n"] = acc["n"] + np.asarray(blk["n"], dtype=np.int64)
-    return pointwise_finish(acc)
+    out = pointwise_finish(acc)
+    counts = ("pit_below", "pit_equal", "pit_n")
+    if all(k in b for b in blocks for k in counts):
+        for k in counts:
+            out[k] = np.sum([np.asarray(b[k], dtype=np.int64) for b in blocks], axis=0)
+    return out
 
 
 def waic(stats):
