@@ -6,7 +6,8 @@ oracle/methanation_oracle.c plus the settings-side conversions of the reference
 
 Parity status: residual / rate law / density / likelihood / prior / inlet conversions are PINNED by
 tests/golden/methanation_golden.npz (reference functions evaluated on a synthetic inlet table, see
-tests/golden/make_methanation_golden.py).  The DAE time integration is parity-UNPINNED.
+tests/golden/make_methanation_golden.py).  The DAE time integration is held to a method-independent solution of the DAE that the pinned
+residual defines (tests/meth_dae_truth.py); agreement with IDA's own step sequence is parity-UNPINNED.
 """
 from __future__ import annotations
 
