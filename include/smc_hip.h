@@ -53,6 +53,11 @@ extern "C" {
 #define SMC_PRIOR_NORMAL 1  /* {"dist":"normal","mu","sigma"}   Micmem_settings.py:55-59 */
 #define SMC_PRIOR_FLAT 2    /* no factor in cal_prior (sigma under normal_pred without taylor,
                              * methanation_functions.py:132-138 multiplies num_est_params-1 densities) */
+/* the families of smc_set_prior_ex (documented there); smc_set_prior refuses them */
+#define SMC_PRIOR_LOGNORMAL 3   /* {"dist":"lognormal","mu","sigma"}                 of log x */
+#define SMC_PRIOR_GAMMA 4       /* {"dist":"gamma","shape","scale"} */
+#define SMC_PRIOR_BETA 5        /* {"dist":"beta","a","b","low","high"}              on (low, high) */
+#define SMC_PRIOR_TRUNCNORMAL 6 /* {"dist":"truncnormal","mu","sigma","low","high"}  "halfnormal": mu 0, low 0, high +inf */
 
 /* what the Metropolis acceptance does with the prior */
 #define SMC_PRIOR_MODE_MASK 0        /* pp = exp(px*g) * p0            Micmem_SMC_main.py:224-233, SMC_methanation_main.py:376-389 */
@@ -351,7 +356,8 @@ typedef struct smc_user_model_spec {
      *   mu = 0 with y = 0 gives x = 0; any b_k < 0, or b_k <= 0 on a negative-binomial output: logL = -inf.  m_e, m_ek count Gaussian
      *   quantified values only:   lk = sum_e [ (-m_e / 2) log(2 pi) - sum_k m_ek log(a_k s_k) - C_e - X_e ].
      * The Poisson form needs no lgamma on the device and does not cancel at large counts.  Below b around 1e-4 the lgamma difference
-     * of the negative binomial loses digits: declare the output Poisson, or keep the prior off 0.  Early rejection stays exact (the
+     * of the negative binomial loses digits: declare the output Poisson, or keep the prior off 0 (a gamma or
+     * log-normal prior does: PRIOR FAMILIES at smc_set_prior_ex).  Early rejection stays exact (the
      * floors do not depend on the solve); the LDS table does not grow.  smc_user_predict returns lk under this
      * likelihood, designs give the mean; smc_user_predict_summary with noise = 1 is refused (it draws Gaussian noise only), noise = 2
      * draws replicated counts, and smc_user_pointwise_summary_opt ranks the observed counts among them (the PIT).
@@ -585,8 +591,41 @@ int smc_meth_sweep_check(smc_ctx *ctx, int64_t out[5]);
 int smc_meth_download_solves(smc_ctx *ctx, double *flows, int32_t *status, int64_t n);
 /* Independent priors, one per parameter: kind[i] in {SMC_PRIOR_UNIFORM, SMC_PRIOR_NORMAL, SMC_PRIOR_FLAT}; (a,b) =
  * (low,high) or (mu,sigma).  Used by the support mask of cal_prior (Micmem_SMC_main.py:60-90,
- * 224-228) and by smc_sample_prior_device. */
+ * 224-228) and by smc_sample_prior_device.  Any other kind is refused with the parameter's index ("Unknown prior kind: parameter i:
+ * kind k ..."); for a family of smc_set_prior_ex the message names that entry point. */
 int smc_set_prior(smc_ctx *ctx, const int *kind, const double *a, const double *b, int dim);
+/* PRIOR FAMILIES on a positive or bounded parameter (priors.py is the definition in NumPy).  kind[i] may also be
+ *   SMC_PRIOR_LOGNORMAL    (a, b) = (mu, sigma) of log x, sigma > 0      support x > 0            k = -L - (L - mu)^2 / (2 sigma^2), L = log x
+ *   SMC_PRIOR_GAMMA        (a, b) = (shape, scale), both > 0             support x > 0            k = (shape - 1) log x - x / scale
+ *   SMC_PRIOR_BETA         (a, b) > 0, lo < hi finite                    support lo < x < hi      k = (a - 1) log u + (b - 1) log1p(-u),
+ *                                                                                                 u = (x - lo) / (hi - lo)
+ *   SMC_PRIOR_TRUNCNORMAL  (a, b) = (mu, sigma), sigma > 0, lo < hi,     support lo <= x <= hi    k = -y^2 / 2, y = (x - mu) / sigma
+ *                          either bound may be infinite
+ * k is the LOG-KERNEL: the log-density without its normaliser, which cancels in the Metropolis ratio (the device needs no lgamma
+ * and no erf).  lo / hi are read for SMC_PRIOR_BETA and SMC_PRIOR_TRUNCNORMAL only and may be NULL when neither kind is present;
+ * for the kinds of smc_set_prior, (a, b) mean what they mean there.  Outside its support a family's density is exactly 0 (k =
+ * -inf), never NaN - at x = +inf too; a NaN argument gives NaN and counts as outside.  A beta's test is made on u as rounded as well
+ * (0 < u < 1): an x within an ulp of an end is outside.
+ * In the propose kernels of all three model families, with P the product of the densities of the smc_set_prior kinds (as before)
+ * and K the sum of k over the parameters of the new kinds: a proposal is in support iff P(cand) > 0 and every new-kind parameter of
+ * it is in its support - otherwise it is reset to the current point and rejected (SMC_PRIOR_MODE_RATIO keeps its one exception: a
+ * candidate outside the support of a smc_set_prior kind alone is not reset there, as before; one outside a new kind's is, so that
+ * no model is solved at a negative level or fraction).  In the ratio modes p0_2 / p0_1 = P(cand) / P(cur) * exp(K(cand) - K(cur))
+ * for a candidate in support and 0 otherwise.  SMC_PRIOR_MODE_MASK applies the support alone, as it does for a normal: A DENSITY
+ * ONLY ACTS UNDER SMC_PRIOR_MODE_RATIO_MASK / SMC_PRIOR_MODE_RATIO.  With no new kind the kernels take the path, and give the
+ * bits, they had before.
+ * smc_sample_prior_device draws a new kind from the uniform supply of csrc/count_draw.h keyed by (seed, global particle, tag
+ * 0x505249, cell = parameter index) - csrc/prior_draw.h: exp(mu + sigma z); scale * Gamma(shape) by Marsaglia-Tsang; G1 / (G1 + G2)
+ * of two such gammas on one supply, mapped to (lo, hi); mu + sigma z repeated until it lies in [lo, hi] - while the parameters
+ * of the smc_set_prior kinds keep their stream and their bits whatever stands beside them.
+ * Rules: a, b as listed (finite); a gamma's shape and a beta's a, b at least 1/16 (the draw's boost u^(1 / shape) underflows to 0 with
+ * probability exp(-745 shape): below the bound a gamma draw could be exactly 0, outside its support, and a beta draw 0 / 0); lo < hi, finite for a beta, not NaN for a truncated normal; a truncated normal keeps at least half
+ * of its mass, Phi((hi - mu) / sigma) - Phi((lo - mu) / sigma) >= 1/2 (formed with erfc) - the draw is by rejection and under this
+ * rule a dry supply (NaN) has probability at most 2^-254; for less mass use a uniform or a shifted normal.  A broken rule fails with
+ * the parameter's index and the rule.  smc_prior_check applies the rules alone (no GPU, no context: the reason is in
+ * smc_last_error(NULL)). */
+int smc_set_prior_ex(smc_ctx *ctx, const int *kind, const double *a, const double *b, const double *lo, const double *hi, int dim);
+int smc_prior_check(const int *kind, const double *a, const double *b, const double *lo, const double *hi, int dim);
 /* SMC_PRIOR_MODE_*: default SMC_PRIOR_MODE_MASK (the live branch of both reference drivers). */
 int smc_set_prior_mode(smc_ctx *ctx, int mode);
 

@@ -6,6 +6,7 @@ loaded by path: `__graft_entry__.load_package()` registers it as the module `smc
   binding   ctypes declarations of include/smc_hip.h
   engine    HipEngine: one libsmc_hip.so context (device-resident particle sets + stages)
   comm      SingleComm / RcclComm
+  priors    prior families: the dict as smc_set_prior_ex's arrays, log-kernel / support / log-density in NumPy
   driver    SMCSettings, run_smc: the tempering loop of the reference's driver scripts
   dropin/   shadow modules with the reference's names (Micmem_settings, Micmem_likelihood)
 """
@@ -16,3 +17,5 @@ from .engine import HipEngine, release_pinned_pool  # noqa: F401
 from . import methanation  # noqa: F401
 from . import datagen  # noqa: F401
 from . import user_models  # noqa: F401
+from . import priors  # noqa: F401
+from .priors import prior_layout, prior_log_kernel, prior_logpdf, prior_support  # noqa: F401

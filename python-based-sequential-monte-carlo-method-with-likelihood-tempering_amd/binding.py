@@ -22,6 +22,7 @@ SMC_USER_MAX_EVENTS, SMC_USER_MAX_EVENT_VALUES = 256, 8
 SMC_USER_MAX_ROOTS, SMC_USER_MAX_ROOT_FIRES = 4, 256      # state-triggered events (smc_user_root)
 USER_METHODS = {"RK45": SMC_USER_METHOD_RK45, "BDF": SMC_USER_METHOD_BDF}
 SMC_PRIOR_UNIFORM, SMC_PRIOR_NORMAL, SMC_PRIOR_FLAT = 0, 1, 2
+SMC_PRIOR_LOGNORMAL, SMC_PRIOR_GAMMA, SMC_PRIOR_BETA, SMC_PRIOR_TRUNCNORMAL = 3, 4, 5, 6      # smc_set_prior_ex (priors.py)
 SMC_PRIOR_MODE_MASK, SMC_PRIOR_MODE_RATIO_MASK, SMC_PRIOR_MODE_RATIO = 0, 1, 2
 PRIOR_MODES = {"mask": 0, "ratio_mask": 1, "ratio": 2}
 RESAMPLING = {"residual_systematic": 0, "systematic": 1, "multinomial": 2}
@@ -146,6 +147,8 @@ SIGNATURES = {
     "smc_meth_sweep_check": (cint, [c_ctx, c_i64p]),
     "smc_meth_download_solves": (cint, [c_ctx, c_dp, ctypes.POINTER(ctypes.c_int32), i64]),
     "smc_set_prior": (cint, [c_ctx, c_ip, c_dp, c_dp, cint]),
+    "smc_set_prior_ex": (cint, [c_ctx, c_ip, c_dp, c_dp, c_dp, c_dp, cint]),
+    "smc_prior_check": (cint, [c_ip, c_dp, c_dp, c_dp, c_dp, cint]),
     "smc_set_prior_mode": (cint, [c_ctx, cint]),
     "smc_set_resampling": (cint, [c_ctx, cint]),
     "smc_set_early_reject": (cint, [c_ctx, cint]),

@@ -412,18 +412,32 @@ generic_propose_kernel(Prior prior, MHParams mh, const double *__restrict__ filt
     for (int c = 0; c < d; ++c) {
         cur[c] = filt[c * stride + p];
         cand[c] = __dadd_rn(cur[c], __dmul_rn(z[c], ratio));
-        const double q = prior_pdf(prior.kind[c], prior.a[c], prior.b[c], cand[c]);
+        const double q = prior_pdf_old(prior, c, cand[c]);
         pdf = (c == 0) ? q : pdf * q;
+    }
+    // the families of smc_set_prior_ex: K = the sum of their log-kernels, -inf (or NaN) outside a support.  prior.n_new is a
+    // kernel argument: with none of them nothing below is reached, and P above is what it always was
+    double kc = 0.0;
+    bool in_new = true;
+    if (prior.n_new) {
+        for (int c = 0; c < d; ++c) kc += prior_k_new(prior, c, cand[c]);
+        in_new = kc > -__longlong_as_double(0x7ff0000000000000LL);
     }
     if (mh.prior_mode != SMC_PRIOR_MODE_MASK) {   // p0_2 / p0_1 (SMC_methanation_main.py:323-324, 343)
         double cur_pdf = 1.0;
         for (int c = 0; c < d; ++c) {
-            const double q = prior_pdf(prior.kind[c], prior.a[c], prior.b[c], cur[c]);
+            const double q = prior_pdf_old(prior, c, cur[c]);
             cur_pdf = (c == 0) ? q : cur_pdf * q;
         }
-        mh.pratio[p] = pdf / cur_pdf;
+        double pratio = pdf / cur_pdf;
+        if (prior.n_new) {
+            double kf = 0.0;
+            for (int c = 0; c < d; ++c) kf += prior_k_new(prior, c, cur[c]);
+            pratio = prior_ratio_new(pdf, cur_pdf, kc, kf, pdf > 0.0 && in_new);
+        }
+        mh.pratio[p] = pratio;
     }
-    const double p0 = (pdf > 0.0 || mh.prior_mode == SMC_PRIOR_MODE_RATIO) ? 1.0 : 0.0, q0 = 1.0 - p0;
+    const double p0 = ((pdf > 0.0 || mh.prior_mode == SMC_PRIOR_MODE_RATIO) && in_new) ? 1.0 : 0.0, q0 = 1.0 - p0;
     for (int c = 0; c < d; ++c) prop[c * pstride + p] = __dadd_rn(__dmul_rn(cand[c], p0), __dmul_rn(cur[c], q0));
     p0_out[p] = (uint8_t)(p0 != 0.0);
 }
@@ -458,7 +472,12 @@ generic_accept_kernel(MHParams mh, const double *__restrict__ prop, int64_t pstr
             const double th = prop[c * pstride + p], f = filt[c * fstride + p];
             filt[c * fstride + p] = __dadd_rn(__dmul_rn(th, r), __dmul_rn(f, nr));
         }
-        lk_io[p] = __dadd_rn(__dmul_rn(lk2, r), __dmul_rn(lk1, nr));
+        // the reference's select, lk2 r + lk1 (1 - r) - whose result is NaN where the side that is NOT taken is not finite (0 x inf):
+        // a rejected proposal whose solve failed (NaN) or whose likelihood is -inf (a count of a zero mean) would poison lk1 and, through
+        // max(lk), the whole run.  A bounded prior keeps such proposals rare; a prior on (0, inf) does not.  There, and only there,
+        // the side that is taken is stored; everywhere else the bits are the product form's
+        const double sel = __dadd_rn(__dmul_rn(lk2, r), __dmul_rn(lk1, nr));
+        lk_io[p] = (sel != sel) ? (r != 0.0 ? lk2 : lk1) : sel;
         const uint8_t ever = (uint8_t)(r_ac[p] | (uint8_t)(r != 0.0));
         r_ac[p] = ever;
         acc_now += (r != 0.0);

@@ -303,18 +303,30 @@ __device__ __forceinline__ void mm_propose_one(const Prior &prior, const MHParam
     const double c0 = __dadd_rn(f0, __dmul_rn(z0, mh_ratio)), c1 = __dadd_rn(f1, __dmul_rn(z1, mh_ratio)),
                  c2 = __dadd_rn(f2, __dmul_rn(z2, mh_ratio));
     // support mask (cal_prior > 0, :225-226) and reset of out-of-support proposals (:228)
-    double pdf = prior_pdf(prior.kind[0], prior.a[0], prior.b[0], c0);
-    pdf = pdf * prior_pdf(prior.kind[1], prior.a[1], prior.b[1], c1);
-    pdf = pdf * prior_pdf(prior.kind[2], prior.a[2], prior.b[2], c2);
+    double pdf = prior_pdf_old(prior, 0, c0);
+    pdf = pdf * prior_pdf_old(prior, 1, c1);
+    pdf = pdf * prior_pdf_old(prior, 2, c2);
+    // the families of smc_set_prior_ex: K = the sum of their log-kernels, -inf (or NaN) outside a support.  prior.n_new is a
+    // kernel argument: with none of them nothing below is reached, and P above is what it always was
+    double kc = 0.0;
+    bool in_new = true;
+    if (prior.n_new) {
+        kc = prior_k_new(prior, 0, c0) + prior_k_new(prior, 1, c1) + prior_k_new(prior, 2, c2);
+        in_new = kc > -__longlong_as_double(0x7ff0000000000000LL);
+    }
     double pratio = 1.0;
     if (mh.prior_mode != SMC_PRIOR_MODE_MASK) {   // p0_2 / p0_1 (SMC_methanation_main.py:323-324, 343)
-        double cur = prior_pdf(prior.kind[0], prior.a[0], prior.b[0], f0);
-        cur = cur * prior_pdf(prior.kind[1], prior.a[1], prior.b[1], f1);
-        cur = cur * prior_pdf(prior.kind[2], prior.a[2], prior.b[2], f2);
+        double cur = prior_pdf_old(prior, 0, f0);
+        cur = cur * prior_pdf_old(prior, 1, f1);
+        cur = cur * prior_pdf_old(prior, 2, f2);
         pratio = pdf / cur;
+        if (prior.n_new) {
+            const double kf = prior_k_new(prior, 0, f0) + prior_k_new(prior, 1, f1) + prior_k_new(prior, 2, f2);
+            pratio = prior_ratio_new(pdf, cur, kc, kf, pdf > 0.0 && in_new);
+        }
         mh.pratio[p] = pratio;
     }
-    const double p0 = (pdf > 0.0 || mh.prior_mode == SMC_PRIOR_MODE_RATIO) ? 1.0 : 0.0, q0 = 1.0 - p0;
+    const double p0 = ((pdf > 0.0 || mh.prior_mode == SMC_PRIOR_MODE_RATIO) && in_new) ? 1.0 : 0.0, q0 = 1.0 - p0;
     const double w0 = __dadd_rn(__dmul_rn(c0, p0), __dmul_rn(f0, q0)), w1 = __dadd_rn(__dmul_rn(c1, p0), __dmul_rn(f1, q0));
     prop[p] = w0;
     prop[pstride + p] = w1;

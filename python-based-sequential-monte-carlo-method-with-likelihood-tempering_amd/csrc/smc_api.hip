@@ -464,13 +464,104 @@ int smc_set_prior(smc_ctx *c, const int *kind, const double *a, const double *b,
     if (!c) return fail(nullptr, "NULL context");
     if (dim != c->dim) return fail(c, "smc_set_prior: dim mismatch");
     for (int i = 0; i < dim; ++i) {
-        if (kind[i] != SMC_PRIOR_UNIFORM && kind[i] != SMC_PRIOR_NORMAL && kind[i] != SMC_PRIOR_FLAT)
-            return fail(c, "Unknown prior kind");
+        if (kind[i] != SMC_PRIOR_UNIFORM && kind[i] != SMC_PRIOR_NORMAL && kind[i] != SMC_PRIOR_FLAT) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "Unknown prior kind: parameter %d: kind %d is not uniform, normal or flat%s", i, kind[i],
+                     kind[i] >= SMC_PRIOR_LOGNORMAL && kind[i] <= SMC_PRIOR_TRUNCNORMAL ? " (smc_set_prior_ex takes this family)" : "");
+            return fail(c, buf);
+        }
         c->prior.kind[i] = kind[i];
         c->prior.a[i] = a[i];
         c->prior.b[i] = b[i];
+        c->prior.lo[i] = 0.0;
+        c->prior.hi[i] = 0.0;
     }
     c->prior.d = dim;
+    c->prior.n_new = 0;
+    c->have_prior = true;
+    return 0;
+}
+
+// The rules of smc_set_prior_ex (include/smc_hip.h: PRIOR FAMILIES; priors.prior_layout hands them on): "" or the reason, with the
+// parameter's index.  The kinds of smc_set_prior are only recognised - their (a, b) stay unchecked, as there.
+static std::string prior_spec_error(const int *kind, const double *a, const double *b, const double *lo, const double *hi, int dim) {
+    char buf[256];
+    if (dim < 1 || dim > SMC_MAX_DIM) {
+        snprintf(buf, sizeof buf, "dim %d is not in 1 .. %d", dim, SMC_MAX_DIM);
+        return buf;
+    }
+    if (!kind || !a || !b) return "kind, a and b must not be NULL";
+    auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+    // Marsaglia-Tsang's boost u^(1 / shape) underflows to 0 with probability exp(-745 shape): 6e-21 at 1/16, 6e-4 at 0.01 - a gamma
+    // draw is then exactly 0, outside its own support, a beta draw 0 / 0.  Below 1/16 a shape is refused
+    const double kMinShape = 0.0625;
+    for (int i = 0; i < dim; ++i) {
+        const int k = kind[i];
+        if (k == SMC_PRIOR_UNIFORM || k == SMC_PRIOR_NORMAL || k == SMC_PRIOR_FLAT) continue;
+        const char *rule = nullptr;
+        if (k == SMC_PRIOR_LOGNORMAL) {
+            if (!std::isfinite(a[i])) rule = "lognormal: mu must be finite";
+            else if (!positive(b[i])) rule = "lognormal: sigma must be finite and > 0";
+        } else if (k == SMC_PRIOR_GAMMA) {
+            if (!positive(a[i])) rule = "gamma: shape must be finite and > 0";
+            else if (!positive(b[i])) rule = "gamma: scale must be finite and > 0";
+            else if (a[i] < kMinShape) rule = "gamma: shape must be >= 1/16 (below it the draw's boost u^(1 / shape) underflows to 0)";
+        } else if (k == SMC_PRIOR_BETA) {
+            if (!positive(a[i])) rule = "beta: a must be finite and > 0";
+            else if (!positive(b[i])) rule = "beta: b must be finite and > 0";
+            else if (a[i] < kMinShape || b[i] < kMinShape) rule = "beta: a and b must be >= 1/16 (below it the draw's boost u^(1 / a) underflows to 0)";
+            else if (!lo || !hi) rule = "beta: lo and hi must not be NULL";
+            else if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) rule = "beta: low and high must be finite";
+            else if (!(lo[i] < hi[i])) rule = "beta: low must be < high";
+        } else if (k == SMC_PRIOR_TRUNCNORMAL) {
+            if (!std::isfinite(a[i])) rule = "truncnormal: mu must be finite";
+            else if (!positive(b[i])) rule = "truncnormal: sigma must be finite and > 0";
+            else if (!lo || !hi) rule = "truncnormal: lo and hi must not be NULL";
+            else if (!(lo[i] < hi[i])) rule = "truncnormal: low must be < high (neither NaN)";
+            else {
+                // Phi(zh) - Phi(zl) with erfc on the side where it is accurate: both in the upper tail -> Q(zl) - Q(zh)
+                const double zl = (lo[i] - a[i]) / b[i], zh = (hi[i] - a[i]) / b[i], r = 0.70710678118654752440;
+                const double mass = zl > 0.0 ? 0.5 * std::erfc(zl * r) - 0.5 * std::erfc(zh * r) : 0.5 * std::erfc(-zh * r) - 0.5 * std::erfc(-zl * r);
+                if (!(mass >= 0.5)) {
+                    snprintf(buf, sizeof buf, "parameter %d: truncnormal: the kept mass Phi((high - mu) / sigma) - Phi((low - mu) / sigma) = %.6g "
+                             "is below 1/2 (the draw is by rejection); use a uniform or a shifted normal instead", i, mass);
+                    return buf;
+                }
+            }
+        } else {
+            snprintf(buf, sizeof buf, "parameter %d: unknown prior kind %d", i, k);
+            return buf;
+        }
+        if (rule) {
+            snprintf(buf, sizeof buf, "parameter %d: %s", i, rule);
+            return buf;
+        }
+    }
+    return "";
+}
+
+int smc_prior_check(const int *kind, const double *a, const double *b, const double *lo, const double *hi, int dim) {
+    const std::string bad = prior_spec_error(kind, a, b, lo, hi, dim);
+    return bad.empty() ? 0 : fail(nullptr, ("smc_prior_check: " + bad).c_str());
+}
+
+int smc_set_prior_ex(smc_ctx *c, const int *kind, const double *a, const double *b, const double *lo, const double *hi, int dim) {
+    if (!c) return fail(nullptr, "NULL context");
+    if (dim != c->dim) return fail(c, "smc_set_prior_ex: dim mismatch");
+    const std::string bad = prior_spec_error(kind, a, b, lo, hi, dim);
+    if (!bad.empty()) return fail(c, ("smc_set_prior_ex: " + bad).c_str());
+    int n_new = 0;
+    for (int i = 0; i < dim; ++i) {
+        const bool bounded = kind[i] == SMC_PRIOR_BETA || kind[i] == SMC_PRIOR_TRUNCNORMAL;
+        c->prior.kind[i] = kind[i];
+        c->prior.a[i] = a[i];
+        c->prior.b[i] = b[i];
+        c->prior.lo[i] = bounded ? lo[i] : 0.0;
+        c->prior.hi[i] = bounded ? hi[i] : 0.0;
+        n_new += kind[i] >= SMC_PRIOR_LOGNORMAL;
+    }
+    c->prior.d = dim;
+    c->prior.n_new = n_new;
     c->have_prior = true;
     return 0;
 }

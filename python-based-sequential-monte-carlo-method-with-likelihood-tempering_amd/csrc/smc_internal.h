@@ -44,6 +44,8 @@ struct Prior {       // passed by value
     int kind[SMC_MAX_DIM];
     double a[SMC_MAX_DIM], b[SMC_MAX_DIM];
     int d;
+    int n_new;           // parameters of a kind >= SMC_PRIOR_LOGNORMAL (smc_set_prior_ex); 0: the kernels take the path they always took
+    double lo[SMC_MAX_DIM], hi[SMC_MAX_DIM];      // bounds of a beta / truncated normal
 };
 
 struct ParticleSet {  // SoA view: theta[c][i] = theta_base[c*stride + i]

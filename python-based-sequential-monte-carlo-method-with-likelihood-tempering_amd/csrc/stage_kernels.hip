@@ -10,6 +10,7 @@
 
 #include "mh_control.h"
 #include "philox.h"
+#include "prior_draw.h"
 #include "smc_internal.h"
 #include "stage_kernels.h"
 
@@ -92,6 +93,10 @@ __global__ void sample_prior_kernel(Prior prior, double *__restrict__ theta, int
     if (p >= n) return;
     const uint64_t g = (uint64_t)(goff + p);
     for (int c = 0; c < prior.d; ++c) {
+        if (prior.n_new && prior.kind[c] >= SMC_PRIOR_LOGNORMAL) {   // a family of smc_set_prior_ex: its own stream (prior_draw.h)
+            theta[c * stride + p] = smc_draw::prior_draw(prior.kind[c], prior.a[c], prior.b[c], prior.lo[c], prior.hi[c], seed, g, (uint64_t)c);
+            continue;
+        }
         const u32x4 r = philox_block(seed, g, 0xFFFFFFFF00000000ull | (uint64_t)c, 0);
         double v;
         if (prior.kind[c] == SMC_PRIOR_UNIFORM) {

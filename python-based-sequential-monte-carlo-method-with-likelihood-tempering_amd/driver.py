@@ -32,6 +32,7 @@ import numpy as np
 
 from .binding import SMC_MAX_ESS_CAND, SMC_SET_FILT, SMC_SET_PRED
 from .comm import SingleComm
+from .priors import sample_new_kind
 
 
 @dataclass
@@ -55,7 +56,9 @@ class SMCSettings:
     seed: int = 20250205
     rtol: float = 1e-3
     atol: float = 1e-6
-    prior_mode: str = "mask"          # "mask" | "ratio_mask" | "ratio"  (HipEngine.set_prior_mode)
+    prior_mode: str = "mask"          # "mask" | "ratio_mask" | "ratio"  (HipEngine.set_prior_mode).  A prior's DENSITY only acts under
+                                      # "ratio_mask" / "ratio": "mask" applies its support alone - for a normal as for the families of
+                                      # priors.py (lognormal, gamma, beta, truncnormal, halfnormal), which `priors` below also takes
     resampling: str = "residual_systematic"   # | "systematic"  (HipEngine.set_resampling; the reference has only the first)
     ess_search: str = "backoff"       # the reference's geometric back-off (main:111-144) | "bisection"
     ess_bisect_tol: float = 1e-9      # bisection: bracket width in gamma at which the search stops
@@ -102,6 +105,8 @@ def sample_prior(priors: dict, n_particle: int) -> np.ndarray:
             p_pred[:, j] = np.random.normal(loc=p["mu"], scale=p["sigma"], size=n_particle)
         elif p["dist"] == "uniform":
             p_pred[:, j] = np.random.uniform(low=p["low"], high=p["high"], size=n_particle)
+        elif p["dist"] in ("lognormal", "gamma", "beta", "truncnormal", "halfnormal"):      # priors.py
+            p_pred[:, j] = sample_new_kind(p, n_particle)
         else:
             raise ValueError(f"Unknown distribution: {p['dist']}")
     return p_pred

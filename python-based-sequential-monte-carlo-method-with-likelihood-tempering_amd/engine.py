@@ -348,7 +348,14 @@ class HipEngine:
         self.model = ("methanation", n_data, 357)
 
     def set_prior(self, priors: dict):
-        """priors: the reference's dict (Micmem_settings.py:55-67), one entry per parameter, in order."""
+        """priors: the reference's dict (Micmem_settings.py:55-67), one entry per parameter, in order.  A dict with a lognormal,
+        gamma, beta, truncnormal or halfnormal entry (priors.py) goes through smc_set_prior_ex, every other through smc_set_prior
+        as before."""
+        from . import priors as P
+        if P.has_new_kind(priors):
+            k, a, b, lo, hi = P.prior_layout(priors)
+            self._ck(self.L.smc_set_prior_ex(self.ctx, k.ctypes.data_as(B.c_ip), _dp(a), _dp(b), _dp(lo), _dp(hi), len(k)), "smc_set_prior_ex")
+            return
         kinds, a, b = [], [], []
         for name, p in priors.items():
             if p["dist"] == "uniform":
