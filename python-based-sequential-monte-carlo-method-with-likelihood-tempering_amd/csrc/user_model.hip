@@ -213,6 +213,21 @@ struct UserSourceSpec {
     UserInputGeom geom{};
 };
 
+// What a launch (launch_user_kernel) runs on, and what differs between the data and a group of a design other than the data's:
+// the experiments, the blocks per CU of the kernel that runs them, and what the kernel writes per (experiment, particle).
+// A plain set of pointers and sizes: whoever filled it owns the allocations (UserModel; DesignGroup and DesignItems).
+struct UserLaunchData {
+    double *d_img = nullptr;              // the LDS image (nullptr: one-output data the image cannot hold, img_error says why)
+    int img_len = 0;
+    double *d_cond = nullptr;
+    double *d_const = nullptr;            // [2 n_ex]: m_e, then sum log s_k (user_finish_kernel); n_t and 0 for a one-output model
+    int n_ex = 0, n_t = 0;
+    int blocks_per_cu = 4;   // persistent blocks (4 waves each) per CU: what the compiled kernel's registers and LDS allow
+    double *d_sum = nullptr;
+    int *d_info = nullptr;
+    unsigned *d_bdf_counts = nullptr;          // BDF: per item {accepted steps, Newton iterations, LU factorisations, Jacobians}
+};
+
 struct UserModel {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
@@ -221,25 +236,26 @@ struct UserModel {
     uint8_t *d_listed = nullptr;
     unsigned *d_count = nullptr;
     int parity = 0;
-    double *d_t = nullptr, *d_obs = nullptr, *d_cond = nullptr, *d_sum = nullptr;
-    int *d_info = nullptr;
-    int n_ex = 0, n_t = 0, n_cond = 0, est_sigma = 1;
-    int blocks_per_cu = 4;   // persistent blocks (4 waves each) per CU: what the compiled kernel's registers and LDS allow
+    UserLaunchData data;                  // the data, for the sweep kernel (fn); set once by set_model_user_impl
+    double *d_t = nullptr, *d_obs = nullptr;      // the data as the one-output sweep kernel reads it; no other kernel does
+    int n_cond = 0, est_sigma = 1;
     double sigma_fixed = 0, rtol = 1e-3, atol = 1e-6;
-    unsigned *d_bdf_counts = nullptr;          // BDF: per item {accepted steps, Newton iterations, LU factorisations, Jacobians}
-    unsigned long long *d_bdf_totals = nullptr;   // ... their sums over the last sweep (user_bdf_count_kernel)
-    double *d_const = nullptr;            // [2 n_ex]: m_e, then sum log s_k (user_finish_kernel); n_t and 0 for a one-output model
+    unsigned long long *d_bdf_totals = nullptr;   // BDF: the sums of d_bdf_counts over the last sweep (user_bdf_count_kernel)
     // smc_set_model_user3 (user_obs_args.h): `multi` models run the multi-output source, whose module also holds the
     // prediction kernel; a model of smc_set_model_user / 2 compiles that source with n_obs = 1 when it first predicts
     bool multi = false;
     int n_obs = 1;
     std::string source;
-    double *d_img = nullptr;              // the LDS image (nullptr: one-output data the image cannot hold, img_error says why)
-    int img_len = 0;
     std::string img_error;
     hipModule_t module_pred = nullptr;
     hipFunction_t fn_pred = nullptr;
     int blocks_per_cu_pred = 4;
+    // the data for the prediction kernel (fn_pred): the same allocations, that kernel's blocks per CU
+    UserLaunchData pred_data() const {
+        UserLaunchData d = data;
+        d.blocks_per_cu = blocks_per_cu_pred;
+        return d;
+    }
     double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;   // smc_user_predict's staging: parameters (AoS + SoA), lk, pred
     int64_t p_cap = 0;
     // smc_user_pointwise / smc_user_pointwise_summary (pointwise_kernels.h): per cell of the data's design its value, what it is and
@@ -520,16 +536,16 @@ void user_model_release(smc_ctx *c) {
     if (!u) return;
     (void)hipFree(u->d_t);
     (void)hipFree(u->d_obs);
-    (void)hipFree(u->d_cond);
-    (void)hipFree(u->d_sum);
-    (void)hipFree(u->d_info);
+    (void)hipFree(u->data.d_cond);
+    (void)hipFree(u->data.d_sum);
+    (void)hipFree(u->data.d_info);
     (void)hipFree(u->d_list);
     (void)hipFree(u->d_listed);
     (void)hipFree(u->d_count);
-    (void)hipFree(u->d_bdf_counts);
+    (void)hipFree(u->data.d_bdf_counts);
     (void)hipFree(u->d_bdf_totals);
-    (void)hipFree(u->d_const);
-    (void)hipFree(u->d_img);
+    (void)hipFree(u->data.d_const);
+    (void)hipFree(u->data.d_img);
     (void)hipFree(u->d_pt);
     (void)hipFree(u->d_plk);
     (void)hipFree(u->d_ppred);
@@ -556,9 +572,10 @@ static size_t user_lds_bytes3(int n_states, int n_ex, int n_t, int n_obs, bool n
 }
 static const size_t kUserLdsCap = 150 * 1024;
 
-// pred != nullptr: the prediction kernel (smc_user_predict) - it writes there, and the BDF totals then add up over its chunks
-static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, int64_t n, uint8_t *p0mask, double *lk,
-                               bool reject, double *pred = nullptr) {
+// d: what it runs on - the model's data, or a group of a design.  pred != nullptr: the prediction kernel (smc_user_predict) - it
+// writes there, and the BDF totals then add up over its chunks.  Of the model it changes `parity` alone.
+static void launch_user_kernel(smc_ctx *c, const UserLaunchData &d, const double *theta, int64_t stride, int64_t n, uint8_t *p0mask,
+                               double *lk, bool reject, double *pred = nullptr) {
     UserModel *u = (UserModel *)c->user;
     UserSolveArgs a{};
     a.theta = theta;
@@ -567,29 +584,29 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     a.p0 = p0mask;
     a.t = u->d_t;
     a.obs = u->d_obs;
-    a.cond = u->d_cond;
-    a.n_ex = u->n_ex;
-    a.n_t = u->n_t;
+    a.cond = d.d_cond;
+    a.n_ex = d.n_ex;
+    a.n_t = d.n_t;
     a.n_cond = u->cond_stride();      // the kernels know it as the stride of a cond row only
     a.dim = c->dim;
     a.est_sigma = u->est_sigma;
     a.sigma_fixed = u->sigma_fixed;
     a.rtol = u->rtol;
     a.atol = u->atol;
-    a.sum_r2 = u->d_sum;
-    a.info = u->d_info;
+    a.sum_r2 = d.d_sum;
+    a.info = d.d_info;
     a.queue = c->d_queue;
     a.rej = reject ? c->d_reject : nullptr;
     // persistent grid: the waves take chunks of kChunk items until the queue is empty (solve_sched.h); with a cost hint a
     // small sweep gets a wave per item so that solo solves do not queue behind each other (as mm_kernels.hip: solve_grid_blocks)
     const bool lists = u->fn_scan && c->stiff_first != 0;
-    const int64_t chunks = (((n + 63) / 64) * 64 * u->n_ex + kChunk - 1) / kChunk;
-    const int64_t need = (chunks + 3) / 4 + (lists ? (n * u->n_ex + 3) / 4 : 0);
-    int64_t blocks = (int64_t)c->cu_count * (pred ? u->blocks_per_cu_pred : u->blocks_per_cu);
+    const int64_t chunks = (((n + 63) / 64) * 64 * d.n_ex + kChunk - 1) / kChunk;
+    const int64_t need = (chunks + 3) / 4 + (lists ? (n * d.n_ex + 3) / 4 : 0);
+    int64_t blocks = (int64_t)c->cu_count * d.blocks_per_cu;
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const bool multi = u->multi || pred;
-    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->spec.censor != 0) : user_lds_bytes(u->spec.n_states, u->n_ex, u->n_t));
+    const unsigned lds = (unsigned)(multi ? user_lds_bytes3(u->spec.n_states, d.n_ex, d.n_t, u->n_obs, u->noise, u->spec.censor != 0) : user_lds_bytes(u->spec.n_states, d.n_ex, d.n_t));
     if (lists) {
         u->parity ^= 1;
         UserScanArgs sa{};
@@ -602,15 +619,15 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
         sa.count = u->d_count + 2 * u->parity;
         sa.count_next = u->d_count + 2 * (u->parity ^ 1);
         sa.stiff_cap = c->n_local;
-        sa.solo_cap = (unsigned)(blocks * 4 / u->n_ex);      // one solo solve per wave of the grid
+        sa.solo_cap = (unsigned)(blocks * 4 / d.n_ex);      // one solo solve per wave of the grid
         // a heterogeneous Metropolis sweep large enough to have something to sort: cost order + in-phase waves, as for the
         // built-in model (mm_kernels.hip); the classes come from the model's hint
         const bool cost_order = p0mask != nullptr && c->cost_order != 0 && c->in_phase != 0 && n >= 16384 && c->d_bucket;
         if (cost_order) {
             sa.bucket = c->d_bucket;
-            sa.done_sums = u->d_sum;
-            sa.done_info = u->d_info;
-            sa.n_ex = u->n_ex;
+            sa.done_sums = d.d_sum;
+            sa.done_info = d.d_info;
+            sa.n_ex = d.n_ex;
         }
         void *sargs[] = {&sa};
         const hipError_t e = hipModuleLaunchKernel(u->fn_scan, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, c->stream, sargs, nullptr);
@@ -632,10 +649,10 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
             }
         }
     }
-    UserObsArgs o{u->d_img, u->img_len, pred};
-    void *args1[] = {&a, &u->d_bdf_counts};     // the RK45 kernel takes the first only
+    UserObsArgs o{d.d_img, d.img_len, pred};
+    void *args1[] = {&a, (void *)&d.d_bdf_counts};     // the RK45 kernel takes the first only
     void *args3[] = {&a, &o};                   // multi-output kernels: RK45 ...
-    void *args3b[] = {&a, &u->d_bdf_counts, &o};   // ... and BDF
+    void *args3b[] = {&a, (void *)&d.d_bdf_counts, &o};   // ... and BDF
     void **args = !multi ? args1 : (u->spec.method == SMC_USER_METHOD_BDF ? args3b : args3);
     {
         ScopedTimer tm(c, SMC_T_SOLVE);
@@ -650,22 +667,22 @@ static void launch_user_kernel(smc_ctx *c, const double *theta, int64_t stride, 
     const int64_t g = (n + 255) / 256;
     if (u->noise)
         hipLaunchKernelGGL(user_finish_noise_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
-                           p0mask, u->d_sum, u->d_info, u->n_ex, u->n_obs, u->d_const, u->d_const + 2 * u->n_ex, u->nz, lk, c->d_counters,
-                           u->count ? u->d_const + u->n_ex : nullptr, u->negbin);
+                           p0mask, d.d_sum, d.d_info, d.n_ex, u->n_obs, d.d_const, d.d_const + 2 * d.n_ex, u->nz, lk, c->d_counters,
+                           u->count ? d.d_const + d.n_ex : nullptr, u->negbin);
     else
         hipLaunchKernelGGL(user_finish_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c->stream, theta, stride, n,
-                           c->dim, p0mask, u->d_sum, u->d_info, u->n_ex, u->d_const, u->d_const + u->n_ex, u->est_sigma, u->sigma_fixed,
+                           c->dim, p0mask, d.d_sum, d.d_info, d.n_ex, d.d_const, d.d_const + d.n_ex, u->est_sigma, u->sigma_fixed,
                            lk, c->d_counters);
     if (u->spec.method == SMC_USER_METHOD_BDF) {
         if (!pred) (void)hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream);
-        const int64_t items = n * u->n_ex, gb = (items + 255) / 256;
-        hipLaunchKernelGGL(user_bdf_count_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0, c->stream, p0mask, u->d_bdf_counts,
-                           n, u->n_ex, u->d_bdf_totals);
+        const int64_t items = n * d.n_ex, gb = (items + 255) / 256;
+        hipLaunchKernelGGL(user_bdf_count_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0, c->stream, p0mask, d.d_bdf_counts,
+                           n, d.n_ex, u->d_bdf_totals);
     }
 }
 
 void launch_user_loglik(smc_ctx *c, const double *theta, int64_t stride, int64_t n, double *lk) {
-    if (n > 0) launch_user_kernel(c, theta, stride, n, nullptr, lk, false);
+    if (n > 0) launch_user_kernel(c, ((UserModel *)c->user)->data, theta, stride, n, nullptr, lk, false);
 }
 
 void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
@@ -676,13 +693,13 @@ void launch_user_mh(smc_ctx *c, int64_t n, const MHParams &mh_in) {
     const bool reject = c->early_reject != 0 && c->debug_capture == 0 && mh_in.gamma > 0.0 && c->d_reject;
     MHParams mh = mh_in;
     if (reject) {
-        mh.pending_sums = u->d_sum;          // the propose kernel marks every item of the sweep "not finished yet"
-        mh.pending_n_ex = u->n_ex;
+        mh.pending_sums = u->data.d_sum;     // the propose kernel marks every item of the sweep "not finished yet"
+        mh.pending_n_ex = u->data.n_ex;
         mh.reject_out = c->d_reject;
         mh.reject_lk1 = c->set[SMC_SET_FILT].lk;
     }
     launch_generic_propose(c, n, mh);
-    launch_user_kernel(c, P.theta, P.stride, n, c->d_p0, c->d_mlk2, reject);
+    launch_user_kernel(c, u->data, P.theta, P.stride, n, c->d_p0, c->d_mlk2, reject);
     launch_generic_accept(c, n, mh, c->d_mlk2);
 }
 
@@ -832,7 +849,7 @@ static std::vector<double> build_obs_image(const double *t, const double *obs, c
 
 // occupancy and LDS limit of the prediction kernel (u->fn_pred)
 static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
-    const size_t lds = user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, u->n_obs, u->noise, u->spec.censor != 0);
+    const size_t lds = user_lds_bytes3(u->spec.n_states, u->data.n_ex, u->data.n_t, u->n_obs, u->noise, u->spec.censor != 0);
     int nb = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu_pred = nb;
     if (lds > 48 * 1024 &&
@@ -842,9 +859,9 @@ static int prepare_pred_kernel(smc_ctx *c, UserModel *u) {
 }
 
 // ---- a design other than the data's (smc_user_predict_at, smc_user_predict_summary) ----------------------------------------
-// The prediction kernel takes n_ex and n_t as arguments and its data as an image, so a design is a second bundle of what
-// launch_user_kernel reads from the model, with every observation NaN (m_e = 0, no likelihood term).  A design whose image does
-// not fit the LDS cap runs as several such bundles, one per run of consecutive experiments.
+// The prediction kernel takes n_ex and n_t as arguments and its data as an image, so a design is a UserLaunchData of its own,
+// with every observation NaN (m_e = 0, no likelihood term).  A design whose image does not fit the LDS cap runs as several such
+// bundles, one per run of consecutive experiments.
 
 // what a launch writes per (experiment, particle): shared by the groups of a design, which run one after the other
 struct DesignItems {
@@ -869,19 +886,22 @@ static bool design_items_alloc(const UserModel *u, DesignItems &it, int64_t n, i
            (u->spec.method != SMC_USER_METHOD_BDF || hipMalloc(&it.d_bdf_counts, 4 * items * sizeof(unsigned)) == hipSuccess);
 }
 
+// experiments [e0, e0 + n_ex) of a design as what a launch runs on.  The group owns the image, the cond rows and the constants
+// of `d`; the per-item pointers of `d` are the design's DesignItems.
 struct DesignGroup {
-    double *d_img = nullptr, *d_cond = nullptr, *d_const = nullptr;
-    int e0 = 0, n_ex = 0, n_t = 0, img_len = 0, blocks_per_cu = 4;
+    UserLaunchData d;
+    int e0 = 0;
     void release() {
-        (void)hipFree(d_img);
-        (void)hipFree(d_cond);
-        (void)hipFree(d_const);
-        d_img = d_cond = d_const = nullptr;
+        (void)hipFree(d.d_img);
+        (void)hipFree(d.d_cond);
+        (void)hipFree(d.d_const);
+        d = UserLaunchData{};
     }
 };
 
 // experiments [e0, e0 + g) of the design (t: rows of n_t times, cond: rows of n_cond numbers) as a bundle on the device
-static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const double *t, const double *cond, int e0, int g, int n_t) {
+static bool design_group_build(const UserModel *u, DesignGroup &dg, const DesignItems &it, const double *t, const double *cond, int e0, int g,
+                               int n_t) {
     const std::vector<double> nan_obs((size_t)g * n_t * u->n_obs, std::nan("")), zero((u->noise ? 10 : 2) * (size_t)g, 0.0);
     std::vector<double> me, ls;
     if (!obs_layout(t + (size_t)e0 * n_t, nan_obs.data(), u->scale, g, n_t, u->n_obs, me, ls).empty()) return false;
@@ -889,44 +909,25 @@ static bool design_group_build(smc_ctx *c, UserModel *u, DesignGroup &dg, const 
                                                     u->noise ? &u->nz : nullptr, u->spec.censor != 0);      // no flag set
     const int cs = u->cond_stride();      // a model with inputs or events: cond holds whole rows, the tables included
     const size_t nc = (size_t)g * (cs > 0 ? cs : 1) * sizeof(double);
+    UserLaunchData &d = dg.d;
     dg.e0 = e0;
-    dg.n_ex = g;
-    dg.n_t = n_t;
-    dg.img_len = (int)img.size();
-    bool ok = hipMalloc(&dg.d_img, img.size() * sizeof(double)) == hipSuccess && hipMalloc(&dg.d_cond, nc) == hipSuccess &&
-              hipMalloc(&dg.d_const, zero.size() * sizeof(double)) == hipSuccess &&
-              hipMemcpy(dg.d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(dg.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    d.n_ex = g;
+    d.n_t = n_t;
+    d.img_len = (int)img.size();
+    d.d_sum = it.d_sum;
+    d.d_info = it.d_info;
+    d.d_bdf_counts = it.d_bdf_counts;
+    bool ok = hipMalloc(&d.d_img, img.size() * sizeof(double)) == hipSuccess && hipMalloc(&d.d_cond, nc) == hipSuccess &&
+              hipMalloc(&d.d_const, zero.size() * sizeof(double)) == hipSuccess &&
+              hipMemcpy(d.d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d.d_const, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && cs > 0)
-        ok = hipMemcpy(dg.d_cond, cond + (size_t)e0 * cs, nc, hipMemcpyHostToDevice) == hipSuccess;
+        ok = hipMemcpy(d.d_cond, cond + (size_t)e0 * cs, nc, hipMemcpyHostToDevice) == hipSuccess;
     const size_t lds = user_lds_bytes3(u->spec.n_states, g, n_t, u->n_obs, u->noise, u->spec.censor != 0);
     int nb = 0;
-    if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) dg.blocks_per_cu = nb;
-    (void)c;
+    if (ok && hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn_pred, 256, lds) == hipSuccess && nb >= 1) d.blocks_per_cu = nb;
     return ok;
 }
-
-// while it lives, launch_user_kernel(..., pred) runs the prediction kernel on the group instead of the data
-struct DesignScope {
-    UserModel *u;
-    UserModel saved;
-    DesignScope(UserModel *um, const DesignGroup &dg, const DesignItems &it) : u(um), saved(*um) {
-        u->d_img = dg.d_img;
-        u->img_len = dg.img_len;
-        u->d_cond = dg.d_cond;
-        u->d_const = dg.d_const;
-        u->n_ex = dg.n_ex;
-        u->n_t = dg.n_t;
-        u->blocks_per_cu_pred = dg.blocks_per_cu;
-        u->d_sum = it.d_sum;
-        u->d_info = it.d_info;
-        u->d_bdf_counts = it.d_bdf_counts;
-    }
-    ~DesignScope() {
-        saved.parity = u->parity;      // the one thing a launch changes in the model
-        *u = saved;
-    }
-};
 
 // the largest run of experiments whose image fits the LDS cap (0: not even one row)
 static int design_lds_group(const UserModel *u, int n_ex, int n_t) {
@@ -954,7 +955,7 @@ static int ensure_pred_kernel(smc_ctx *c, UserModel *u, const char *who) {
         return smc_fail(c, (std::string(who) + ": loading the prediction module failed").c_str());
     }
     // the data's own image may be one the kernel cannot hold (smc_user_predict refuses it): then only designs are predicted
-    if (user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, 1) <= kUserLdsCap && prepare_pred_kernel(c, u) != 0) {
+    if (user_lds_bytes3(u->spec.n_states, u->data.n_ex, u->data.n_t, 1) <= kUserLdsCap && prepare_pred_kernel(c, u) != 0) {
         u->fn_pred = nullptr;
         return 1;
     }
@@ -966,6 +967,119 @@ static int raise_pred_lds(smc_ctx *c, UserModel *u, const char *who) {
         return smc_fail(c, (std::string(who) + ": raising the dynamic LDS limit of the prediction kernel failed").c_str());
     return 0;
 }
+
+// The experiments per group of a summary under its staging budget (max_staging_bytes; 0: most of what is free), for `fixed` bytes
+// once and per_ex bytes per experiment of a group: at most g_lds, what the LDS cap allows.  0 with the refusal if not even one
+// experiment fits; `noun`: what the caller stages beside the predictions.
+static int design_staging_group(smc_ctx *c, const char *who, const char *noun, size_t max_staging_bytes, size_t fixed, size_t per_ex,
+                                int64_t n, int g_lds, int n_ex) {
+    size_t budget = max_staging_bytes;
+    if (budget == 0) {      // default: most of what is free
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+            smc_fail(c, (std::string(who) + ": hipMemGetInfo failed").c_str());
+            return 0;
+        }
+        budget = free_b / 10 * 8;
+    }
+    if (budget < fixed + per_ex) {
+        smc_fail(c, (std::string(who) + ": one experiment of the design needs " + std::to_string(fixed + per_ex) +
+                     " B of staging (predictions and " + noun + " of " + std::to_string(n) + " particles), max_staging_bytes allows " +
+                     std::to_string(budget) + " B").c_str());
+        return 0;
+    }
+    const int g_max = (int)std::min<size_t>((budget - fixed) / per_ex, (size_t)g_lds);
+    return g_max > n_ex ? n_ex : g_max;
+}
+
+// One run of the prediction kernel over a design, group after group (smc_user_predict_at, smc_user_predict_summary,
+// smc_user_pointwise_summary): the groups, what their launches write, the counters around them and, of a summary, its results
+// and three events per group.  A caller: alloc() with its own buffers, begin(), a loop over `groups` - solve(k, ...), then its
+// own kernels on d_ppred, then stamp(k) -, finish().  rc holds the first failure; solve() and stamp() expect rc == 0.  Everything
+// is released when the run goes out of scope, on whichever path.
+struct DesignRun {
+    smc_ctx *const c;
+    UserModel *const u;
+    const std::string who;
+    std::vector<DesignGroup> groups;
+    DesignItems items;
+    double *d_plk = nullptr, *d_ppred = nullptr;      // of one launch: the likelihoods the finish kernel writes, the predictions
+    // a summary: what its kernels leave of all groups, which finish() brings to the host; per group an event before the solve,
+    // one behind it and one behind the caller's kernels
+    double *d_out = nullptr;
+    std::vector<double> h_out;
+    std::vector<hipEvent_t> ev;
+    int rc = 0;
+    DesignRun(smc_ctx *c_, UserModel *u_, const char *who_) : c(c_), u(u_), who(who_) {}
+    DesignRun(const DesignRun &) = delete;
+    ~DesignRun() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (DesignGroup &dg : groups) dg.release();
+        items.release();
+        (void)hipFree(d_plk);
+        (void)hipFree(d_ppred);
+        (void)hipFree(d_out);
+    }
+    int fail(const std::string &what) { return rc = smc_fail(c, (who + ": " + what).c_str()); }
+    // the design in groups of g_max experiments, for launches of up to n particles; out_words > 0: a summary with that many words
+    // of results.  false: an allocation or an upload failed
+    bool alloc(const double *t, const double *cond, int n_ex, int n_t, int64_t n, int g_max, size_t out_words) {
+        groups.resize((size_t)(n_ex + g_max - 1) / g_max);
+        h_out.resize(out_words);
+        bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
+                  hipMalloc(&d_ppred, (size_t)n * g_max * n_t * u->n_obs * sizeof(double)) == hipSuccess &&
+                  (out_words == 0 || hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess);
+        for (size_t k = 0; ok && k < groups.size(); ++k) {
+            const int e0 = (int)k * g_max;
+            ok = design_group_build(u, groups[k], items, t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
+        }
+        if (out_words > 0) ev.assign(3 * groups.size(), nullptr);
+        for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
+        return ok;
+    }
+    // ok: alloc() and the caller's own allocations.  Clears the counters the launches add to.
+    int begin(bool ok) {
+        if (!ok) return fail("device allocation / upload failed");
+        if (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
+            (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess))
+            return fail("clearing the counters failed");
+        return 0;
+    }
+    // the solve of group k for the particles (theta, stride, n): its predictions are in d_ppred
+    int solve(size_t k, const double *theta, int64_t stride, int64_t n) {
+        if (!ev.empty()) (void)hipEventRecord(ev[3 * k], c->stream);
+        launch_user_kernel(c, groups[k].d, theta, stride, n, nullptr, d_plk, false, d_ppred);
+        if (c->launch_failed) {
+            c->launch_failed = false;
+            return rc = 1;
+        }
+        if (!ev.empty()) (void)hipEventRecord(ev[3 * k + 1], c->stream);
+        return 0;
+    }
+    void stamp(size_t k) {
+        if (!ev.empty()) (void)hipEventRecord(ev[3 * k + 2], c->stream);
+    }
+    // the one synchronisation, for results and counters: what the solves counted, and per part the time between the events
+    int finish(int64_t *n_failed, int64_t *attempts, double *kernel_ms) {
+        if (rc == 0 && ((d_out && hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+                        hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                        hipStreamSynchronize(c->stream) != hipSuccess))
+            fail(hipGetErrorString(hipGetLastError()));
+        if (rc != 0) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+        if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
+        if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
+        for (size_t k = 0; kernel_ms && 3 * k < ev.size(); ++k) {
+            float a_ms = 0.f, b_ms = 0.f;
+            if (hipEventElapsedTime(&a_ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) kernel_ms[0] += a_ms;
+            if (hipEventElapsedTime(&b_ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) kernel_ms[1] += b_ms;
+        }
+        return 0;
+    }
+};
 
 }  // namespace smc
 
@@ -1531,12 +1645,12 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     const size_t nt = (size_t)n_ex * n_t * sizeof(double);
     const bool tabled = in || ev;      // the cond rows carry a table
     const size_t nc = tabled ? rows.size() * sizeof(double) : (size_t)n_ex * (n_cond > 0 ? n_cond : 1) * sizeof(double);
-    bool ok = hipMalloc(&u->d_cond, nc) == hipSuccess;
+    bool ok = hipMalloc(&u->data.d_cond, nc) == hipSuccess;
     if (ok && !multi)      // the one-output kernel reads the data itself
         ok = hipMalloc(&u->d_t, nt) == hipSuccess && hipMalloc(&u->d_obs, nt) == hipSuccess &&
              hipMemcpy(u->d_t, t, nt, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(u->d_obs, obs, nt, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && tabled) ok = hipMemcpy(u->d_cond, rows.data(), nc, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !tabled && n_cond > 0) ok = hipMemcpy(u->d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && tabled) ok = hipMemcpy(u->data.d_cond, rows.data(), nc, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !tabled && n_cond > 0) ok = hipMemcpy(u->data.d_cond, cond, nc, hipMemcpyHostToDevice) == hipSuccess;
     {   // likelihood constants; and the image (one-output model: only if its data is what smc_set_model_user3 would accept)
         std::vector<double> k(2 * (size_t)n_ex, 0.0);
         for (int e = 0; e < n_ex; ++e) {
@@ -1547,17 +1661,17 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
             const std::vector<double> mek = count_mek(t, obs, n_ex, n_t, n_obs, censor, family);
             k.insert(k.end(), mek.begin(), mek.end());
         }
-        ok = ok && hipMalloc(&u->d_const, k.size() * sizeof(double)) == hipSuccess &&
-             hipMemcpy(u->d_const, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMalloc(&u->data.d_const, k.size() * sizeof(double)) == hipSuccess &&
+             hipMemcpy(u->data.d_const, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
         if (bad.empty() && !multi) {
             for (int e = 0; e < n_ex; ++e)
                 if (me[e] != (double)n_t) bad = "a missing observation (NaN)";
         }
         if (bad.empty()) {
             const std::vector<double> img = build_obs_image(t, obs, obs_scale, n_ex, n_t, n_obs, me, ls, nz, censor != nullptr, censor, family);
-            u->img_len = (int)img.size();
-            ok = ok && hipMalloc(&u->d_img, img.size() * sizeof(double)) == hipSuccess &&
-                 hipMemcpy(u->d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+            u->data.img_len = (int)img.size();
+            ok = ok && hipMalloc(&u->data.d_img, img.size() * sizeof(double)) == hipSuccess &&
+                 hipMemcpy(u->data.d_img, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
             std::vector<double> cv, cf;      // the pointwise kernels' tables
             std::vector<int> cc;
             build_cell_tables(t, obs, n_ex, n_t, n_obs, censor, family, cv, cc, cf);
@@ -1573,10 +1687,10 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
         }
     }
     if (ok && !c->d_mlk2) ok = hipMalloc(&c->d_mlk2, (size_t)c->n_local * sizeof(double)) == hipSuccess;
-    ok = ok && hipMalloc(&u->d_sum, (size_t)c->n_local * n_ex * sizeof(double)) == hipSuccess &&
-         hipMalloc(&u->d_info, (size_t)c->n_local * n_ex * sizeof(int)) == hipSuccess;
+    ok = ok && hipMalloc(&u->data.d_sum, (size_t)c->n_local * n_ex * sizeof(double)) == hipSuccess &&
+         hipMalloc(&u->data.d_info, (size_t)c->n_local * n_ex * sizeof(int)) == hipSuccess;
     if (ok && method == SMC_USER_METHOD_BDF)
-        ok = hipMalloc(&u->d_bdf_counts, (size_t)4 * c->n_local * n_ex * sizeof(unsigned)) == hipSuccess &&
+        ok = hipMalloc(&u->data.d_bdf_counts, (size_t)4 * c->n_local * n_ex * sizeof(unsigned)) == hipSuccess &&
              hipMalloc(&u->d_bdf_totals, 4 * sizeof(unsigned long long)) == hipSuccess &&
              hipMemset(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (ok && u->fn_scan)
@@ -1605,7 +1719,7 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
             user_model_release(c);
             return smc_fail(c, "smc_set_model_user: data set too large for the kernel's LDS table (n_ex * n_t * 16 B + pools > 150 KB)");
         }
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn, 256, lds) == hipSuccess && nb >= 1) u->blocks_per_cu = nb;
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, u->fn, 256, lds) == hipSuccess && nb >= 1) u->data.blocks_per_cu = nb;
         if (lds > 48 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(u->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             user_model_release(c);
@@ -1618,8 +1732,8 @@ static int set_model_user_impl(smc_ctx *c, const smc_user_model_spec &s, const c
     if (t) u->h_t.assign(t, t + (size_t)n_ex * n_t);
     if (n_cond > 0) u->h_cond.assign(cond, cond + (size_t)n_ex * n_cond);
     for (int k = 0; k < n_obs && obs_scale; ++k) u->scale[k] = obs_scale[k];
-    u->n_ex = n_ex;
-    u->n_t = n_t;
+    u->data.n_ex = n_ex;
+    u->data.n_t = n_t;
     u->n_cond = n_cond;
     u->est_sigma = plan.est_sigma;
     u->sigma_fixed = plan.sigma_fixed;
@@ -1796,27 +1910,15 @@ static int user_predict_impl(smc_ctx *c, const char *who, const double *particle
     if (n_failed) *n_failed = 0;
     if (attempts) *attempts = 0;
     if (n == 0) return 0;
-    if (!u->d_img) return smc_fail(c, u->img_error.c_str());
-    if (!u->fn_pred) {      // a one-output model of smc_set_model_user / 2: its prediction kernel, compiled once
-        if (user_lds_bytes3(u->spec.n_states, u->n_ex, u->n_t, 1) > kUserLdsCap)
-            return smc_fail(c, "smc_user_predict: data set too large for the prediction kernel's LDS table");
-        std::vector<char> code;
-        std::string lg;
-        if (!compile_user(u->source.c_str(), pred_source_spec(u), code, lg))
-            return smc_fail(c, ("smc_user_predict: the prediction kernel does not compile:\n" + lg.substr(0, 3000)).c_str());
-        if (hipModuleLoadData(&u->module_pred, code.data()) != hipSuccess ||
-            hipModuleGetFunction(&u->fn_pred, u->module_pred, "smc_user_predict_kernel") != hipSuccess) {
-            u->fn_pred = nullptr;
-            return smc_fail(c, "smc_user_predict: loading the prediction module failed");
-        }
-        if (prepare_pred_kernel(c, u) != 0) {
-            u->fn_pred = nullptr;
-            return 1;
-        }
-    }
+    if (!u->data.d_img) return smc_fail(c, u->img_error.c_str());
+    // a one-output model of smc_set_model_user / 2: its prediction kernel, compiled once (a multi-output model's data has been
+    // held to the cap when it was set)
+    if (!u->fn_pred && user_lds_bytes3(u->spec.n_states, u->data.n_ex, u->data.n_t, 1) > kUserLdsCap)
+        return smc_fail(c, "smc_user_predict: data set too large for the prediction kernel's LDS table");
+    if (ensure_pred_kernel(c, u, "smc_user_predict") != 0) return 1;
     const int dim = c->dim;
     const int64_t chunk = n < c->n_local ? n : c->n_local;      // the per-item buffers hold n_local particles
-    const size_t per = (size_t)u->n_ex * u->n_t * u->n_obs;
+    const size_t per = (size_t)u->data.n_ex * u->data.n_t * u->n_obs;
     if (chunk > u->p_cap) {
         (void)hipFree(u->d_pt);
         (void)hipFree(u->d_plk);
@@ -1845,7 +1947,7 @@ static int user_predict_impl(smc_ctx *c, const char *who, const double *particle
         if (hipMemcpyAsync(aos, particle + off * dim, (size_t)m * dim * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)
             return smc_fail(c, "smc_user_predict: upload failed");
         launch_aos_to_soa(c, aos, soa, m, dim, m);
-        launch_user_kernel(c, soa, m, m, nullptr, u->d_plk, false, u->d_ppred);
+        launch_user_kernel(c, u->pred_data(), soa, m, m, nullptr, u->d_plk, false, u->d_ppred);
         if (c->launch_failed) {
             c->launch_failed = false;
             return 1;
@@ -1892,11 +1994,11 @@ static int resolve_design(smc_ctx *c, UserModel *u, const char *who, const doubl
                           std::vector<double> &rows) {
     const std::string w = std::string(who) + ": ";
     if (!t) {
-        if (!u->d_img) return smc_fail(c, u->img_error.c_str());
+        if (!u->data.d_img) return smc_fail(c, u->img_error.c_str());
         t = u->h_t.data();
         cond = u->spec.geom.tabled() ? u->h_rows.data() : u->h_cond.data();
-        n_ex = u->n_ex;
-        n_t = u->n_t;
+        n_ex = u->data.n_ex;
+        n_t = u->data.n_t;
         return 0;
     }
     if (n_ex < 1 || n_t < 1) return smc_fail(c, (w + "bad design shape").c_str());
@@ -1963,59 +2065,30 @@ int smc_user_predict_at(smc_ctx *c, const double *particle, int64_t n, const dou
     const int dim = c->dim;
     const int64_t chunk = n < c->n_local ? n : c->n_local;      // the scan lists of a model with a cost hint hold n_local particles
     const size_t row = (size_t)n_t * u->n_obs;                   // one experiment of one particle
-    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
-    DesignItems items;
-    double *d_pt = nullptr, *d_plk = nullptr, *d_ppred = nullptr;
-    int rc = 0;
-    bool ok = design_items_alloc(u, items, chunk, g_max) && hipMalloc(&d_pt, (size_t)chunk * dim * 2 * sizeof(double)) == hipSuccess &&
-              hipMalloc(&d_plk, (size_t)chunk * sizeof(double)) == hipSuccess &&
-              hipMalloc(&d_ppred, (size_t)chunk * g_max * row * sizeof(double)) == hipSuccess;
-    for (size_t k = 0; ok && k < groups.size(); ++k) {
-        const int e0 = (int)k * g_max;
-        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
-    }
-    if (!ok) rc = smc_fail(c, "smc_user_predict_at: device allocation / upload failed");
+    DesignRun run(c, u, "smc_user_predict_at");
+    double *d_pt = nullptr;
+    run.begin(run.alloc(t, cond, n_ex, n_t, chunk, g_max, 0) && hipMalloc(&d_pt, (size_t)chunk * dim * 2 * sizeof(double)) == hipSuccess);
     double *aos = d_pt, *soa = d_pt + (size_t)chunk * dim;
-    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
-        rc = smc_fail(c, "smc_user_predict_at: clearing the counters failed");
-    for (int64_t off = 0; rc == 0 && off < n; off += chunk) {
+    for (int64_t off = 0; run.rc == 0 && off < n; off += chunk) {
         const int64_t m = (n - off < chunk) ? n - off : chunk;
         if (hipMemcpyAsync(aos, particle + off * dim, (size_t)m * dim * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            rc = smc_fail(c, "smc_user_predict_at: upload failed");
+            run.fail("upload failed");
             break;
         }
         launch_aos_to_soa(c, aos, soa, m, dim, m);
-        for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
-            const DesignGroup &dg = groups[k];
-            {
-                DesignScope scope(u, dg, items);
-                launch_user_kernel(c, soa, m, m, nullptr, d_plk, false, d_ppred);
-            }
-            if (c->launch_failed) {
-                c->launch_failed = false;
-                rc = 1;
-                break;
-            }
+        for (size_t k = 0; run.rc == 0 && k < run.groups.size(); ++k) {
+            if (run.solve(k, soa, m, m) != 0) break;
             // the group's experiments of every particle into their place in pred[p][e][i][k]
-            if (hipMemcpy2DAsync(pred + ((size_t)off * n_ex + dg.e0) * row, (size_t)n_ex * row * sizeof(double), d_ppred,
-                                 (size_t)dg.n_ex * row * sizeof(double), (size_t)dg.n_ex * row * sizeof(double), (size_t)m,
+            const DesignGroup &dg = run.groups[k];
+            if (hipMemcpy2DAsync(pred + ((size_t)off * n_ex + dg.e0) * row, (size_t)n_ex * row * sizeof(double), run.d_ppred,
+                                 (size_t)dg.d.n_ex * row * sizeof(double), (size_t)dg.d.n_ex * row * sizeof(double), (size_t)m,
                                  hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-                rc = smc_fail(c, "smc_user_predict_at: download failed");
+                run.fail("download failed");
         }
     }
-    if (rc == 0 && (hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess))
-        rc = smc_fail(c, (std::string("smc_user_predict_at: ") + hipGetErrorString(hipGetLastError())).c_str());
-    if (rc != 0) (void)hipStreamSynchronize(c->stream);
-    if (rc == 0 && n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
-    if (rc == 0 && attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
-    for (DesignGroup &dg : groups) dg.release();
-    items.release();
+    run.finish(n_failed, attempts, nullptr);
     (void)hipFree(d_pt);
-    (void)hipFree(d_plk);
-    (void)hipFree(d_ppred);
-    return rc;
+    return run.rc;
 }
 
 int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const double *cond_new, int n_ex_new, int n_t_new,
@@ -2055,59 +2128,22 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
     const size_t out_words = (size_t)cells_total * (3 + 2 * (size_t)n_probs);
     const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pred_summary_key_bytes(n, (int)row);
     const size_t fixed = (size_t)n * sizeof(double) + out_words * sizeof(double);
-    size_t budget = max_staging_bytes;
-    if (budget == 0) {      // default: most of what is free
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return smc_fail(c, "smc_user_predict_summary: hipMemGetInfo failed");
-        budget = free_b / 10 * 8;
-    }
-    if (budget < fixed + per_ex)
-        return smc_fail(c, (std::string(who) + ": one experiment of the design needs " + std::to_string(fixed + per_ex) +
-                            " B of staging (predictions and keys of " + std::to_string(n) + " particles), max_staging_bytes allows " +
-                            std::to_string(budget) + " B").c_str());
-    int g_max = (int)std::min<size_t>((budget - fixed) / per_ex, (size_t)g_lds);
-    if (g_max > n_ex) g_max = n_ex;
+    const int g_max = design_staging_group(c, who, "keys", max_staging_bytes, fixed, per_ex, n, g_lds, n_ex);
+    if (g_max < 1) return 1;
     if (ensure_pred_kernel(c, u, who) != 0 || raise_pred_lds(c, u, who) != 0) return 1;
 
-    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
-    std::vector<hipEvent_t> ev(3 * groups.size(), nullptr);
-    DesignItems items;
-    double *d_plk = nullptr, *d_ppred = nullptr, *d_out = nullptr;
+    DesignRun run(c, u, who);
     unsigned long long *d_keys = nullptr;
-    std::vector<double> h_out(out_words);
-    int rc = 0;
-    bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
-              hipMalloc(&d_ppred, (size_t)n * g_max * row * sizeof(double)) == hipSuccess &&
-              hipMalloc(&d_keys, pred_summary_key_bytes(n, (int)(g_max * row))) == hipSuccess &&
-              hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess;
-    for (size_t k = 0; ok && k < groups.size(); ++k) {
-        const int e0 = (int)k * g_max;
-        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
-    }
-    for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
-    if (!ok) rc = smc_fail(c, "smc_user_predict_summary: device allocation / upload failed");
-    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
-        rc = smc_fail(c, "smc_user_predict_summary: clearing the counters failed");
+    run.begin(run.alloc(t, cond, n_ex, n_t, n, g_max, out_words) && hipMalloc(&d_keys, pred_summary_key_bytes(n, (int)(g_max * row))) == hipSuccess);
     const ParticleSet &P = c->set[set];
-    for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
-        const DesignGroup &dg = groups[k];
-        (void)hipEventRecord(ev[3 * k], c->stream);
-        {
-            DesignScope scope(u, dg, items);
-            launch_user_kernel(c, P.theta, P.stride, n, nullptr, d_plk, false, d_ppred);
-        }
-        if (c->launch_failed) {
-            c->launch_failed = false;
-            rc = 1;
-            break;
-        }
-        (void)hipEventRecord(ev[3 * k + 1], c->stream);
+    for (size_t k = 0; run.rc == 0 && k < run.groups.size(); ++k) {
+        if (run.solve(k, P.theta, P.stride, n) != 0) break;
+        const DesignGroup &dg = run.groups[k];
         PredSummaryArgs a{};
-        a.pred = d_ppred;
+        a.pred = run.d_ppred;
         a.keys = d_keys;
         a.n = n;
-        a.cells = (int)(dg.n_ex * row);
+        a.cells = (int)(dg.d.n_ex * row);
         a.cell_base = (int64_t)dg.e0 * (int64_t)row;      // the GLOBAL cell index keys the noise: grouping cannot change a result
         a.cells_total = cells_total;
         a.n_obs = u->n_obs;
@@ -2125,17 +2161,12 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
         a.global_offset = global_offset;
         a.n_probs = n_probs;
         for (int j = 0; j < n_probs; ++j) a.probs[j] = probs[j];
-        a.out = d_out;
+        a.out = run.d_out;
         launch_pred_summary(c, a);
-        (void)hipEventRecord(ev[3 * k + 2], c->stream);
+        run.stamp(k);
     }
-    // the one synchronisation: results and counters
-    if (rc == 0 && (hipMemcpyAsync(h_out.data(), d_out, out_words * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess))
-        rc = smc_fail(c, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
-    if (rc != 0) (void)hipStreamSynchronize(c->stream);
-    if (rc == 0) {
+    if (run.finish(n_failed, attempts, kernel_ms) == 0) {
+        const std::vector<double> &h_out = run.h_out;
         const size_t ct = (size_t)cells_total;
         for (size_t i = 0; i < ct; ++i) {
             mean[i] = h_out[i];
@@ -2146,23 +2177,9 @@ int smc_user_predict_summary(smc_ctx *c, int set, const double *t_new, const dou
             lower[i] = h_out[3 * ct + i];
             upper[i] = h_out[(3 + (size_t)n_probs) * ct + i];
         }
-        if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
-        if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
-        for (size_t k = 0; kernel_ms && k < groups.size(); ++k) {
-            float a_ms = 0.f, b_ms = 0.f;
-            if (hipEventElapsedTime(&a_ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) kernel_ms[0] += a_ms;
-            if (hipEventElapsedTime(&b_ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) kernel_ms[1] += b_ms;
-        }
     }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (DesignGroup &dg : groups) dg.release();
-    items.release();
-    (void)hipFree(d_plk);
-    (void)hipFree(d_ppred);
     (void)hipFree(d_keys);
-    (void)hipFree(d_out);
-    return rc;
+    return run.rc;
 }
 
 int smc_user_pointwise_summary(smc_ctx *c, int set, size_t max_staging_bytes, int64_t *n_terms, double *max, double *sum_exp, double *mean,
@@ -2205,80 +2222,40 @@ int smc_user_pointwise_summary_opt(smc_ctx *c, int set, size_t max_staging_bytes
     const size_t per_ex = (size_t)n * (row * sizeof(double) + design_item_bytes(u)) + pointwise_terms_bytes(n, (int)row) + pointwise_pit_bytes(n, (int)row) +
                           (draw ? pointwise_pit_count_bytes(n, (int)row) : 0);
     const size_t fixed = (size_t)n * sizeof(double) + out_words * sizeof(double);
-    size_t budget = max_staging_bytes;
-    if (budget == 0) {      // default: most of what is free
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return smc_fail(c, "smc_user_pointwise_summary: hipMemGetInfo failed");
-        budget = free_b / 10 * 8;
-    }
-    if (budget < fixed + per_ex)
-        return smc_fail(c, (std::string(who) + ": one experiment of the design needs " + std::to_string(fixed + per_ex) +
-                            " B of staging (predictions and terms of " + std::to_string(n) + " particles), max_staging_bytes allows " +
-                            std::to_string(budget) + " B").c_str());
-    int g_max = (int)std::min<size_t>((budget - fixed) / per_ex, (size_t)g_lds);
-    if (g_max > n_ex) g_max = n_ex;
+    const int g_max = design_staging_group(c, who, "terms", max_staging_bytes, fixed, per_ex, n, g_lds, n_ex);
+    if (g_max < 1) return 1;
     if (ensure_pred_kernel(c, u, who) != 0 || raise_pred_lds(c, u, who) != 0) return 1;
 
-    std::vector<DesignGroup> groups((size_t)(n_ex + g_max - 1) / g_max);
-    std::vector<hipEvent_t> ev(3 * groups.size(), nullptr);
-    DesignItems items;
-    double *d_plk = nullptr, *d_ppred = nullptr, *d_out = nullptr, *d_terms = nullptr, *d_pit = nullptr;
+    DesignRun run(c, u, who);
+    double *d_terms = nullptr, *d_pit = nullptr;
     unsigned *d_cnt = nullptr;
-    std::vector<double> h_out(out_words);
-    int rc = 0;
-    bool ok = design_items_alloc(u, items, n, g_max) && hipMalloc(&d_plk, (size_t)n * sizeof(double)) == hipSuccess &&
-              hipMalloc(&d_ppred, (size_t)n * g_max * row * sizeof(double)) == hipSuccess &&
+    run.begin(run.alloc(t, cond, n_ex, n_t, n, g_max, out_words) &&
               hipMalloc(&d_terms, pointwise_terms_bytes(n, (int)(g_max * row))) == hipSuccess &&
               hipMalloc(&d_pit, pointwise_pit_bytes(n, (int)(g_max * row))) == hipSuccess &&
-              (!draw || hipMalloc(&d_cnt, pointwise_pit_count_bytes(n, (int)(g_max * row))) == hipSuccess) &&
-              hipMalloc(&d_out, out_words * sizeof(double)) == hipSuccess;
-    for (size_t k = 0; ok && k < groups.size(); ++k) {
-        const int e0 = (int)k * g_max;
-        ok = design_group_build(c, u, groups[k], t, cond, e0, n_ex - e0 < g_max ? n_ex - e0 : g_max, n_t);
-    }
-    for (size_t k = 0; ok && k < ev.size(); ++k) ok = hipEventCreate(&ev[k]) == hipSuccess;
-    if (!ok) rc = smc_fail(c, "smc_user_pointwise_summary: device allocation / upload failed");
-    if (rc == 0 && (hipMemsetAsync(c->d_counters, 0, sizeof(SweepCounters), c->stream) != hipSuccess ||
-                    (u->spec.method == SMC_USER_METHOD_BDF && hipMemsetAsync(u->d_bdf_totals, 0, 4 * sizeof(unsigned long long), c->stream) != hipSuccess)))
-        rc = smc_fail(c, "smc_user_pointwise_summary: clearing the counters failed");
+              (!draw || hipMalloc(&d_cnt, pointwise_pit_count_bytes(n, (int)(g_max * row))) == hipSuccess));
     const ParticleSet &P = c->set[set];
-    for (size_t k = 0; rc == 0 && k < groups.size(); ++k) {
-        const DesignGroup &dg = groups[k];
-        (void)hipEventRecord(ev[3 * k], c->stream);
-        {
-            DesignScope scope(u, dg, items);
-            launch_user_kernel(c, P.theta, P.stride, n, nullptr, d_plk, false, d_ppred);
-        }
-        if (c->launch_failed) {
-            c->launch_failed = false;
-            rc = 1;
-            break;
-        }
-        (void)hipEventRecord(ev[3 * k + 1], c->stream);
+    for (size_t k = 0; run.rc == 0 && k < run.groups.size(); ++k) {
+        if (run.solve(k, P.theta, P.stride, n) != 0) break;
+        const DesignGroup &dg = run.groups[k];
         PointwiseArgs a = pointwise_args_of(c, u);
-        a.pred = d_ppred;
+        a.pred = run.d_ppred;
         a.terms = d_terms;
         a.pit_part = d_pit;
         a.pit_cnt = d_cnt;
         a.seed = draw ? opts->seed : 0;
         a.global_offset = draw ? opts->global_offset : 0;
         a.n = n;
-        a.cells = (int)(dg.n_ex * row);
+        a.cells = (int)(dg.d.n_ex * row);
         a.cell_base = (int64_t)dg.e0 * (int64_t)row;
         a.cells_total = cells_total;
         a.theta = P.theta;
         a.stride = P.stride;
-        a.out = d_out;
+        a.out = run.d_out;
         launch_pointwise(c, a);
-        (void)hipEventRecord(ev[3 * k + 2], c->stream);
+        run.stamp(k);
     }
-    // the one synchronisation: results and counters
-    if (rc == 0 && (hipMemcpyAsync(h_out.data(), d_out, out_words * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(c->h_counters, c->d_counters, sizeof(SweepCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess))
-        rc = smc_fail(c, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
-    if (rc != 0) (void)hipStreamSynchronize(c->stream);
-    if (rc == 0) {
+    if (run.finish(n_failed, attempts, kernel_ms) == 0) {
+        const std::vector<double> &h_out = run.h_out;
         const size_t ct = (size_t)cells_total;
         for (size_t i = 0; i < ct; ++i) {
             n_terms[i] = (int64_t)h_out[i];
@@ -2293,25 +2270,11 @@ int smc_user_pointwise_summary_opt(smc_ctx *c, int set, size_t max_staging_bytes
             opts->pit_equal[i] = draw ? (int64_t)h_out[(kPwOutWords + 1) * ct + i] : 0;
             opts->pit_n[i] = draw ? (int64_t)h_out[(kPwOutWords + 2) * ct + i] : 0;
         }
-        if (n_failed) *n_failed = (int64_t)c->h_counters->n_failed;
-        if (attempts) *attempts = (int64_t)c->h_counters->rk_attempts;
-        for (size_t k = 0; kernel_ms && k < groups.size(); ++k) {
-            float a_ms = 0.f, b_ms = 0.f;
-            if (hipEventElapsedTime(&a_ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) kernel_ms[0] += a_ms;
-            if (hipEventElapsedTime(&b_ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) kernel_ms[1] += b_ms;
-        }
     }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (DesignGroup &dg : groups) dg.release();
-    items.release();
-    (void)hipFree(d_plk);
-    (void)hipFree(d_ppred);
     (void)hipFree(d_terms);
     (void)hipFree(d_pit);
     (void)hipFree(d_cnt);
-    (void)hipFree(d_out);
-    return rc;
+    return run.rc;
 }
 
 int smc_user_sweep_counters(smc_ctx *c, int64_t out[4]) {

@@ -373,38 +373,80 @@ def test_staging_groups_do_not_change_a_bit_and_too_little_is_refused(pkg):
                 eng.predictive_summary(max_staging_bytes=need - 1, **kw)
 
 
+# the two-output reactions with a cost hint (include/smc_hip.h: smc_user_cost) that puts about four particles in ten of the
+# populations below on the stiff list (cost > 220) and one in ten among the solo solves (cost > 3700)
+AB_WITH_COST = "__device__ double smc_user_cost(const double *theta) { return theta[0] > 0.9 ? 5000.0 : (theta[0] > 0.8 ? 300.0 : 0.0); }\n"
+
+
 @pytest.mark.gpu
-def test_summary_leaves_sets_lk_flags_and_work_totals_alone(pkg):
+@pytest.mark.parametrize("model", ["plain", "cost_hint", "bdf"])
+def test_summary_leaves_sets_lk_flags_and_work_totals_alone(pkg, model):
+    """Two engines run upload / loglik / sweep / sweep / sweep; one of them predicts in between the first two sweeps - both
+    summaries, ungrouped and in groups of one experiment, the pointwise summary and predict_user_at on a design of six groups' worth.
+    What the predictions run on is not the model's: the sets, lk and flags are untouched by them, and every later sweep is the
+    twin's bit for bit.  cost_hint: with stiff_first the scan lists and their alternating counters run in every launch, the
+    predictions' too; bdf: the per-item work counters are part of what a launch writes.
+    The second sweep runs without early rejection: where a certainly rejected solve stops is not part of the result, so with
+    it rk_attempts and the BDF work totals differ between two runs of the same code (see the full-run test below); without it
+    every count of the sweep must be the twin's.  The third runs with it again and is held to its results."""
     t, obs, A0, k_true, _, scale = _ab_data(seed=3)
-    n = 4096
+    n = 4096 if model == "plain" else 512
     rs = np.random.RandomState(7)
     th = np.column_stack([k_true[0] * (1 + 0.1 * rs.standard_normal(n)), k_true[1] * (1 + 0.1 * rs.standard_normal(n)),
                           rs.uniform(0.005, 0.03, n)])
-    with pkg.HipEngine(n, 3, device=0) as eng:
-        eng.set_prior(PRIORS)
-        eng.set_model_user(pkg.user_models.CONSECUTIVE_REACTIONS_AB, 2, t, obs, cond=A0[:, None], obs_scale=scale)
-        eng.upload_particles(pkg.SMC_SET_PRED, th)
-        eng.loglik(pkg.SMC_SET_PRED)
-        eng.upload_particles(pkg.SMC_SET_FILT, th)
-        eng.upload_lk(pkg.SMC_SET_FILT, eng.download_lk(pkg.SMC_SET_PRED))
-        mh = eng.mh_step_device_rng(0.5, 1.0, np.diag([0.004, 0.004, 0.002]), 7, 3)
-        assert 0 < mh["accepted_now"] < n
+    source = pkg.user_models.CONSECUTIVE_REACTIONS_AB + (AB_WITH_COST if model == "cost_hint" else "")
+    step = np.diag([0.004, 0.004, 0.002])
+    t_new = np.tile(np.linspace(0.0, 12.0, 50), (6, 1))
+    design = {"t": t_new, "cond": np.linspace(0.5, 3.0, 6)[:, None]}
 
-        def state():
-            return [eng.download_particles(pkg.SMC_SET_PRED), eng.download_particles(pkg.SMC_SET_FILT), eng.download_lk(pkg.SMC_SET_PRED),
-                    eng.download_lk(pkg.SMC_SET_FILT), eng.download_accept_flags().astype(np.float64),
-                    np.asarray(list(eng.work_totals().values()) if isinstance(eng.work_totals(), dict) else eng.work_totals(), dtype=np.float64)]
-        before = state()
-        t_new = np.tile(np.linspace(0.0, 12.0, 50), (6, 1))
-        eng.predictive_summary(pkg.SMC_SET_FILT)
-        eng.predictive_summary(pkg.SMC_SET_PRED, t=t_new, cond=np.linspace(0.5, 3.0, 6)[:, None], noise=True, seed=5)
-        after = state()
-        # ... and the next sweep is what it would have been
-        mh2 = eng.mh_step_device_rng(0.5, 1.0, np.diag([0.004, 0.004, 0.002]), 7, 4)
-    assert before[4].sum() > 0
-    for a, b in zip(before, after):
+    def run(predict):
+        with pkg.HipEngine(n, 3, device=0) as eng:
+            eng.set_prior(PRIORS)
+            eng.set_stiff_first(True)
+            eng.set_model_user(source, 2, t, obs, cond=A0[:, None], obs_scale=scale, method="BDF" if model == "bdf" else "RK45")
+            eng.upload_particles(pkg.SMC_SET_PRED, th)
+            eng.loglik(pkg.SMC_SET_PRED)
+            eng.upload_particles(pkg.SMC_SET_FILT, th)
+            eng.upload_lk(pkg.SMC_SET_FILT, eng.download_lk(pkg.SMC_SET_PRED))
+            mh = eng.mh_step_device_rng(0.5, 1.0, step, 7, 3)
+            assert 0 < mh["accepted_now"] < n
+
+            def state():
+                return [eng.download_particles(pkg.SMC_SET_PRED), eng.download_particles(pkg.SMC_SET_FILT), eng.download_lk(pkg.SMC_SET_PRED),
+                        eng.download_lk(pkg.SMC_SET_FILT), eng.download_accept_flags().astype(np.float64),
+                        np.asarray(list(eng.work_totals().values()) if isinstance(eng.work_totals(), dict) else eng.work_totals(), dtype=np.float64)]
+            out = {"before": state()}
+            if predict:
+                eng.predictive_summary(pkg.SMC_SET_FILT)
+                eng.predictive_summary(pkg.SMC_SET_PRED, noise=True, seed=5, **design)
+                need = _bytes_of_one_experiment(pkg, eng, **design)
+                eng.predictive_summary(pkg.SMC_SET_PRED, noise=True, seed=5, max_staging_bytes=need, **design)     # six groups
+                eng.pointwise_summary(pkg.SMC_SET_FILT)
+                pred, info = eng.predict_user_at(np.concatenate([th, th[:37]]), **design)                           # two chunks
+                assert info["n_failed"] == 0 and not np.isnan(pred).any()
+            out["after"] = state()
+            eng.set_early_reject(False)
+            out["mh2"] = eng.mh_step_device_rng(0.5, 1.0, step, 7, 4)
+            out["work2"] = eng.user_sweep_counters() if model == "bdf" else None
+            out["state2"] = state()
+            eng.set_early_reject(True)
+            mh3 = eng.mh_step_device_rng(0.5, 1.0, step, 7, 5)
+            out["mh3"] = {k: mh3[k] for k in ("accepted_now", "accepted_ever", "n_failed")}
+            out["state3"] = state()
+        return out
+    with_pred, twin = run(True), run(False)
+    assert with_pred["before"][4].sum() > 0
+    for a, b in zip(with_pred["before"], with_pred["after"]):
         assert a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-    assert mh2["n_failed"] == 0
+    # ... and the next sweeps are what they would have been
+    assert with_pred["mh2"] == twin["mh2"] and with_pred["mh2"]["n_failed"] == 0 and 0 < with_pred["mh2"]["accepted_now"] < n
+    assert with_pred["mh3"] == twin["mh3"] and 0 < with_pred["mh3"]["accepted_now"] < n
+    if model == "bdf":
+        print(f"BDF work of the second sweep: {with_pred['work2']}")
+        assert with_pred["work2"] == twin["work2"] and with_pred["work2"]["steps"] > 0
+    for key in ("state2", "state3"):
+        for a, b in zip(with_pred[key][:5], twin[key][:5]):      # both sets, both lk, the flags
+            assert a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64)), key
 
 
 @pytest.mark.gpu
