@@ -547,11 +547,16 @@ __device__ __forceinline__ bool mm_certainly_rejected(const MMModel &mm, const S
 // EXACT: parity mode (smc_set_exact_pow) - the step controller's power is the correctly rounded pow(x, -0.2), mm_rk45.h.
 // FAST: lone chains run the hand-written attempt loop (mm_rk45.h: mm_fast_uniform_attempts).  A template parameter, not a flag:
 // selected at run time the block's registers cost the kernel its fourth wave per SIMD (140 instead of 128 VGPRs); as its own
-// instantiation it fits into 128, but its bulk loop is still ~6 % slower than the plain one's (register allocation around the
+// instantiation it fits into 128, but its bulk loop was ~6 % slower than the plain one's (register allocation around the
 // block), which a sweep over 10^6 particles does not notice and one over 10^7 does: launch_solve picks by the size of the sweep.
+// (With mm_item_attempt_lane the two run a steady-state sweep of 10^6 particles alike: 1.033 / 1.034 ms, profiles/ab_bulk_attempt.log.)
 // SHARE: the items are solve groups of replicate experiments (ShareArgs; mm_rk45.h: mm_dense_outputs).
-template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false>
+// LANE_FORM: the attempt of the two per-lane call sites of solve_persistent (bulk loop, lane tail): 1 = mm_item_attempt_lane, the
+// form with the fewest vector instructions on the common path; 0 = mm_item_attempt as everywhere else (always in parity mode;
+// in the default mode for A/B runs, SMC_BULK_ATTEMPT=0).  Same bits either way.
+template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false, int LANE_FORM = 0>
 struct MMOps {
+    static_assert(!(EXACT && LANE_FORM != 0), "parity mode keeps mm_item_attempt");
     struct Item {
         MMItem s;
         int64_t out_idx;    // e*n + p
@@ -690,6 +695,10 @@ struct MMOps {
     __device__ __forceinline__ int attempt(Item &it) const {
         return mm_item_attempt<WRITE_PRED, kDivLean6, EXACT, SHARE>(it.s, s_tp, n_t, rtol, atol, it.pred, sum2_word());
     }
+    __device__ __forceinline__ int attempt_lane(Item &it) const {
+        if (LANE_FORM == 0) return attempt(it);
+        return mm_item_attempt_lane<WRITE_PRED, SHARE>(it.s, s_tp, n_t, rtol, atol, it.pred, sum2_word());
+    }
     __device__ __forceinline__ bool long_running(const Item &it) const { return it.s.attempts > kLongItemAttempts; }
     __device__ __forceinline__ long long positions() const { return n_pos; }
     __device__ __forceinline__ int start_at(long long pos, int e, Item &nb) const {
@@ -777,7 +786,7 @@ struct MMOps {
     }
 };
 
-template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false>
+template <bool WRITE_PRED, bool EXACT, bool FAST, bool SHARE = false, int LANE_FORM = 0>
 __device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs &a, const ShareArgs *sh = nullptr) {
     extern __shared__ double2 smem_tp[];
     if (a.ctl && __builtin_amdgcn_readfirstlane(a.ctl->stop)) return;   // the Metropolis loop has ended: nothing to solve (scalar branch)
@@ -799,7 +808,7 @@ __device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs
     const unsigned n_stiff = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[0]) : 0u;
     unsigned n_solo = a.stiff_list ? (unsigned)__builtin_amdgcn_readfirstlane((int)a.stiff_count[1]) : 0u;
     if (n_solo > a.solo_cap) n_solo = a.solo_cap;   // the overflow went onto the ordinary list (stiff_list_append)
-    MMOps<WRITE_PRED, EXACT, FAST, SHARE> ops{mm, a, s_tp, s_S0, (long long)a.n, SHARE ? sh->n_solve : n_ex, own_sgpr(n_t), a.stiff_list, n_stiff,
+    MMOps<WRITE_PRED, EXACT, FAST, SHARE, LANE_FORM> ops{mm, a, s_tp, s_S0, (long long)a.n, SHARE ? sh->n_solve : n_ex, own_sgpr(n_t), a.stiff_list, n_stiff,
                                  a.stiff_list ? a.stiff_list + (a.stiff_cap - 1) : nullptr, n_solo, own_sgpr(mm.rtol), own_sgpr(mm.atol),
                                  own_sgpr(a.patience),
                                  a.n_ordered ? (long long)__builtin_amdgcn_readfirstlane((int)a.n_ordered[0]) : (long long)a.n,
@@ -811,13 +820,23 @@ __device__ __forceinline__ void mm_solve_body(const MMModel &mm, const SolveArgs
 // attempt loop in registers of their own the allocator otherwise lands on 130.
 template <bool WRITE_PRED, bool EXACT, bool FAST>
 __global__ void __launch_bounds__(kSolveBlock) mm_solve_kernel(MMModel mm, SolveArgs a) {
-    mm_solve_body<WRITE_PRED, EXACT, FAST>(mm, a);
+    mm_solve_body<WRITE_PRED, EXACT, FAST, false, EXACT ? 0 : 1>(mm, a);
+}
+// The default-mode kernels with the per-lane attempt in the form of mm_item_attempt (MMOps: LANE_FORM 0), under names of their
+// own: chosen at launch by SMC_BULK_ATTEMPT=0 (smc_create), for A/B runs and tests/test_gpu_bulk_attempt_paths.py.
+template <bool WRITE_PRED, bool FAST>
+__global__ void __launch_bounds__(kSolveBlock) mm_solve_form0_kernel(MMModel mm, SolveArgs a) {
+    mm_solve_body<WRITE_PRED, false, FAST, false, 0>(mm, a);
 }
 #ifndef SMC_NO_OWN_SGPR
 #define SMC_SOLVE_DEFAULT_MODE(WP, F)                                                                                              \
     template <>                                                                                                                    \
     __global__ void __launch_bounds__(kSolveBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) mm_solve_kernel<WP, false, F>(MMModel mm, SolveArgs a) { \
-        mm_solve_body<WP, false, F>(mm, a);                                                                                        \
+        mm_solve_body<WP, false, F, false, 1>(mm, a);                                                                              \
+    }                                                                                                                              \
+    template <>                                                                                                                    \
+    __global__ void __launch_bounds__(kSolveBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) mm_solve_form0_kernel<WP, F>(MMModel mm, SolveArgs a) { \
+        mm_solve_body<WP, false, F, false, 0>(mm, a);                                                                              \
     }
 SMC_SOLVE_DEFAULT_MODE(false, false)     // (the WRITE_PRED instantiations - predictions for the drop-in's plots - stay with the primary template)
 SMC_SOLVE_DEFAULT_MODE(false, true)
@@ -827,13 +846,21 @@ SMC_SOLVE_DEFAULT_MODE(false, true)
 // launch, so that a data set without replicates (or smc_set_share_replicates(0)) runs exactly the code above.
 template <bool WRITE_PRED, bool EXACT, bool FAST>
 __global__ void __launch_bounds__(kSolveBlock) mm_solve_share_kernel(MMModel mm, SolveArgs a, ShareArgs sh) {
-    mm_solve_body<WRITE_PRED, EXACT, FAST, true>(mm, a, &sh);
+    mm_solve_body<WRITE_PRED, EXACT, FAST, true, EXACT ? 0 : 1>(mm, a, &sh);
+}
+template <bool WRITE_PRED, bool FAST>
+__global__ void __launch_bounds__(kSolveBlock) mm_solve_share_form0_kernel(MMModel mm, SolveArgs a, ShareArgs sh) {
+    mm_solve_body<WRITE_PRED, false, FAST, true, 0>(mm, a, &sh);
 }
 #ifndef SMC_NO_OWN_SGPR
 #define SMC_SOLVE_SHARE_DEFAULT_MODE(WP, F)                                                                                        \
     template <>                                                                                                                    \
     __global__ void __launch_bounds__(kSolveBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) mm_solve_share_kernel<WP, false, F>(MMModel mm, SolveArgs a, ShareArgs sh) { \
-        mm_solve_body<WP, false, F, true>(mm, a, &sh);                                                                             \
+        mm_solve_body<WP, false, F, true, 1>(mm, a, &sh);                                                                          \
+    }                                                                                                                              \
+    template <>                                                                                                                    \
+    __global__ void __launch_bounds__(kSolveBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) mm_solve_share_form0_kernel<WP, F>(MMModel mm, SolveArgs a, ShareArgs sh) { \
+        mm_solve_body<WP, false, F, true, 0>(mm, a, &sh);                                                                          \
     }
 SMC_SOLVE_SHARE_DEFAULT_MODE(false, false)
 SMC_SOLVE_SHARE_DEFAULT_MODE(false, true)
@@ -1243,6 +1270,12 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
     void (*kern_share)(MMModel, SolveArgs, ShareArgs) =
         pred ? (exact ? mm_solve_share_kernel<true, true, false> : fast ? mm_solve_share_kernel<true, false, true> : mm_solve_share_kernel<true, false, false>)
              : (exact ? mm_solve_share_kernel<false, true, false> : fast ? mm_solve_share_kernel<false, false, true> : mm_solve_share_kernel<false, false, false>);
+    if (!exact && ctx->bulk_attempt_form0) {     // SMC_BULK_ATTEMPT=0: the per-lane attempt as mm_item_attempt (A/B runs)
+        kern = pred ? (fast ? mm_solve_form0_kernel<true, true> : mm_solve_form0_kernel<true, false>)
+                    : (fast ? mm_solve_form0_kernel<false, true> : mm_solve_form0_kernel<false, false>);
+        kern_share = pred ? (fast ? mm_solve_share_form0_kernel<true, true> : mm_solve_share_form0_kernel<true, false>)
+                          : (fast ? mm_solve_share_form0_kernel<false, true> : mm_solve_share_form0_kernel<false, false>);
+    }
     if (lds > 48 * 1024 && !ctx->solve_lds_raised) {
         // the largest data set (16 x 256) needs 66 + 30 KB of the CU's 160 KB: above the default dynamic limit.  The
         // attribute belongs to the (function, device) pair, so the flag lives in the context, not in the process.
@@ -1252,7 +1285,11 @@ static void launch_solve(smc_ctx *ctx, const double *theta, int64_t stride, int6
                               reinterpret_cast<const void *>(&mm_solve_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_kernel<false, false, true>),
                               reinterpret_cast<const void *>(&mm_solve_share_kernel<true, true, false>), reinterpret_cast<const void *>(&mm_solve_share_kernel<true, false, false>),
                               reinterpret_cast<const void *>(&mm_solve_share_kernel<true, false, true>), reinterpret_cast<const void *>(&mm_solve_share_kernel<false, true, false>),
-                              reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, true>)})
+                              reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, false>), reinterpret_cast<const void *>(&mm_solve_share_kernel<false, false, true>),
+                              reinterpret_cast<const void *>(&mm_solve_form0_kernel<true, false>), reinterpret_cast<const void *>(&mm_solve_form0_kernel<true, true>),
+                              reinterpret_cast<const void *>(&mm_solve_form0_kernel<false, false>), reinterpret_cast<const void *>(&mm_solve_form0_kernel<false, true>),
+                              reinterpret_cast<const void *>(&mm_solve_share_form0_kernel<true, false>), reinterpret_cast<const void *>(&mm_solve_share_form0_kernel<true, true>),
+                              reinterpret_cast<const void *>(&mm_solve_share_form0_kernel<false, false>), reinterpret_cast<const void *>(&mm_solve_share_form0_kernel<false, true>)})
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (e != hipSuccess) {
             smc_fail(ctx, "mm_solve_kernel: raising the dynamic LDS limit failed (hipFuncSetAttribute)");

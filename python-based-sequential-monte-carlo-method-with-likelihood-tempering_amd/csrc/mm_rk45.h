@@ -27,6 +27,12 @@
 #define SMC_HAVE_POW_FIFTH_EXACT 1
 #include "rk45_math.h"
 
+#ifdef SMC_ISA_MARKS   // analysis builds only (tools/bulk_loop_report.py, see solve_sched.h)
+#define SMC_RK45_MARK(name) asm volatile("; MARK " name)
+#else
+#define SMC_RK45_MARK(name)
+#endif
+
 namespace smc {
 
 // Dormand-Prince coefficients (rk.py:377-404), the same double literals Python evaluates.
@@ -184,7 +190,27 @@ __device__ __forceinline__ bool mm_item_begin(MMItem &it, double Vmax, double Km
 struct RkStages {
     double k1, k2, k3, k4, k5, k6, y_new, error_norm;
 };
-template <int LEAN /* kDiv* */>
+// v_min_f64 / v_max_f64 as single instructions.  fmin() / fmax() put a canonicalising `v_max_f64 x, x` in front of every operand
+// the compiler cannot prove free of signalling NaNs (a value from LDS, an fabs(), the join of two paths): one more vector
+// instruction in an issue-bound loop.  For operands that are never a signalling NaN the results are the same bits.
+__device__ __forceinline__ double raw_min(double a, double b) {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double raw_max_s(double a, double b_uniform) {   // second operand: a constant, in a scalar register pair
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b_uniform));
+    return r;
+}
+__device__ __forceinline__ double raw_max_abs(double a, double b) {   // max(|a|, |b|)
+    double r;
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// RAW_MAX: the scale's maximum by raw_max_abs (the per-lane attempt, mm_item_attempt_lane); y is the solver's state and y_new
+// the result of a fused multiply-add: neither is ever a signalling NaN.
+template <int LEAN /* kDiv* */, bool RAW_MAX = false>
 __device__ __forceinline__ RkStages rk_attempt_core(double y, double k0, double h, double negVmax, double Km,
                                                     double rtol, double atol) {
     RkStages s;
@@ -198,7 +224,7 @@ __device__ __forceinline__ RkStages rk_attempt_core(double y, double k0, double 
     // np.maximum(|y|, |y_new|) propagates NaN, v_max_f64 returns the other operand - and it makes no difference to the one
     // value that is used, error_norm: a NaN y makes k0, a NaN y_new makes k6 and with it err NaN whatever the scale is.  One
     // instruction instead of two compares, an or and two selects, in every attempt.
-    const double scale = atol + fmax(fabs(y), fabs(s.y_new)) * rtol;
+    const double scale = atol + (RAW_MAX ? raw_max_abs(y, s.y_new) : fmax(fabs(y), fabs(s.y_new))) * rtol;
     const double err = (k0 * E1 + s.k2 * E3 + s.k3 * E4 + s.k4 * E5 + s.k5 * E6 + s.k6 * E7) * h;
     s.error_norm = fabs(mm_div<LEAN>(err, scale));
     return s;
@@ -339,6 +365,7 @@ __device__ __forceinline__ int mm_item_attempt(MMItem &it, const double2 *s_tp, 
     bool accept = st.error_norm < 1.0;
     const bool redo = !EXACT && !__builtin_isfinite(st.error_norm);   // NaN / inf from the lean division (v_cmp_class: no constant)
     if (fail || redo || (accept && it.t_next <= t_new)) {
+        SMC_RK45_MARK("off_path rare_branch");
         if (fail) return 2;
         if (redo) {
             st = rk_attempt_core<kDivIeee>(y, k0, h, negVmax, Km, rtol, atol);
@@ -358,6 +385,83 @@ __device__ __forceinline__ int mm_item_attempt(MMItem &it, const double2 *s_tp, 
     it.f = accept ? st.k6 : k0;
     // head of the next _step_impl (rk.py:120-127) after an accepted step; after a rejection t, hence
     // min_step, is unchanged and the reference only re-tests h_abs < min_step (top of this function)
+    it.min_step = min_step_of(it.t);
+    it.h_abs = (accept && it.h_abs < it.min_step) ? it.min_step : it.h_abs;
+    return (accept && (t_new - it.t_bound >= 0)) ? 1 : 0;  // base.py:196
+}
+
+// The same attempt for the two places where every lane runs its own item (solve_sched.h: the bulk loop and the lane tail),
+// default arithmetic only.  Those loops are issue-bound (profiles/r05_pmc_sq_summary.json: vector ALUs busy 84.5 %), so what
+// counts is the number of vector instructions on the path of an attempt that is accepted or rejected with no output due.
+// Same operations, same operands, same order of roundings as mm_item_attempt<WRITE_PRED, kDivLean6, false, SHARE> - the
+// stages and the error norm ARE rk_attempt_core<kDivLean6> - and bit-identical results (tests/test_gpu_bulk_attempt_paths.py
+// runs both forms); what is gone is bookkeeping around the arithmetic (tools/bulk_loop_report.py):
+//   * the canonicalising v_max_f64 x, x in front of three minima / maxima (raw_min and friends above): t_bound, |y| and the
+//     power are never signalling NaNs;
+//   * the window test of pow_minus_fifth (five vector instructions, two exec-mask switches and two branches per attempt):
+//     the fast core's value is taken unconditionally, and "error norm outside 2^-64 .. 2^64" (zero, inf and NaN included, so
+//     the lean division's re-run too) is one more reason for the ONE rare branch, where today's pow_minus_fifth is called;
+//   * the step controller's factor.  rk.py:149-171 is
+//         accepted:  f = min(10, pw), and f = min(1, f) after a rejection in this step;      rejected:  f = max(0.2, pw)
+//     with Python's min / max (py_min / py_max: keep the first argument unless the second is strictly better), which the
+//     other form evaluates on both sides and then selects from.  Here the BOUNDS are selected - hi = 1 or 10 (accepted) or
+//     +inf (rejected): three doubles whose low words are zero, so two v_cndmask_b32 on the high word - and one v_min_f64 and
+//     one v_max_f64 apply them: f = max(min(pw, hi), 0.2).  Equal to the above on every pw that reaches it:
+//       - pw is never NaN here: a NaN error norm is outside the window, goes through the rare branch, and is replaced there by
+//         0 (py_max(0.2, NaN) = 0.2 = max(min(0, inf), 0.2); a NaN error norm is never accepted);
+//       - accepted, pw not NaN: py_min(10, pw) = min(pw, 10), py_min(1, min(pw, 10)) = min(pw, 1); the lower bound does nothing
+//         because error_norm < 1 makes pw = 0.9 * error_norm ** -0.2 >= 0.9 * (1 - 2^-50) > 0.2 (the fast root is within 1.5 ulp;
+//         error_norm = 0 gives pw = inf, hence 10 or 1, the reference's special case);
+//       - rejected, pw not NaN: min(pw, +inf) = pw and max(pw, 0.2) = py_max(0.2, pw); pw >= +0 always (never -0).
+// Rare paths (failure, window, IEEE re-run, outputs) run the code of mm_item_attempt from the uncommitted state.
+__device__ __forceinline__ double pow_minus_fifth_window_core(double x) {   // pow_minus_fifth_core<false>(x, .): same operations
+    const float lf = __builtin_amdgcn_logf((float)x);
+    const double y = (double)__builtin_amdgcn_exp2f(-0.2f * lf);
+    const double y2 = y * y;
+    const double y5 = (y2 * y2) * y;
+    const double rho = fma(-x, y5, 1.0);
+    // fma(0.12, rho, 0.2) in its three-address form: the compiler picks the accumulate form and copies 0.2 in front of it
+    double c;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(c) : "s"(0.12), "v"(rho), "v"(0.2));
+    return fma(y * rho, c, y);
+}
+template <bool WRITE_PRED, bool SHARE>
+__device__ __forceinline__ int mm_item_attempt_lane(MMItem &it, const double2 *s_tp, int n_t, double rtol, double atol,
+                                                    double *pred, double *sum2_word = nullptr) {
+    constexpr int DIV = kDivLean6;
+    const bool fail = it.h_abs < it.min_step || it.attempts >= RK_MAX_ATTEMPTS;
+    const double t = it.t, y = it.y, negVmax = it.negVmax, Km = it.Km;
+    const double t_new = raw_min(t + it.h_abs, it.t_bound);     // rk.py:137-141
+    const double h = t_new - t;
+    it.h_abs = fabs(h);
+
+    const double k0 = it.f;
+    RkStages st = rk_attempt_core<DIV, true>(y, k0, h, negVmax, Km, rtol, atol);
+    ++it.attempts;
+
+    double pw = 0.9 * pow_minus_fifth_window_core(st.error_norm);
+    bool accept = st.error_norm < 1.0;
+    // outside pow_minus_fifth's window, the same set as its exponent test: error_norm = |.| is < 2^-64 (0 included), >= 2^64, or NaN
+    const bool outside = !(st.error_norm >= 0x1p-64) || !(st.error_norm < 0x1p64);
+    if (fail || outside || (accept && it.t_next <= t_new)) {
+        SMC_RK45_MARK("off_path rare_branch");
+        if (fail) return 2;
+        if (outside) {
+            if (!__builtin_isfinite(st.error_norm)) {   // NaN / inf from the lean division
+                st = rk_attempt_core<kDivIeee>(y, k0, h, negVmax, Km, rtol, atol);
+                accept = st.error_norm < 1.0;
+            }
+            pw = py_max(0.0, 0.9 * pow_minus_fifth<false>(st.error_norm));   // NaN -> 0: see above
+        }
+        if (accept && it.t_next <= t_new) mm_attempt_outputs<WRITE_PRED, DIV, SHARE>(it, s_tp, st, k0, t, t_new, y, pred, n_t, sum2_word);
+    }
+    const int hi_accepted = it.rejected ? 0x3ff00000 : 0x40240000;              // 1.0 : 10.0
+    const double hi = __hiloint2double(accept ? hi_accepted : 0x7ff00000, 0);   // rejected: +inf
+    it.h_abs *= raw_max_s(raw_min(pw, hi), 0.2);
+    it.rejected = !accept;
+    it.t = accept ? t_new : t;
+    it.y = accept ? st.y_new : y;
+    it.f = accept ? st.k6 : k0;
     it.min_step = min_step_of(it.t);
     it.h_abs = (accept && it.h_abs < it.min_step) ? it.min_step : it.h_abs;
     return (accept && (t_new - it.t_bound >= 0)) ? 1 : 0;  // base.py:196

@@ -190,6 +190,8 @@ int smc_create(smc_ctx **out, int device, int64_t n_local, int64_t n_global, int
         c->share_env_off = e ? atoi(e) == 0 : false;
         e = getenv("SMC_START_REJECT");         // the same for smc_set_start_reject
         c->start_reject_env_off = e ? atoi(e) == 0 : false;
+        e = getenv("SMC_BULK_ATTEMPT");         // 0 = the per-lane attempt in the form of mm_item_attempt (mm_kernels.hip: LANE_FORM)
+        c->bulk_attempt_form0 = e ? atoi(e) == 0 : false;
     }
 #define CK(call)                                   \
     do {                                           \

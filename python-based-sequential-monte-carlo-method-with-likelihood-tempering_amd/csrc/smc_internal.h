@@ -323,6 +323,7 @@ struct smc_ctx {
     // replicate experiments (replicate_groups.h): solve groups of the data set, as (primary, partner or -1) pairs on host and device
     int share_replicates = 1;              // one integration per group (smc_set_share_replicates) ...
     bool share_env_off = false;            // ... unless the environment says SMC_SHARE_REPLICATES=0
+    bool bulk_attempt_form0 = false;       // SMC_BULK_ATTEMPT=0: default-mode solve kernels with mm_item_attempt at the per-lane call sites
     int n_solve = 0, partner_mask = 0;
     int groups[2 * smc::kMaxEx]{};
     int *d_groups = nullptr;

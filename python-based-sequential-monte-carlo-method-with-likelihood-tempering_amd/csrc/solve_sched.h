@@ -35,6 +35,8 @@
 //                                        particle of the list (from_list == false) - it has been handed out already
 //   void pack(const Item &, double *slot)   / void unpack(Item &, const double *slot)     slot[w * 64], w < kPoolWords
 //   int  attempt(Item &)                 one step attempt; 0 = still running, anything else = finished / failed
+//   int  attempt_lane(Item &)            the same attempt (same results) where every lane runs its own item - the bulk loop and the
+//                                        lane tail: an Ops may give it a form with fewer vector instructions, or forward to attempt()
 //   int  uniform_attempts(Item &, int n) up to n attempts of an item whose state is wave-uniform, stopping at the first that
 //                                        does not return 0; returns the last status (uniform_attempts_plain() below, or better)
 //   void finish(Item &, int status)      publish the result
@@ -67,7 +69,8 @@
 #ifndef SMC_STIFF_PER_CHUNK
 #define SMC_STIFF_PER_CHUNK 16
 #endif
-#ifdef SMC_ISA_MARKS   // analysis builds only (tools/isa_blocks.py): names the loops in the `hipcc -S` listing
+#ifdef SMC_ISA_MARKS   // analysis builds only (tools/bulk_loop_report.py): names the loops in the `hipcc -S` listing; a mark that
+                       // begins with "off_path" stands at the head of code that an attempt with no output due does not execute
 #define SMC_ISA_MARK(name) asm volatile("; MARK " name)
 #else
 #define SMC_ISA_MARK(name)
@@ -346,7 +349,7 @@ __device__ __forceinline__ void solve_persistent(Ops &ops, unsigned long long *q
                     }
                     if (live) {
                         SMC_ISA_MARK("lane_tail_attempt");
-                        const int st = ops.attempt(it);
+                        const int st = ops.attempt_lane(it);
                         if (st != 0) {
                             ops.finish(it, st);
                             live = false;
@@ -365,16 +368,25 @@ __device__ __forceinline__ void solve_persistent(Ops &ops, unsigned long long *q
         do {
             SMC_ISA_MARK("bulk_attempt");
             if (live) {
-                const int st = ops.attempt(it);
+                const int st = ops.attempt_lane(it);
                 if (st != 0) {
+                    SMC_ISA_MARK("off_path item_finished");
                     ops.finish(it, st);
                     live = false;
                 }
             }
-            idle_now = kWave - __popcll(__ballot(live));
-            waited += (idle_now >= kRefillAt);                      // scalar
+            // The count of a ballot is a scalar, and the tests below are kept scalar too: 32-bit counts (the count of the 64-bit
+            // mask is a 64-bit value to the compiler, and the scalar unit has no ordered 64-bit comparison), and "the wave can
+            // hand out" as a 0 / 1 word in a scalar register whose origin the compiler does not see (as a comparison it becomes a
+            // 64-bit lane mask, and its 0 / 1 comes back through v_cndmask and v_readfirstlane).  Before: v_cmp_lt_u64, v_cndmask,
+            // v_readfirstlane and v_cmp_gt_u64 in every attempt.
+            const unsigned long long live_mask = __ballot(live);
+            idle_now = kWave - (int)(__builtin_popcount((unsigned)live_mask) + __builtin_popcount((unsigned)(live_mask >> 32)));
+            int can_hand_out = (int)((unsigned)(kRefillAt - 1 - idle_now) >> 31);   // idle_now >= kRefillAt
+            asm("" : "+s"(can_hand_out));
+            waited += can_hand_out;
             // waiting for ALL lanes makes sense only while none of them is a straggler (looked at only once the wave could hand out)
-            if (patience > 0 && idle_now >= kRefillAt && __ballot(live && ops.long_running(it)) != 0ull) waited = patience + 1;
+            if (patience > 0 && can_hand_out != 0 && __ballot(live && ops.long_running(it)) != 0ull) waited = patience + 1;
         } while (idle_now < kRefillAt || (idle_now < kWave && waited <= patience));
     }
 }

@@ -262,6 +262,7 @@ struct Ops {
         if (it.attempts >= 0x1fffffffu) it.s.status = -1;        // hard bound so that every wave drains
         return it.s.status;
     }
+    __device__ __forceinline__ int attempt_lane(Item &it) const { return attempt(it); }
     __device__ __forceinline__ int uniform_attempts(Item &it, int budget) const { return smc::uniform_attempts_plain(*this, it, budget); }
     __device__ __forceinline__ bool long_running(const Item &it) const { return it.attempts > 64u; }
     __device__ __forceinline__ long long positions() const { return n_pos; }
