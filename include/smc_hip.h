@@ -350,14 +350,19 @@ typedef struct smc_user_model_spec {
      *   Data: a finite value of a count output is a non-negative integer <= 2^53; NaN is "not measured" as ever.
      *   Likelihood (user_models.count_loglik is the definition in NumPy; y = obs, mu = f):
      *     Poisson   log p = -c(y) - x,  c(y) = lgamma(y + 1) - y log y + y (the saturated model: a data constant, summed per experiment
-     *               on the host as C_e),  x = y (d - log1p(d)), d = (mu - y) / y  (d < -1/2: log mu - log y for log1p(d));  x = mu for y = 0
-     *     neg. binomial  u = b^2 mu, phi = 1 / b^2:  x = -log p = -[lgamma(y + phi) - lgamma(phi) - lgamma(y + 1) - phi log1p(u) + y log u - y log1p(u)]
+     *               on the host as C_e),  x = bd0(y, mu) = y log(y / mu) + mu - y;  x = mu for y = 0
+     *     neg. binomial  log p = -x;  u = b^2 mu, phi = 1 / b^2, n = phi + y, n p = n / (1 + u), n q = mu (1 + b^2 y) / (1 + u), L = log1p(b^2 y):
+     *               x = L - [stirlerr(n) - stirlerr(phi) - stirlerr(y) - bd0(phi, n p) - bd0(y, n q)] - 1/2 [L - log(2 pi y)];  y = 0: phi log1p(u)
+     *     Loader's saddle-point form: bd0(x, m) = x log(x / m) + m - x, by its series in (x - m) / (x + m) where |x - m| < 0.1 (x + m);
+     *               stirlerr(n) = lgamma(n + 1) - (n + 1/2) log n + n - 1/2 log(2 pi), as written up to n = 15, by its series above
      *   x is clamped at >= 0; mu NaN gives NaN (a failed output's route); mu < 0, mu = +inf, or mu = 0 with y > 0 give logL = -inf;
      *   mu = 0 with y = 0 gives x = 0; any b_k < 0, or b_k <= 0 on a negative-binomial output: logL = -inf.  m_e, m_ek count Gaussian
      *   quantified values only:   lk = sum_e [ (-m_e / 2) log(2 pi) - sum_k m_ek log(a_k s_k) - C_e - X_e ].
-     * The Poisson form needs no lgamma on the device and does not cancel at large counts.  Below b around 1e-4 the lgamma difference
-     * of the negative binomial loses digits: declare the output Poisson, or keep the prior off 0 (a gamma or
-     * log-normal prior does: PRIOR FAMILIES at smc_set_prior_ex).  Early rejection stays exact (the
+     * In this form no large numbers cancel and no lgamma of an argument above 16 is taken: every term is within 1e-11 max(1, |term|)
+     * of its 60-digit value for counts up to 2^53, means from 1e-300 y to 1e5 y and b from 10 down to 1e-6, where the negative
+     * binomial has become the Poisson (tests/test_likelihood_terms_truth.py).  Below b = 1e-7 phi + y no longer holds a small y:
+     * declare the output Poisson, or keep the prior off 0 (a gamma or log-normal prior does: PRIOR FAMILIES at smc_set_prior_ex).
+     * Early rejection stays exact (the
      * floors do not depend on the solve); the LDS table does not grow.  smc_user_predict returns lk under this
      * likelihood, designs give the mean; smc_user_predict_summary with noise = 1 is refused (it draws Gaussian noise only), noise = 2
      * draws replicated counts, and smc_user_pointwise_summary_opt ranks the observed counts among them (the PIT).

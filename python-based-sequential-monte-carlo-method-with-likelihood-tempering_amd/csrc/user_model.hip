@@ -28,6 +28,7 @@
 #include "stage_kernels.h" // launch_aos_to_soa (smc_user_predict)
 #include "user_censor.h"   // censored observations (smc_set_model_user7)
 #include "user_count.h"    // count observations (smc_user_obs_family)
+#include "count_floor.h"   // ... and the floor of a Poisson term, host code
 #include "user_obs_args.h" // several outputs, missing values, ragged rows, predictions (smc_set_model_user3)
 #include "predictive_kernels.h"   // smc_user_predict_summary's kernels
 #include "pointwise_kernels.h"    // smc_user_pointwise, smc_user_pointwise_summary
@@ -756,15 +757,7 @@ static std::vector<double> count_mek(const double *t, const double *obs, int n_e
     return mek;
 }
 
-// c(y) = lgamma(y + 1) - y log y + y, minus the log-probability of the saturated Poisson model at the count y (user_count.h;
-// user_models.count_floor is the same in NumPy): as written up to y = 32, where nothing cancels yet, and from there on by its
-// Stirling series 1/2 log(2 pi y) + 1/(12 y) - 1/(360 y^3) + 1/(1260 y^5) - 1/(1680 y^7), whose next term is below 1e-16 - the
-// three terms of the definition reach 1e7 at y = 1e6 and would leave c(y), a number below 10, with an error of 1e-9.
-static double count_floor(double y) {
-    if (y < 32.0) return y > 0.0 ? (std::lgamma(y + 1.0) - y * std::log(y)) + y : 0.0;
-    const double r = 1.0 / y, r2 = r * r;
-    return 0.5 * std::log(6.283185307179586 * y) + r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
-}
+using smc_cnt_host::count_floor;      // c(y), the floor of a Poisson term (count_floor.h)
 // C_e: the sum of c(y) over the Poisson values of experiment e, for data the rules have accepted
 static std::vector<double> count_floor_sums(const double *t, const double *obs, int n_ex, int n_t, int n_obs, const int *family) {
     std::vector<double> ce((size_t)n_ex, 0.0);

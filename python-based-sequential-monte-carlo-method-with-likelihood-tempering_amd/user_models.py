@@ -576,18 +576,58 @@ def count_floor(y):
     return np.where(y < 32.0, (gammaln(small + 1.0) - xlogy(small, small)) + small, series)
 
 
+def count_bd0(x, m):
+    """The deviance part of Loader's saddle-point form, bd0(x, m) = x log(x / m) + m - x >= 0 for x > 0 and m > 0, as the kernels
+    form it (csrc/user_count.h: bd0), operation for operation.  With v = (x - m) / (x + m): where |x - m| < 0.1 (x + m) the series
+    (x - m) v + 2 x (v^3 / 3 + v^5 / 5 + ... + v^19 / 19) - every term has one sign, nothing cancels, and the first term left out is
+    below 1e-18 of the sum; elsewhere x L + (m - x) with L = log(x / m), or log x - log m for m < x / 2 (the same number, where
+    x / m may overflow).  Exactly 0 at m = x."""
+    import numpy as np
+    x, m = np.asarray(x, dtype=np.float64), np.asarray(m, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        d = x - m
+        s = x + m
+        v = d / s
+        v2 = v * v
+        p = 1.0 / 19.0
+        for c in (17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0):
+            p = p * v2 + 1.0 / c
+        series = d * v + ((2.0 * x) * v) * (v2 * p)
+        low = m < 0.5 * x
+        l = np.where(low, np.log(x) - np.log(m), np.log(x / m))
+        return np.where(np.abs(d) < 0.1 * s, series, x * l + (m - x))
+
+
+def count_stirlerr(n):
+    """The remainder of Stirling's formula, stirlerr(n) = gammaln(n + 1) - (n + 1/2) log n + n - 1/2 log(2 pi) for n > 0, as the
+    kernels form it (csrc/user_count.h: stirlerr), operation for operation: as written up to n = 15 (its terms stay below 45, an
+    absolute error of 1e-14), above by the series 1/(12 n) - 1/(360 n^3) + 1/(1260 n^5) - 1/(1680 n^7) + 1/(1188 n^9) -
+    691/(360360 n^11) + 1/(156 n^13), whose next term is below 1e-19 at n = 15."""
+    import numpy as np
+    from scipy.special import gammaln
+    n = np.asarray(n, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        small = np.where(n <= 15.0, n, 1.0)
+        direct = ((gammaln(small + 1.0) - (small + 0.5) * np.log(small)) + small) - 0.9189385332046727
+        r = 1.0 / np.where(n <= 15.0, 16.0, n)
+        r2 = r * r
+        series = r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0 - r2 * (1.0 / 1188.0 - r2 * (
+            691.0 / 360360.0 - r2 * (1.0 / 156.0)))))))
+    return np.where(n <= 15.0, direct, series)
+
+
 def count_excess(y, mu, b, family):
     """x >= 0, the excess of a count term over its floor (include/smc_hip.h: COUNT OBSERVATIONS), as the kernels form it
     (csrc/user_count.h), operation for operation.  y the count, mu the model's mean, b the overdispersion, family 1 (Poisson: log
-    p = -count_floor(y) - x, b is not used) or 2 (negative binomial: log p = -x).  Arrays broadcast; family is one number.
-      Poisson:  x = y (d - L), d = (mu - y) / y, L = log1p(d) for d >= -1/2 and log mu - log y below (the same number, without
-                losing a mu below y 2^-53);  x = mu for y = 0.
-      negative binomial, u = b^2 mu, phi = 1 / b^2:
-                x = -[gammaln(y + phi) - gammaln(phi) - gammaln(y + 1) - phi log1p(u) + y log u - y log1p(u)];  y = 0: phi log1p(u).
+    p = -count_floor(y) - x, b is not used) or 2 (negative binomial: log p = -x).  Arrays broadcast; family is one number.  Both
+    are written in Loader's saddle-point form (count_bd0, count_stirlerr), in which no large numbers cancel:
+      Poisson:  x = bd0(y, mu);  x = mu for y = 0.
+      negative binomial, u = b^2 mu, phi = 1 / b^2, n = phi + y, n p = n / (1 + u), n q = mu (1 + b^2 y) / (1 + u), L = log1p(b^2 y):
+                x = L - [stirlerr(n) - stirlerr(phi) - stirlerr(y) - bd0(phi, n p) - bd0(y, n q)] - 1/2 [L - log(2 pi y)];
+                y = 0: phi log1p(u).
     Both: clamped at >= 0; NaN for mu NaN; +inf for mu < 0, mu = +inf, or mu = 0 with y > 0; 0 for mu = 0 with y = 0.  A negative
     binomial b that is not > 0 gives 0 (such parameters have logL = -inf, which count_loglik decides)."""
     import numpy as np
-    from scipy.special import gammaln
     family = int(family)
     if family not in (1, 2):
         raise ValueError(f"count_excess: family {family} is neither 1 (Poisson) nor 2 (negative binomial)")
@@ -597,10 +637,7 @@ def count_excess(y, mu, b, family):
     safe_y = np.where(y > 0, y, 1.0)
     with np.errstate(all="ignore"):
         if family == 1:
-            d = (safe_mu - safe_y) / safe_y
-            low = d < -0.5
-            l = np.where(low, np.log(safe_mu) - np.log(safe_y), np.log1p(np.where(low, 0.0, d)))
-            x = safe_y * (d - l)
+            x = count_bd0(safe_y, safe_mu)
             x = np.where(y == 0, mu, x)
         else:
             ok_b = b > 0
@@ -609,8 +646,14 @@ def count_excess(y, mu, b, family):
             u = b2 * safe_mu
             l1 = np.log1p(u)
             pl = phi * l1
-            g = (gammaln(safe_y + phi) - gammaln(phi)) - gammaln(safe_y + 1.0)
-            x = -(((g - pl) + safe_y * np.log(u)) - safe_y * l1)
+            n = phi + safe_y
+            den = 1.0 + u
+            b2y = b2 * safe_y
+            ly = np.log1p(b2y)
+            n_p = n / den
+            n_q = safe_mu * ((1.0 + b2y) / den)
+            lc = (((count_stirlerr(n) - count_stirlerr(phi)) - count_stirlerr(safe_y)) - count_bd0(phi, n_p)) - count_bd0(safe_y, n_q)
+            x = (ly - lc) - 0.5 * (ly - np.log(6.283185307179586 * safe_y))
             x = np.where(y == 0, np.where(mu == 0, 0.0, pl), x)
         x = np.where(x < 0, 0.0, x)
         x = np.where(inf_case, np.inf, x)

@@ -9,7 +9,7 @@ both entry points' sizes), real models against predict_user's lk, the per-cell s
 a closed form at n = 65536, staging groups and repeated calls bit for bit, and run_smc(pointwise=True) on one and several ranks.
 
 Measured on an MI355X (worst |device - definition| / max(1, |l|) per family, planted values, bar 1e-9): Gaussian
-4.4e-16, left-censored 1.1e-15, right-censored 1.0e-15, Poisson 5.5e-15, negative binomial 1.4e-12.  Real models, nansum(ll)
+4.4e-16, left-censored 1.1e-15, right-censored 1.0e-15, Poisson 5.5e-15, negative binomial 6.7e-15 (1.4e-12 with the lgamma form).  Real models, nansum(ll)
 against predict_user's lk: 6.9e-14 at worst.  Closed form: lpd off by 1.9 se, pit by 1.7e-3."""
 import ctypes
 import os
@@ -304,7 +304,7 @@ def _family_of_cells(d, shape):
 def test_device_terms_are_the_definition_on_the_devices_own_predictions(pkg, name, cells):
     """Planted values: the device's ll against pointwise_loglik of the device's own pred; the NaN and -inf masks exactly equal and
     |delta| <= 1e-9 max(1, |l|) per term.  n_local = 2048, so 2049 and 5000 host particles run in chunks.
-    Measured: Gaussian 4.4e-16, left 1.1e-15, right 1.0e-15, Poisson 5.5e-15, negative binomial 1.4e-12 (264 cells)."""
+    Measured: Gaussian 4.4e-16, left 1.1e-15, right 1.0e-15, Poisson 5.5e-15, negative binomial 6.7e-15 (264 cells; 1.4e-12 with the lgamma form)."""
     um = pkg.user_models
     v = PM.VARIANTS[name]
     worst = {}
